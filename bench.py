@@ -14,14 +14,19 @@ N > 1   : launched by torch.distributed.run, one rank per GPU. The 5M-row corpus
           own questions. Per-GPU work is then constant in N (100 sequences through the encoder; rows/N x queries*N
           through the MIPS). --scaling strong keeps ONE 100-question batch and splits the encoder slices instead; a
           10 ms step of 2 x 12 dependent transformer layers is latency-bound there (NEGATIVE_RESULTS.md §3.6).
-Prints ONE JSON line on rank 0 with
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if --dump-outputs DIR is given, and prints
+ONE JSON line on rank 0 with the headline (metric, value, unit, higher_is_better, dtype, ms_per_step) and the figures read off
+the timed steps themselves:
   roofline          the MIPS kernel (HBM-bound): PHYSICAL HBM bytes per search call / HIP-event time of the call on the launch
                     stream / 8 TB/s. The screen kernels stream only the int8 screening plane (beam = 1: 776 B per row) or the
                     fp16 hi plane of the fp32-accurate index, so the fp32-equivalent ("algorithmic", SURVEY.md §8d:
                     N x d x 4 bytes) rate is a SEPARATE key, never `frac`.
   roofline_encoder  the encoder (MFMA-bound, the larger share of the step): executed FLOPs / stage time / 2.5 PFLOP/s.
+--full adds everything that needs work of its own after the timed steps:
   self_check        structural properties + `full_size_exact`: after the timed region every row of the 5M corpus is
                     re-scored with a plain torch matmul and compared with what the kernels returned.
+  sequential        the same job one batch at a time; numerics_modes: the encoder's other residual-stream modes (N = 1).
+  anisotropic, structured   the k = 1 search on corpora shaped unlike i.i.d. noise (N = 1).
   cpu_baseline      the FAISS-equivalent CPU path on a bounded row sample (N = 1 only).
   strong_scaling    (N > 1, default weak scaling) the same job with ONE --batch questions for all ranks.
 
@@ -34,6 +39,7 @@ csrc/mdr_mips* at measurement time) is applied to this run's algorithmic bytes -
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -108,6 +114,12 @@ def parse():
                     help="token lengths of the synthetic passages behind the encoder-geometry sub-result (short by default so that the default run stays within "
                          "minutes: 5 M passages = ~15 s; profiles/r06_structured_full_length.json is the same at 20..300 tokens)")
     ap.add_argument("--dump-ids", default=None, help="rank 0 writes the last step's hop-1 / hop-2 ids and scores to this .npz (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes every array the last timed step returned as DIR/<name>.npy (float32, or float64 for ids and masks; a fixed, seeded "
+                         "row sample of each when they exceed 64 MB in all): two builds compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: self-checks incl. the full-size brute-force exactness check, the sequential, numerics-mode and "
+                         "strong-scaling sub-results, the anisotropic and structured corpora, the CPU baseline (each still subject to its --no-* flag)")
     ap.add_argument("--no-strong", action="store_true", help="N>1, weak scaling: do not append the strong-scaling sub-result")
     ap.add_argument("--mode", choices=["retrieval", "encode-corpus", "cli", "structured"], default="retrieval",
                     help="encode-corpus: throughput of the corpus encoder (scripts/encode_corpus.py path) on a synthetic pre-tokenised corpus; "
@@ -495,6 +507,28 @@ def timed_steps(pipe, args, world, device, dist):
     return out, elapsed
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, dirname):
+    """--dump-outputs: every array of the dict the last timed step() returned, as DIR/<name>.npy -- floating point as float32, ids and masks as
+    float64 (exact below 2**53). Beyond 64 MB in all, each array keeps a fixed, seeded sample of its rows (sorted), the same from run to run."""
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {}
+    for name, t in out.items():
+        if t is None:
+            continue
+        a = t.detach().cpu().numpy()
+        arrs[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "iub" else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        for name, a in arrs.items():
+            n = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES / total))
+            arrs[name] = a[np.sort(np.random.default_rng(0).choice(a.shape[0], n, replace=False))]
+    for name, a in arrs.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def encode_corpus_mode(args):
     """Secondary measurement: passages/s of the corpus encoder on one GPU -- encode_corpus.predict() driven by
     length-bucketed windows of a synthetic pre-tokenised corpus (title+text pairs of 20..300 tokens, max_c_len 300), embeddings
@@ -745,8 +779,9 @@ def cli_mode(args):
         print(json.dumps(result), flush=True)
 
 def self_launch(args):
-    """`python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): re-exec this very command line under
-    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>` so that N ranks exist, one per GPU.
+    """`python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): run this very command line in a child process under
+    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>` so that N ranks exist, one per GPU,
+    and exit with its status. A child, not an exec: this process has already initialised the HIP runtime.
     Under a launcher (WORLD_SIZE set) nothing happens here, and a WORLD_SIZE that disagrees with --gpus is an error, not a warning: a scaling record
     whose n_gpus is not what was asked for is void. Fewer than N visible devices is an error too (unless --share-gpu, the one-GPU debugging mode)."""
     if args.mode in ("encode-corpus", "structured"):
@@ -777,11 +812,13 @@ def self_launch(args):
         env.pop(k, None)  # the launcher sets its own
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: RCCL across processes needs it on this driver
     env.setdefault("OMP_NUM_THREADS", str(max(1, len(os.sched_getaffinity(0)) // args.gpus)))
-    os.execvpe(sys.executable, cmd, env)
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def main():
     args = parse()
+    if args.dump_outputs and args.mode != "retrieval":
+        raise SystemExit(f"bench.py: --dump-outputs writes the outputs of the retrieval loop; --mode {args.mode} does not run it")
     self_launch(args)
     if args.mode == "encode-corpus":
         return encode_corpus_mode(args)
@@ -827,15 +864,19 @@ def main():
                                 use_encoder=not args.no_encoder, planted_rows=rows_sum, rank=rank, world=world, weak=weak,
                                 pipelined=not args.sequential, pool=args.pool)
     out, elapsed = timed_steps(pipe, args, world, device, dist)
+    if args.dump_outputs and rank == 0:  # before anything else runs: later encoder calls may reuse the buffers these views point into
+        dump_outputs(out, args.dump_outputs)
 
-    # self-checks, outside the timed region: structural properties + exactness against a brute-force pass over ALL rows
-    ok = pipe.self_check(out, planted)
-    if not args.no_verify:
-        ok.update(verify_full_size(out, lo, hi, N, d, device, args.beam, bf16_rows=args.storage == "bf16"))
-        if world > 1:  # a shard only sees its own rows: the claim holds when it holds on every rank
-            flag = torch.tensor([1.0 if ok["full_size_exact"] else 0.0], device=device)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            ok["full_size_exact"] = bool(flag.item() > 0.5)
+    # self-checks (--full), outside the timed region: structural properties + exactness against a brute-force pass over ALL rows
+    ok = None
+    if args.full:
+        ok = pipe.self_check(out, planted)
+        if not args.no_verify:
+            ok.update(verify_full_size(out, lo, hi, N, d, device, args.beam, bf16_rows=args.storage == "bf16"))
+            if world > 1:  # a shard only sees its own rows: the claim holds when it holds on every rank
+                flag = torch.tensor([1.0 if ok["full_size_exact"] else 0.0], device=device)
+                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+                ok["full_size_exact"] = bool(flag.item() > 0.5)
 
     if args.dump_ids and rank == 0:
         np.savez(args.dump_ids, I=out["I"].cpu().numpy(), I2=out["I2"].cpu().numpy(), D=out["D"].cpu().numpy(), D2=out["D2"].cpu().numpy())
@@ -864,9 +905,10 @@ def main():
                         "corpus pass (every batch still walks the full hop-1 -> hop-2 chain; see `sequential` for the unpipelined loop)") if pipe.pipelined
                        else "sequential: one batch at a time, four dependent stages")},
         "roofline": roofline,
-        "self_check": ok,
         "stage_ms": stage,
     }
+    if ok is not None:
+        result["self_check"] = ok
     if pipe.use_encoder:
         # ---- second roofline entry: the encoder (MFMA-bound), the larger share of the step --------------------------------
         # executed FLOPs averaged over the timed steps (the pool's batches differ): hop 1 from each step's question lengths, hop 2 from the lengths its
@@ -929,7 +971,7 @@ def main():
     result["stage_share"] = {"encoder": round((stage.get("hop1_encode", 0) + stage.get("hop2_encode", 0)) / ms_per_step, 3),
                              "mips": round((stage.get("hop1_search", 0) + stage.get("hop2_search", 0)) / ms_per_step, 3)}
 
-    if pipe.pipelined and not args.no_sequential:
+    if args.full and pipe.pipelined and not args.no_sequential:
         # the same job, one batch at a time (the loop exactly as the reference writes it): sub-result of the same line
         mhop.SyntheticTwoHop._defer_encoder = True  # share the encoder and the arena of the main pipeline
         pipe_q = mhop.SyntheticTwoHop(sidx, batch=B, beam=args.beam, topk=args.topk, dim=d, device=device, max_q_len=args.max_q_len,
@@ -943,7 +985,7 @@ def main():
                                 "stage_ms": pipe_q.stage_ms(), "mips_roofline": mips_roofline(pipe_q, local, args, d)}
         del pipe_q
 
-    if pipe.pipelined and pipe.use_encoder and world == 1 and not args.no_sequential:
+    if args.full and pipe.pipelined and pipe.use_encoder and world == 1 and not args.no_sequential:
         # the same job in the encoder's OTHER residual-stream numerics modes (mdr_encoder_config.residual_fp32; the headline runs the default, an
         # apex-O1-faithful one: DESIGN.md section 4): what each costs and how far its embeddings are from the default's -- sub-results of the same line
         from multihop_dense_retrieval_amd.retriever import RobertaRetriever
@@ -978,7 +1020,7 @@ def main():
                 "hop1_ids_equal_to_default": bool((out_r["I"] == out["I"]).all()) if out_r["I"].shape == out["I"].shape else None}
             del pipe_r, enc_m
 
-    if world > 1 and weak and not args.no_strong:
+    if args.full and world > 1 and weak and not args.no_strong:
         # The same job with ONE 100-question batch shared by all ranks (the reference's fixed --batch-size): a sub-result of
         # the same JSON line, so a scaling run carries the strong-scaling number next to the weak one.
         mhop.SyntheticTwoHop._defer_encoder = True
@@ -993,13 +1035,13 @@ def main():
         result["strong_scaling"] = {"value": round(B * args.steps / el_s, 2), "unit": "queries/s", "ms_per_step": round(el_s / args.steps * 1e3, 4),
                                     "global_batch": B, "note": "one batch of --batch questions for all ranks: encoder slices split over ranks + all-gather"}
 
-    # (part of the full default line only: diagnostic invocations -- --no-cpu-baseline / --no-verify / --no-encoder -- skip it)
-    if (rank == 0 and world == 1 and not args.no_anisotropic and args.beam == 1 and args.storage != "bf16" and d == 768
+    # (part of the complete --full line only: diagnostic invocations -- --no-cpu-baseline / --no-verify / --no-encoder -- skip it)
+    if (args.full and rank == 0 and world == 1 and not args.no_anisotropic and args.beam == 1 and args.storage != "bf16" and d == 768
             and not (args.no_cpu_baseline or args.no_verify or args.no_encoder)):
         result["anisotropic"] = anisotropic_subresult(args, device)
         if args.structured:
             result["structured"] = structured_subresult(args, device)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, device, gpu_index=local)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -8,7 +8,7 @@ cd /tmp
 for PMC in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS" "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS" \
            "SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" "SQ_INSTS_VALU_MFMA_MOPS_I8 SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM"; do
   D=/tmp/pq_$$; rm -rf $D
-  timeout 400 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $D -o p -- python $REPO/bench.py --rows 5000000 --steps 3 --warmup 1 --no-encoder --no-cpu-baseline --no-verify > /tmp/pq.log 2>&1 || { echo "pass [$PMC] failed: $(tail -2 /tmp/pq.log | tr '\n' ' ')" >> $OUT/i8_pmc_sq.txt; continue; }
+  timeout 400 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $D -o p -- python $REPO/bench.py --full --rows 5000000 --steps 3 --warmup 1 --no-encoder --no-cpu-baseline --no-verify > /tmp/pq.log 2>&1 || { echo "pass [$PMC] failed: $(tail -2 /tmp/pq.log | tr '\n' ' ')" >> $OUT/i8_pmc_sq.txt; continue; }
   P=$(find $D -name "*counter_collection.csv" | head -1)
   python - "$P" >> $OUT/i8_pmc_sq.txt <<'PY'
 import csv, sys, collections

@@ -6,7 +6,7 @@ cd /tmp
 rocprofv3 -L 2>/dev/null | grep -o -E "SQ_[A-Z_0-9]+" | sort -u | tr '\n' ' ' > $OUT/sq_counters.txt
 for PMC in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES" "SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_MISC SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM" "SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_SALU" "GRBM_GUI_ACTIVE"; do
   N=$(echo $PMC | tr ' ' '_' | cut -c1-40)
-  MDR_GEMM_CFG=${2:-0} timeout 300 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $OUT/p -o p -- python $REPO/bench.py --rows 1000000 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/log_$N.txt 2>&1
+  MDR_GEMM_CFG=${2:-0} timeout 300 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $OUT/p -o p -- python $REPO/bench.py --full --rows 1000000 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/log_$N.txt 2>&1
   P=$(find $OUT/p -name "*counter_collection.csv" | head -1)
   [ -n "$P" ] && python - "$P" <<'PY'
 import csv, sys, collections

@@ -3,7 +3,7 @@ set -u
 TAG=${1:-pmcl2}; REPO=$(pwd); OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 cd /tmp
 for PMC in "FETCH_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_REQ_sum" "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum"; do
-  timeout 300 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $OUT/p -o p -- python $REPO/bench.py --rows 1000000 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/log.txt 2>&1
+  timeout 300 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $OUT/p -o p -- python $REPO/bench.py --full --rows 1000000 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/log.txt 2>&1
   P=$(find $OUT/p -name "*counter_collection.csv" | head -1)
   [ -n "$P" ] && python - "$P" <<'PY'
 import csv, sys, collections

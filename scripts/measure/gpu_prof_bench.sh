@@ -3,7 +3,7 @@
 set -u
 TAG=${1:-profb}; shift || true; REPO=$(pwd); OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python $REPO/bench.py --steps 10 --warmup 2 --no-cpu-baseline "$@" > $OUT/stats.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python $REPO/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline "$@" > $OUT/stats.log 2>&1
 grep '"metric"' $OUT/stats.log | python -c "
 import json,sys
 r=json.loads(sys.stdin.read()); print(r['value'], r['ms_per_step'], r['stage_ms'])"

@@ -3,7 +3,7 @@
 set -u
 TAG=${1:-prof}; ROWS=${2:-2000000}; BATCH=${3:-100}; REPO=$(pwd); OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python $REPO/bench.py --rows $ROWS --steps 20 --warmup 3 --no-encoder --no-cpu-baseline --batch $BATCH > $OUT/stats.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python $REPO/bench.py --full --rows $ROWS --steps 20 --warmup 3 --no-encoder --no-cpu-baseline --batch $BATCH > $OUT/stats.log 2>&1
 grep '"metric"' $OUT/stats.log | python -c "
 import json,sys
 r=json.loads(sys.stdin.read()); print(r['roofline'])"

@@ -5,7 +5,7 @@ TAG=${1:-r03e}; REPO=$(pwd); OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT; export TM
 echo "== pytest encoder"
 timeout 1200 python -m pytest tests/test_encoder_gpu.py tests/test_gemm_gpu.py tests/test_assemble_gpu.py -m gpu -q 2>&1 | grep -v "amdgpu.ids" | tail -4
 echo "== bench (no cpu baseline)"
-timeout 600 python bench.py --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; tail -2 $OUT/bench.err
+timeout 600 python bench.py --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; tail -2 $OUT/bench.err
 python - $OUT/bench.json <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ timeout 1500 python -m pytest tests/test_mips_i8_gpu.py tests/test_mips_fullsize
 grep -E "int8 tier on aniso|screen telemetry|passed|failed|Error|assert" $OUT/pytest_mips.txt | cut -c1-900 | tail -30
 tail -2 $OUT/pytest_mips.txt
 echo "== bench default"
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -3 $OUT/bench_default.err
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -3 $OUT/bench_default.err
 python - $OUT/bench_default.json <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -20,11 +20,11 @@ echo "== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; tail -3 $OUT/smoke.txt
 
 echo "== bench 1M (MIPS only)"
-timeout 600 python bench.py --rows 1000000 --steps 50 --warmup 5 --no-encoder --no-cpu-baseline $EXTRA > $OUT/bench_1m_mips.json 2> $OUT/bench_1m_mips.err; cut -c1-300 $OUT/bench_1m_mips.json
+timeout 600 python bench.py --full --rows 1000000 --steps 50 --warmup 5 --no-encoder --no-cpu-baseline $EXTRA > $OUT/bench_1m_mips.json 2> $OUT/bench_1m_mips.err; cut -c1-300 $OUT/bench_1m_mips.json
 echo "== bench 5M (MIPS only)"
-timeout 900 python bench.py --rows 5000000 --steps 20 --warmup 3 --no-encoder --no-cpu-baseline $EXTRA > $OUT/bench_5m_mips.json 2> $OUT/bench_5m_mips.err; cut -c1-300 $OUT/bench_5m_mips.json
+timeout 900 python bench.py --full --rows 5000000 --steps 20 --warmup 3 --no-encoder --no-cpu-baseline $EXTRA > $OUT/bench_5m_mips.json 2> $OUT/bench_5m_mips.err; cut -c1-300 $OUT/bench_5m_mips.json
 echo "== bench DEFAULT (5M, 2-hop with encoder, cpu baseline, anisotropic sub-result) -- the headline line"
-timeout 900 python bench.py $EXTRA > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -2 $OUT/bench_default.err
+timeout 900 python bench.py --full $EXTRA > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -2 $OUT/bench_default.err
 python - $OUT/bench_default.json <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -40,7 +40,7 @@ PY
 
 echo "== rocprofv3 kernel stats (default bench command, no cpu baseline)"
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -o bench -- python $REPO/bench.py --no-cpu-baseline $EXTRA > $OUT/prof_stats.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -o bench -- python $REPO/bench.py --full --no-cpu-baseline $EXTRA > $OUT/prof_stats.log 2>&1
 S=$(find $OUT/prof_stats -name "*kernel_stats.csv" | head -1); [ -n "$S" ] && (cp "$S" $OUT/kernel_stats.csv; cut -c1-150 "$S" | head -14)
 rm -rf $OUT/prof_stats
 find $OUT -name "*.db" -size +20M -delete 2>/dev/null

@@ -14,9 +14,9 @@ echo "== FETCH_SIZE pass (pmc_traffic.json)"
 PMC_FETCH_ONLY=1 PMC_PROFILE_TAG=r04_mips5m_pmc bash scripts/measure/gpu_pmc_screen.sh $TAG/pmc > $OUT/pmc.log 2>&1; grep "pmc_traffic.json:" $OUT/pmc.log | cut -c1-200
 [ -f $OUT/pmc/pmc_traffic.json ] && cp $OUT/pmc/pmc_traffic.json $REPO/profiles/pmc_traffic.json
 echo "== bench 5M (MIPS only)"
-timeout 900 python bench.py --rows 5000000 --steps 20 --warmup 3 --no-encoder --no-cpu-baseline > $OUT/bench_5m_mips.json 2> $OUT/bench_5m_mips.err; cut -c1-200 $OUT/bench_5m_mips.json
+timeout 900 python bench.py --full --rows 5000000 --steps 20 --warmup 3 --no-encoder --no-cpu-baseline > $OUT/bench_5m_mips.json 2> $OUT/bench_5m_mips.err; cut -c1-200 $OUT/bench_5m_mips.json
 echo "== bench DEFAULT -- the headline line"
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -2 $OUT/bench_default.err
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -2 $OUT/bench_default.err
 python - $OUT/bench_default.json <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -40,7 +40,7 @@ print("ratio", r.get("cli_over_device_loop"), "identical", r.get("legs_jsonl_ide
 PY
 echo "== rocprofv3 kernel stats (default bench command, no cpu baseline)"
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -o bench -- python $REPO/bench.py --no-cpu-baseline --no-anisotropic > $OUT/prof_stats.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -o bench -- python $REPO/bench.py --full --no-cpu-baseline --no-anisotropic > $OUT/prof_stats.log 2>&1
 S=$(find $OUT/prof_stats -name "*kernel_stats.csv" | head -1); [ -n "$S" ] && (cp "$S" $OUT/kernel_stats.csv; cut -c1-150 "$S" | head -12)
 rm -rf $OUT/prof_stats $OUT/pmc/p
 find $OUT -name "*.db" -size +20M -delete 2>/dev/null

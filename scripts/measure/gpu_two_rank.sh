@@ -6,7 +6,7 @@ TAG=${1:-two_rank}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 for extra in "" "--beam 2 --topk 2" "--no-encoder" "--scaling strong" "--sequential"; do
   echo "== bench --gpus 2 (gloo, shared GPU) $extra"
-  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 2 \
+  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29571 bench.py --full --gpus 2 \
       --backend gloo --share-gpu --rows 1000000 --steps 3 --warmup 2 $extra 2> $OUT/err.txt | tail -1 | python -c "
 import sys, json
 r = json.loads(sys.stdin.readline())
@@ -14,8 +14,8 @@ print({k: r.get(k) for k in ('value', 'ms_per_step', 'n_gpus', 'scaling')}, r['s
 " || tail -5 $OUT/err.txt
 done
 echo "== same, one rank (reference ids)"
-python bench.py --rows 1000000 --steps 3 --warmup 2 --no-encoder --no-cpu-baseline --sequential --dump-ids $OUT/one.npz > /dev/null 2>&1
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29572 bench.py --gpus 2 --backend gloo --share-gpu \
+python bench.py --full --rows 1000000 --steps 3 --warmup 2 --no-encoder --no-cpu-baseline --sequential --dump-ids $OUT/one.npz > /dev/null 2>&1
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29572 bench.py --full --gpus 2 --backend gloo --share-gpu \
     --rows 1000000 --steps 3 --warmup 2 --no-encoder --scaling strong --sequential --dump-ids $OUT/two.npz > /dev/null 2>&1
 python -c "
 import numpy as np

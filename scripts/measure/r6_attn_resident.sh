@@ -10,7 +10,7 @@ cd /tmp
 for rep in 1 2; do
   for L in product variant; do
     if [ $L = variant ]; then export MDR_LIB_PATH=$V; else unset MDR_LIB_PATH; fi
-    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$L$rep -o b -- python $REPO/bench.py --no-cpu-baseline --no-sequential > $OUT/bench_$L$rep.json 2> $OUT/bench_$L$rep.err
+    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$L$rep -o b -- python $REPO/bench.py --full --no-cpu-baseline --no-sequential > $OUT/bench_$L$rep.json 2> $OUT/bench_$L$rep.err
     S=$(find $OUT/prof_$L$rep -name "*kernel_stats.csv" | head -1)
     python - "$S" $L $rep $OUT/bench_$L$rep.json <<'PY'
 import csv, json, sys

@@ -10,7 +10,7 @@ echo "== timeline build"
 MDR_LIB_PATH=$REPO/multihop_dense_retrieval_amd/libmdrhip_gemm_timeline.so GEMM_SHAPES=qkv:2304:768:0,ffn1:3072:768:1 timeout 300 python scripts/measure/gpu_gemm_bench.py $M 6 2>&1 | grep -v amdgpu.ids | tee $OUT/timeline.txt
 echo "== in-forward kernel averages (default bench command under rocprofv3)"
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o b -- python $REPO/bench.py --no-cpu-baseline --no-anisotropic --structured > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o b -- python $REPO/bench.py --full --no-cpu-baseline --no-anisotropic --structured > $OUT/bench.json 2> $OUT/bench.err
 S=$(find $OUT/prof -name "*kernel_stats.csv" | head -1); [ -n "$S" ] && cp "$S" $OUT/bench_default_kernel_stats.csv
 python - $OUT/bench_default_kernel_stats.csv <<'PY'
 import csv, sys

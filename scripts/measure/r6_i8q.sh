@@ -15,7 +15,7 @@ done
 echo "== MIPS-only bench (pipelined loop: fused 200-query pass), kernel averages"
 cd /tmp
 for Q in 0 1; do
-  MDR_MIPS_I8Q=$Q timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof$Q -o b -- python $REPO/bench.py --no-encoder --no-cpu-baseline --no-sequential --steps 40 > $OUT/bench_q$Q.json 2> $OUT/bench_q$Q.err
+  MDR_MIPS_I8Q=$Q timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof$Q -o b -- python $REPO/bench.py --full --no-encoder --no-cpu-baseline --no-sequential --steps 40 > $OUT/bench_q$Q.json 2> $OUT/bench_q$Q.err
   S=$(find $OUT/prof$Q -name "*kernel_stats.csv" | head -1)
   python - "$S" $Q $OUT/bench_q$Q.json <<'PY'
 import csv, json, sys

@@ -15,7 +15,7 @@ for M in 0 1 2; do
   MDR_MIPS_EVEN_GROUPS=$M timeout 300 python scripts/measure/r6_groups_ab.py 625000 f32x2h 800:1 400:4 2>&1 | grep groups= | tee -a $OUT/groups.txt
 done
 echo "== bench DEFAULT"
-/usr/bin/time -v timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; grep "Elapsed (wall" $OUT/bench_default.err
+/usr/bin/time -v timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; grep "Elapsed (wall" $OUT/bench_default.err
 python - $OUT/bench_default.json <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

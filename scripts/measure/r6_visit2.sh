@@ -16,7 +16,7 @@ rm -rf $OUT/prof_struct
 cd $REPO
 echo "== bench DEFAULT"
 SECONDS=0
-timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench wall seconds: $SECONDS"
+timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench wall seconds: $SECONDS"
 python - $OUT/bench_default.json <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

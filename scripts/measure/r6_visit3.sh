@@ -24,7 +24,7 @@ for tag in ("cb0", "cb1", "auto"):
 PY
 echo "== anisotropic + default bench"
 SECONDS=0
-timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench wall seconds: $SECONDS"
+timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench wall seconds: $SECONDS"
 python - $OUT/bench_default.json <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -34,7 +34,7 @@ print("seq", r["sequential"]["value"], r["sequential"]["stage_ms"], r["sequentia
 print("self_check", r["self_check"]["full_size_exact"], r.get("mips_tiers"))
 print("aniso", json.dumps(r.get("anisotropic"))[:1500])
 PY
-MDR_MIPS_I8_CB=0 timeout 1200 python bench.py --no-cpu-baseline --structured > $OUT/bench_default_cb0.json 2> $OUT/bench_default_cb0.err
+MDR_MIPS_I8_CB=0 timeout 1200 python bench.py --full --no-cpu-baseline --structured > $OUT/bench_default_cb0.json 2> $OUT/bench_default_cb0.err
 python - $OUT/bench_default_cb0.json <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -1,4 +1,5 @@
-"""CPU: bench.self_launch -- what `python bench.py --gpus N` execs when no launcher is around it, and what it refuses."""
+"""CPU: bench.self_launch -- what `python bench.py --gpus N` starts as a child process when no launcher is around it (never an exec: the process
+has initialised the HIP runtime by then), and what it refuses."""
 import os
 import sys
 import types
@@ -24,6 +25,7 @@ def no_launcher(monkeypatch):
 
 def test_one_gpu_and_launched_runs_do_not_exec(monkeypatch, no_launcher):
     monkeypatch.setattr(os, "execvpe", lambda *a: pytest.fail("must not exec"))
+    monkeypatch.setattr(bench.subprocess, "call", lambda *a, **k: pytest.fail("must not launch"))
     bench.self_launch(_args(gpus=1))
     monkeypatch.setenv("WORLD_SIZE", "8")
     bench.self_launch(_args(gpus=8))  # under torch.distributed.run: nothing to do
@@ -52,10 +54,11 @@ def test_an_exported_world_size_of_one_without_a_launcher_self_launches(monkeypa
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8"])
     seen = {}
 
-    def fake_exec(exe, cmd, env):
+    def fake_call(cmd, env):
         seen.update(cmd=cmd, env=env)
-        raise SystemExit(0)
-    monkeypatch.setattr(os, "execvpe", fake_exec)
+        return 0
+    monkeypatch.setattr(os, "execvpe", lambda *a: pytest.fail("must start a child, not exec"))
+    monkeypatch.setattr(bench.subprocess, "call", fake_call)
     with pytest.raises(SystemExit):
         bench.self_launch(_args(gpus=8))
     assert seen["cmd"][seen["cmd"].index("--nproc-per-node") + 1] == "8" and "WORLD_SIZE" not in seen["env"]
@@ -67,12 +70,14 @@ def test_execs_torch_distributed_run_with_n_ranks(monkeypatch, no_launcher):
     monkeypatch.setattr(bench.torch.cuda, "device_count", lambda: 8)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "5", "--warmup", "2"])
 
-    def fake_exec(exe, cmd, env):
-        seen.update(exe=exe, cmd=cmd, env=env)
-        raise SystemExit(0)
-    monkeypatch.setattr(os, "execvpe", fake_exec)
-    with pytest.raises(SystemExit):
+    def fake_call(cmd, env):
+        seen.update(cmd=cmd, env=env)
+        return 3
+    monkeypatch.setattr(os, "execvpe", lambda *a: pytest.fail("must start a child, not exec"))
+    monkeypatch.setattr(bench.subprocess, "call", fake_call)
+    with pytest.raises(SystemExit) as e:
         bench.self_launch(_args(gpus=8))
+    assert e.value.code == 3  # the child's exit status is this process's
     cmd = seen["cmd"]
     assert cmd[:3] == [sys.executable, "-m", "torch.distributed.run"]
     assert cmd[cmd.index("--nproc-per-node") + 1] == "8" and cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
@@ -86,7 +91,7 @@ def test_fewer_devices_than_ranks_is_refused_unless_shared(monkeypatch, no_launc
     with pytest.raises(SystemExit) as e:
         bench.self_launch(_args(gpus=2))
     assert "only 1 HIP device" in str(e.value)
-    monkeypatch.setattr(os, "execvpe", lambda *a: (_ for _ in ()).throw(SystemExit(0)))
+    monkeypatch.setattr(bench.subprocess, "call", lambda cmd, env: 0)
     with pytest.raises(SystemExit) as e:
         bench.self_launch(_args(gpus=2, share_gpu=True))
     assert e.value.code == 0

@@ -30,7 +30,7 @@ def _bench(argv, env_extra=None, expect_rc=0):
     return r.stderr
 
 
-COMMON = ["--rows", "200000", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"]
+COMMON = ["--rows", "200000", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"]  # --full: self_check, strong_scaling
 
 
 def test_gpus_2_without_a_launcher_runs_two_ranks(tmp_path):
@@ -68,7 +68,7 @@ def test_more_ranks_than_devices_is_refused_without_share_gpu():
 
 
 def test_structured_mode_reports_both_corpora_with_exact_ids():
-    """`bench.py --mode structured` (round 6; the same sub-results ride in every default line): the k = 1 search on a clustered corpus and on the HIP encoder's own
+    """`bench.py --mode structured` (round 6; the same sub-results ride in every --full line): the k = 1 search on a clustered corpus and on the HIP encoder's own
     outputs, here at 300 k rows -- int8 tier deciding, query split on for the encoder rows only, ids equal to the brute force up to exact copies, and the beam > 1 case."""
     r = _bench(["--mode", "structured", "--rows", "300000"])
     s = r["structured"]
