@@ -81,7 +81,9 @@ int mdr_index_reserve(mdr_index* h, int64_t n_rows);
  * |x| (its fp16 hi/lo pair is then normal) and degrades gracefully below that (lo, then hi, go subnormal: relative accuracy 1e-3..1e-4
  * at 2^-24 of the maximum, zero below ~2^-34). Embedding matrices (unit-scale LayerNorm outputs, the reference's case) sit inside the
  * accurate range by 10 orders of magnitude; an index mixing rows of wildly different scales is better served by MDR_STORE_BF16 or by
- * scaling the rows. */
+ * scaling the rows. The int8 screening tier's query split keeps one fp32 term per row, c.(x - c) with c the centre taken from the first
+ * add(); once a later row makes that term overflow (|x| |c| beyond ~3.4e38 with every score still finite), the index scores its int8
+ * plane without the split from then on (MDR_MIPS_I8_CB=1 included): same results, the split's speed-up is lost for that index. */
 int mdr_index_add(mdr_index* h, const void* rows, int64_t n, int src_dtype, int rows_on_device, void* stream);
 
 int64_t mdr_index_ntotal(const mdr_index* h);

@@ -28,6 +28,11 @@ def _stale():
     return any(os.path.getmtime(p) > t for p in deps)
 
 
+def hipcc_flags():
+    """Compiler flags of the product build (tests/test_kernel_resources.py compiles the same sources device-only with them)."""
+    return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-I", INCLUDE]
+
+
 def build_lib(force=False, verbose=True, defines=(), out=None):
     """defines / out: build a measurement VARIANT of the library next to the product one (e.g. defines=["MDR_MIPS_DMA_AUX=2"],
     out="libmdrhip_nt.so"); a process selects it with MDR_LIB_PATH (scripts/measure/gpu_ab.sh). The product build takes neither."""
@@ -35,8 +40,7 @@ def build_lib(force=False, verbose=True, defines=(), out=None):
     if out is None and not force and not _stale():
         return LIB
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
-           "-Wno-unused-variable", "-I", INCLUDE] + ["-D" + d for d in defines] + sources() + ["-o", target + ".tmp"]
+    cmd = [hipcc] + hipcc_flags() + ["-shared"] + ["-D" + d for d in defines] + sources() + ["-o", target + ".tmp"]
     if verbose:
         print("[mdr build]", " ".join(cmd), flush=True)
     subprocess.check_call(cmd)

@@ -76,11 +76,13 @@ struct mdr_index {
                              // them, frozen afterwards; [3 d .. 5 d) scratch for the column sums
     bool centre_set = false;
     bool cb = false;         // the int8 tier scores the plane against q - lambda c (mdr_mips_screen_i8.inl "Query split"): decided with the centre (flags[11])
+    bool terms_inf = false;  // a stored row's term b_r = c.(x_r - c) overflowed fp32 (flags[12], convert_to_i8_kernel): the query split stays off for good
     int xexp = 0;            // F32X2H: the planes hold x * 2^-xexp (see convert_to_frag_kernel); fitted to the data by add(), grown by a rescale
     bool xexp_set = false;
     int* flags = nullptr;    // device ints: [0] range error seen by add(), [1] same for queries (ignored), [2] max row |x|^2 (float bits),
                              // [8], [9], [10] int8 tier: max row scale, max s_r (L1(x8_r)/2 + d/4), max sum|c_i (x_i - c_i)| (float bits);
-                             // [11] the centre is large against the rows' spread around it (centre_finish_kernel) -> cb
+                             // [11] the centre is large against the rows' spread around it (centre_finish_kernel) -> cb;
+                             // [12] a row's b_r or sum|c_i (x_i - c_i)| overflowed fp32 (convert_to_i8_kernel) -> terms_inf
     void* stage = nullptr;   // device staging for host-sourced add()
     size_t stage_bytes = 0;
     // pipelined host upload (upload_host_rows): two pinned staging buffers, a copy stream, "chunk copied" / "chunk converted" events per slot
@@ -324,8 +326,12 @@ struct SearchPlan {
 // (run_screen8 serves ONE group of at most kStreamQ queries; more than that goes to the 32-queries-per-wave kernel, which loops over
 // groups of 256 -- or, with MDR_MIPS_WIDE=0, stays on the fp16 screen, which loops over groups of 128)
 // MDR_MIPS_I8_CB = 0 / 1 forces the query split of the int8 tier off / on (A/B runs; results are the same either way: any lambda is correct)
+// -- except on an index with a row whose term b_r overflowed fp32 (terms_inf: finite rows with |x| |c| beyond 3.4e38, added after the rows that set
+// the centre c): that row's split bound is NaN and would never make it a candidate, so the split is off there whatever the index or the variable says.
+// The non-split kernels never read b_r.
 bool use_cb(const mdr_index* h) {
     static const int force = getenv("MDR_MIPS_I8_CB") ? atoi(getenv("MDR_MIPS_I8_CB")) : -1;
+    if (h->terms_inf) return false;
     return force < 0 ? h->cb : force != 0;
 }
 bool i8_tier(const mdr_index* h, int path, int nq, int k) {
@@ -876,7 +882,7 @@ int mdr_index_add(mdr_index* h, const void* rows, int64_t n, int src_dtype, int 
     hipStream_t st = (hipStream_t)stream;
     int rc = grow(h, h->ntotal + n, st);
     if (rc) return rc;
-    int before[16] = {0};  // [0..3] range / query / norm flags, [8..11] the int8 tier's row statistics and its query-split verdict: all restored when the rows are rejected
+    int before[16] = {0};  // [0..3] range / query / norm flags, [8..12] the int8 tier's row statistics, its query-split verdict and the row-term overflow: all restored when the rows are rejected
     const bool centre_was_set = h->centre_set;
     const int xexp_was = h->xexp;
     const bool xexp_was_set = h->xexp_set;
@@ -891,6 +897,7 @@ int mdr_index_add(mdr_index* h, const void* rows, int64_t n, int src_dtype, int 
         (void)hipStreamSynchronize(st);
         h->centre_set = centre_was_set;
         h->cb = before[11] != 0;
+        h->terms_inf = before[12] != 0;
         if (!xexp_was_set) { h->xexp = xexp_was; h->xexp_set = false; }  // the exponent was fitted to rejected rows: forget it
         return code;
     };
@@ -907,6 +914,7 @@ int mdr_index_add(mdr_index* h, const void* rows, int64_t n, int src_dtype, int 
     MDR_HIP_TRY(hipStreamSynchronize(st));
     if (after[0]) return reject(set_error(MDR_E_RANGE, "add(): a value is non-finite; rows were not added"));
     h->cb = after[11] != 0;  // (written once, with the centre: centre_finish_kernel)
+    h->terms_inf = after[12] != 0;
     h->ntotal += n;
     return MDR_OK;
 }

@@ -21,6 +21,9 @@
 // the plane is scored against dq (t, alpha, beta now come from dq: several times smaller) and the per-row term enters the bounds exactly:
 //     U_r = s_r (t A + alpha_q) + beta_q + lambda_q b_r,   L_r = U_r - 2 (alpha_q s_r + beta_q).
 // ANY lambda is correct; fp32 rounding of b_r (768 terms) is covered by |lambda_q| 1e-4 max_r sum_i |c_i (x_ri - c_i)| (i8stats[2]) added to beta_q.
+// ... as long as b_r is finite: a finite row far larger than the rows that set c (|x_r| |c| > 3.4e38) has b_r = +-inf, and its bound would be NaN
+// (lambda_q = 0) or -inf (lambda_q of the other sign) -- the row could never be a candidate. convert_to_i8_kernel flags such a row (i8stats[4]) and
+// the index then stays on the non-CB instantiations, which never read b_r (use_cb in mdr_mips.hip).
 // Measured at 5 M rows on this repo's encoder outputs (|c| = 26.5, centred rows 9.8): see DESIGN.md section 4.
 // Layout: a super-block (32 rows) = 2 x NKB8 fragment blocks of 1 KiB (16 rows x 64 int8; lane (lr, g) of the MFMA owns the
 // 16 bytes k = 64 kb + 16 g .. of row lr at (16 g + lr) * 16) followed by 256 bytes holding the 32 row scales and the 32 row terms b_r: 24.25 KiB at
@@ -151,6 +154,9 @@ __global__ void __launch_bounds__(1024) centre_finish_kernel(const float* __rest
 // one wave per row: lanes 0 .. d/16-1 quantise 16 consecutive columns each of x - centre. stats[0] = max s_r, stats[1] = max s_r (L1(x8_r)/2 + d/4),
 // stats[2] = max_r sum_i |c_i (x_ri - c_i)| (what the fp32 rounding of the row term b_r = c.(x_r - c) scales with)
 // (non-negative floats, kept as their bit patterns: they order like ints)
+// stats[4] = 1 when a row's b_r or sum_i |c_i (x_ri - c_i)| overflowed fp32 (finite rows far larger than the centre's rows: |x| |c| > 3.4e38). Such a
+// row's bound under the query split would be inf * lambda or -inf + inf = NaN, never >= `known`: the row could never be a candidate. The flag turns the
+// split off for the index (use_cb); the row is left out of stats[2] so that the non-split bounds, which multiply it by lambda = 0, stay finite.
 template <typename T>
 __global__ void __launch_bounds__(256) convert_to_i8_kernel(const T* __restrict__ src, long long n, int d, long long row0, char* __restrict__ dst,
                                                             int* __restrict__ stats, const float* __restrict__ centre) {
@@ -164,6 +170,7 @@ __global__ void __launch_bounds__(256) convert_to_i8_kernel(const T* __restrict_
         iw[j] = on ? centre[d + lane * 16 + j] : 0.f;
     }
     float smax = 0.f, cmax = 0.f, bamax = 0.f;
+    bool terms_inf = false;
     for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (long long)gridDim.x * 4) {
         float x[16];
         float mx = 0.f, br = 0.f, bra = 0.f;
@@ -205,7 +212,8 @@ __global__ void __launch_bounds__(256) convert_to_i8_kernel(const T* __restrict_
             *(float*)(sb + (size_t)2 * nkb8 * kFragBytes + (row & 31) * 4) = sc;
             *(float*)(sb + (size_t)2 * nkb8 * kFragBytes + kI8TailB + (row & 31) * 4) = br;
         }
-        bamax = fmaxf(bamax, bra);
+        if (fabsf(br) <= FLT_MAX && bra <= FLT_MAX) bamax = fmaxf(bamax, bra);
+        else terms_inf = true;
         smax = fmaxf(smax, sc);
         cmax = fmaxf(cmax, sc * (0.5f * (float)l1 + 0.25f * (float)d));
     }
@@ -213,6 +221,7 @@ __global__ void __launch_bounds__(256) convert_to_i8_kernel(const T* __restrict_
         if (__float_as_int(smax) > stats[0]) atomicMax(stats + 0, __float_as_int(smax));
         if (__float_as_int(cmax) > stats[1]) atomicMax(stats + 1, __float_as_int(cmax));
         if (__float_as_int(bamax) > stats[2]) atomicMax(stats + 2, __float_as_int(bamax));
+        if (terms_inf) atomicOr(stats + 4, 1);
     }
 }
 

@@ -277,3 +277,117 @@ def test_query_split_on_the_hip_encoders_own_outputs(mdr):
         t = idx.telemetry(nq, 1)
         assert t["i8_query_split"] and t["i8_tier"] and not t["i8_overflow"] and t["fallback"] == 0, t
         print(f"encoder-geometry rows, nq {nq}: candidates emitted {t['candidates']}, re-scored {t['i8_refined']}")
+
+
+# ---- rows at the far end of fp32 (add() takes any finite fp32) ----------------------------------------------------------------------
+# The first add() sets the int8 plane's centre c from rows c + 0.33 n (a common component: the query split turns on); a second add() brings rows
+# s (c + 0.33 n'). From s ~ 4e35 on, a large row's term b_r = c.(x_r - c) ~ s |c|^2 and sum_i |c_i (x_ri - c_i)| overflow fp32 while every score
+# stays finite; its split bound would be lambda_q * inf (NaN for lambda_q = 0, -inf for lambda_q < 0) and the row could never become a candidate.
+# From s ~ 1e36 on, the non-split bound constant overflows as well (+inf bounds: the lists overflow, the fp16 tier decides).
+# Storage note (include/mdr_hip.h, dynamic range of F32X2H): the first add's rows lie ~2^110 below the largest element and are stored as zeros.
+# The queries are therefore built so that the true top-(k + 1) are large rows with positive scores, where the stored values are fp32-accurate:
+# (a) rows' kind, (b) pointing away from c (q.c < 0, lambda_q < 0) and (c) orthogonal to c (lambda_q ~ 0).
+EXTREME_SCALES = [1e34, 3e35, 5e35, 1e36, 3e36]
+
+
+def extreme_corpus(n1, n2, s, nq=96, seed=41):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    c = torch.randn((D_,), generator=g, device="cuda")
+    first = c + 0.33 * torch.randn((n1, D_), generator=g, device="cuda")
+    base = c + 0.33 * torch.randn((n2, D_), generator=g, device="cuda")
+    noise = torch.randn((nq, D_), generator=g, device="cuda")
+    q = torch.empty((nq, D_), device="cuda")
+    kind = torch.arange(nq, device="cuda") % 3
+    ortho = noise - (noise @ c)[:, None] * c / (c @ c)
+    ortho = ortho / ortho.norm(dim=1, keepdim=True)
+    q[kind == 0] = c + 0.33 * noise[kind == 0]
+    q[kind == 1] = ortho[kind == 1] - 0.2 * c / (c @ c)  # q.c = -0.2: lambda_q < 0, and the best large rows still score > 0
+    q[kind == 2] = ortho[kind == 2]
+    q = q / q.norm(dim=1, keepdim=True)
+    return first, (base * s).contiguous(), q.contiguous(), kind.cpu().numpy()
+
+
+def extreme_case(idx_factory, n1, n2, s, ks=(1, 8)):
+    """Variants 0 (int8 tier in front), 4 (fp16 screen) and 2 (exact stream) against the fp64 inner products of the fp32 rows. Returns the telemetry of variant 0, k = 1."""
+    from test_oracle_mips import check_against_truth
+    first, big, q, kind = extreme_corpus(n1, n2, s)
+    idx = idx_factory()
+    idx.add(first)
+    idx.add(big)
+    kmax = max(ks)
+    S = q.double() @ torch.cat([first, big]).double().T
+    assert float(S.abs().max()) < 1e38  # legal input: every score is a finite fp32
+    St, It = torch.sort(S, dim=1, descending=True, stable=True)
+    Dt, It = St[:, : kmax + 1].cpu().numpy(), It[:, : kmax + 1].cpu().numpy()
+    assert (It >= n1).all() and (Dt > 0).all(), "the truth must lie among the large rows (the first add's rows are stored as zeros)"
+    tele = None
+    for v in (0, 4, 2):
+        idx.set_variant(v)
+        for k in ks:
+            D, I = idx.search(q, k)
+            if v == 0 and k == 1:
+                tele = idx.telemetry(q.shape[0], 1)
+                assert tele["i8_tier"], tele
+            D, I = D.cpu().numpy().astype(np.float64), I.cpu().numpy()
+            for kd in range(3):
+                m = kind == kd
+                tol = 2e-6 * float(np.abs(Dt[m]).max())
+                try:
+                    check_against_truth(D[m], I[m], Dt[m, :k], It[m, :k], Dt[m, k - 1] - Dt[m, k], tol=tol)
+                except AssertionError as e:
+                    bad = np.nonzero(I[m, 0] != It[m, 0])[0]
+                    raise AssertionError(f"s {s:g} variant {v} k {k} query kind {kd}: {len(bad)} wrong top-1 ids of {int(m.sum())} "
+                                         f"(e.g. got {I[m][bad[:3], 0]} want {It[m][bad[:3], 0]})") from e
+    idx.set_variant(0)
+    return tele
+
+
+@pytest.mark.parametrize("s", EXTREME_SCALES)
+@pytest.mark.parametrize("n1,n2", [(1024, 3072), (8192, 192_000)])
+def test_rows_near_the_top_of_fp32_after_a_centred_first_add(mdr, n1, n2, s):
+    """A finite row whose split row term overflows must still be found: the index switches the query split off for good (telemetry
+    `i8_query_split`) once such a row is stored, and every tier returns the fp64 answer. Below the overflow the split stays on."""
+    tele = extreme_case(lambda: mdr.IndexFlatIP(D_), n1, n2, s)
+    overflow = s >= 5e35
+    assert tele["i8_query_split"] == (not overflow), tele
+
+
+def test_row_term_overflow_state_rolls_back_with_a_rejected_add(mdr):
+    """A rejected add() restores every statistic of the int8 tier, the row-term overflow state included: host rows go up in chunks of
+    32 k rows, the first chunks are converted (and raise the state) before the NaN in the last one rejects the call. The split stays on
+    for the rows that were really added."""
+    first, big, q, _ = extreme_corpus(8192, 192_000, 5e35)
+    idx = mdr.IndexFlatIP(D_)
+    idx.add(first)
+    bad = big.cpu().numpy()
+    bad[-1, 5] = np.nan
+    with pytest.raises(Exception):
+        idx.add(bad)
+    assert idx.ntotal == 8192
+    idx.search(q, 1)
+    assert idx.telemetry(q.shape[0], 1)["i8_query_split"]
+    idx.add(big)
+    idx.search(q, 1)
+    assert not idx.telemetry(q.shape[0], 1)["i8_query_split"]
+
+
+def test_forced_query_split_does_not_bring_the_row_term_overflow_back():
+    """MDR_MIPS_I8_CB=1 (read once per process, hence the child) forces the split on -- except where a row term overflowed."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = """
+import sys
+sys.path.insert(0, 'tests')
+import test_mips_i8_gpu as t
+from multihop_dense_retrieval_amd import index as mi
+for n1, n2 in ((1024, 3072), (8192, 192_000)):
+    tele = t.extreme_case(lambda: mi.IndexFlatIP(768), n1, n2, 5e35)
+    assert not tele['i8_query_split'], tele
+tele = t.extreme_case(lambda: mi.IndexFlatIP(768), 1024, 3072, 1e34)
+assert tele['i8_query_split'], tele
+print('ok')
+"""
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MDR_MIPS_I8_CB="1"), capture_output=True, text=True, timeout=900, cwd=root)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
