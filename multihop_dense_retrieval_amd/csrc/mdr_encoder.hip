@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "mdr_common.h"
+#include "../../include/mdr_reader.h"
 
 namespace mdr {
 namespace {
@@ -595,3 +596,6 @@ int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* m
 }
 
 }  // extern "C"
+
+// the answer reader (include/mdr_reader.h) shares this translation unit's file-local kernels and launchers
+#include "mdr_reader.inl"
