@@ -69,6 +69,40 @@ int mdr_reader_forward(mdr_reader* h, const int64_t* ids_dev, const int64_t* mas
 int mdr_reader_span_search(const uint16_t* start_logits_dev, const uint16_t* end_logits_dev, int batch, int seq_len, int max_ans_len,
                            int64_t* span_start_dev, int64_t* span_end_dev, uint16_t* span_score_dev, int device, void* stream);
 
+/* ---- reader input assembly from a QA passage arena (the end-to-end path) ----
+ * Builds, for `rows` chains (passage ids p1, p2), the tensors qa_collate makes from QAEvalDataset items:
+ *   input_ids       [CLS] q [SEP] wp [SEP] [PAD]...   wp = (yes no [SEP] P1 [SEP] P2) cut to max_seq_len - para_offset - 1
+ *   attention_mask  1 on tokens; token_type_ids 1 on [para_offset, len); paragraph_mask 1 on [para_offset, len - 1)
+ *   sent_offsets    [rows, n_sent]: the [unused1] positions of P1 then P2 inside the cut wp, + para_offset, zero-padded
+ * with para_offset = q_len + 2 and len = para_offset + |wp| + 1. The arena holds each passage's WordPiece ids (tokens,
+ * token_offsets [N + 1]) and its [unused1] positions relative to the passage (sent_starts, sent_offsets [N + 1]).
+ * A passage id outside [0, N) is an empty passage and a question index outside [0, n_questions) an empty question.
+ * Rows longer than out_len and sentences past n_sent are cut: the caller sizes both from the arena's host metadata. */
+typedef struct mdr_reader_arena {
+    const int32_t* tokens_dev;
+    const int64_t* token_offsets_dev; /* [n_passages + 1] */
+    const int32_t* sent_starts_dev;
+    const int64_t* sent_offsets_dev;  /* [n_passages + 1] */
+    int64_t n_passages;
+} mdr_reader_arena;
+
+typedef struct mdr_reader_batch {
+    int64_t* input_ids;      /* [rows, out_len] */
+    int64_t* attention_mask; /* [rows, out_len] */
+    int64_t* token_type_ids; /* [rows, out_len] */
+    int64_t* paragraph_mask; /* [rows, out_len]: qa_collate's float 0 / 1 as integers */
+    int64_t* sent_offsets;   /* [rows, n_sent]; may be NULL when n_sent == 0 */
+    int64_t* para_offsets;   /* [rows]; may be NULL */
+    int64_t* lengths;        /* [rows]: len above, not clipped to out_len; may be NULL */
+} mdr_reader_batch;
+
+/* q_ids_dev int64 [n_questions, q_stride] (WordPiece ids, already cut to max_q_len), q_lens_dev int64 [n_questions],
+ * chains_dev int64 [rows, 2], row_question_dev int64 [rows], special = {cls, sep, yes, no, pad} ids (host memory).
+ * Requires max_seq_len - q_stride >= 6. One workgroup per row, integer copies only. */
+int mdr_reader_assemble(const int64_t* q_ids_dev, const int64_t* q_lens_dev, int n_questions, int q_stride, const int64_t* chains_dev,
+                        const int64_t* row_question_dev, int rows, const mdr_reader_arena* arena, const int32_t* special, int max_seq_len,
+                        int out_len, int n_sent, const mdr_reader_batch* out, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -599,3 +599,4 @@ int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* m
 
 // the answer reader (include/mdr_reader.h) shares this translation unit's file-local kernels and launchers
 #include "mdr_reader.inl"
+#include "mdr_reader_assemble.inl"

@@ -37,6 +37,16 @@ class ReaderOutputs(ctypes.Structure):
                 ("sp_prob", _c.c_void_p), ("span_start", _c.c_void_p), ("span_end", _c.c_void_p), ("span_score", _c.c_void_p)]
 
 
+class ReaderArena(ctypes.Structure):
+    _fields_ = [("tokens_dev", _c.c_void_p), ("token_offsets_dev", _c.c_void_p), ("sent_starts_dev", _c.c_void_p), ("sent_offsets_dev", _c.c_void_p),
+                ("n_passages", _c.c_int64)]
+
+
+class ReaderBatch(ctypes.Structure):
+    _fields_ = [("input_ids", _c.c_void_p), ("attention_mask", _c.c_void_p), ("token_type_ids", _c.c_void_p), ("paragraph_mask", _c.c_void_p),
+                ("sent_offsets", _c.c_void_p), ("para_offsets", _c.c_void_p), ("lengths", _c.c_void_p)]
+
+
 # include/mdr_reader.h -- bound here, apart from _lib._SIGNATURES (which is include/mdr_hip.h's table, pinned by its own test)
 SIGNATURES = {
     "mdr_reader_create": (_c.c_int, [_c.POINTER(ReaderConfig), _c.POINTER(_lib.Tensor), _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
@@ -47,6 +57,8 @@ SIGNATURES = {
                                       _c.c_int, _c.POINTER(ReaderOutputs), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "mdr_reader_span_search": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int,
                                           _c.c_void_p]),
+    "mdr_reader_assemble": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                       _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 MAX_SEQ_LEN = 512  # the span kernel keeps one row of start / end logits in LDS
