@@ -1,6 +1,6 @@
 """GPU parity tests (-m gpu) for the encoder's GEMM kernels in isolation (mdr_test_gemm_f16): every kernel flavour
-against a float64 matmul of the same fp16 operands. Tolerance: fp32 accumulation of K <= 3072 products of O(1) values
--> 2e-3 absolute on f32 outputs; f16 outputs add half-precision rounding of the result (2^-11 relative)."""
+against a float64 matmul of the same fp16 operands. Tolerance: fp32 accumulation of K <= 4096 products (W is scaled by 1 / sqrt(K), so the
+outputs stay O(1) at every K) -> 2e-3 absolute on f32 outputs; f16 outputs add half-precision rounding of the result (2^-11 relative)."""
 import numpy as np
 import pytest
 
@@ -36,7 +36,18 @@ SHAPES = [  # (M, N, K): encoder shapes incl. ragged M, one tile, many tiles per
     (9000, 768, 3072), (70000, 768, 768),
     # shapes outside roberta-base: K of 4 and 6 K-tiles (the four-wave kernel's shortest loops), N = 256, roberta-large's 1024
     (300, 256, 256), (5000, 512, 384), (3000, 1024, 1024),
+    # the answer reader at ELECTRA-large geometry, 3 x 512 and 64 x 512 tokens: FFN1 (N = 4096 is wider than kPersistBiasMax: one-tile-per-block kernels whatever
+    # is asked for), FFN2 (K = 4096: the four-wave kernel's K >= 2048 branch), QKV, out-projection; FFN2 at the reader's M_est = 32768 - 32768 / 3 and at 256 * 80 + 1 rows
+    (1536, 4096, 1024), (32768, 4096, 1024), (20000, 1024, 4096), (32768, 1024, 4096), (32768, 3072, 1024), (32768, 1024, 1024), (21846, 1024, 4096),
+    (20481, 1024, 4096),
 ]
+
+
+def _hook_rejects(shape, kernel):
+    """Why the test hook is not asked for this pair (None: it is)."""
+    if kernel in (1, 2) and shape[0] > 10000:
+        return "small-tile kernels are not used at this size"
+    return None
 
 
 @pytest.mark.parametrize("kernel", [0, 1, 2, 4, 6, 7])
@@ -44,8 +55,8 @@ SHAPES = [  # (M, N, K): encoder shapes incl. ragged M, one tile, many tiles per
 @pytest.mark.parametrize("shape", SHAPES)
 def test_gemm_matches_fp64(shape, epilogue, kernel):
     M, N, K = shape
-    if kernel in (1, 2) and M > 10000:
-        pytest.skip("small-tile kernels are not used at this size")
+    if _hook_rejects(shape, kernel):
+        pytest.skip(_hook_rejects(shape, kernel))
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
     A = torch.randn((M, K), generator=g, device="cuda").half()
     W = (torch.randn((N, K), generator=g, device="cuda") / K ** 0.5).half()
@@ -56,6 +67,26 @@ def test_gemm_matches_fp64(shape, epilogue, kernel):
     tol = 2e-3 if epilogue == 3 else 2e-3 + ref.abs() * 2 ** -10
     bad = err > tol
     assert not bool(bad.any()), f"{int(bad.sum())} bad of {M * N}; worst {err.max().item():.3e} at {np.unravel_index(int(err.argmax()), (M, N))}"
+
+
+def test_the_readers_ffn2_shape_runs_on_the_256x256_kernels():
+    """(M, 1024, 4096) on kernels 6 and 7 is the pair the answer reader depends on at large M: the cases above must not skip it, and launch_gemm's conditions for
+    handing a forced 6 / 7 to gemm_big_kernel / gemm_quad_kernel (instead of falling through to another flavour) must hold for it."""
+    shapes = [s for s in SHAPES if s[1:] == (1024, 4096)]
+    assert len(shapes) >= 4 and max(s[0] for s in shapes) >= 32768
+    for M, N, K in shapes:
+        for kernel in (6, 7):
+            assert _hook_rejects((M, N, K), kernel) is None
+        assert N % 256 == 0 and N <= 3072 and K % 128 == 0 and K >= 256
+        assert (M + 255) * N * 4 < 1 << 32 and (M + 255) * K * 2 < 1 << 32  # the buffer descriptors' 32-bit offsets (out32, a32)
+    g = torch.Generator(device="cuda").manual_seed(11)
+    M, N, K = 20481, 1024, 4096
+    A = torch.randn((M, K), generator=g, device="cuda").half()
+    W = (torch.randn((N, K), generator=g, device="cuda") / K ** 0.5).half()
+    bias = torch.randn((N,), generator=g, device="cuda")
+    ref = _gemm(A, W, bias, 3, 2)
+    for kernel in (6, 7):
+        assert torch.equal(_gemm(A, W, bias, 3, kernel), ref), kernel
 
 
 def test_quad_kernel_is_bit_identical_to_the_eight_wave_kernel():
@@ -72,21 +103,24 @@ def test_quad_kernel_is_bit_identical_to_the_eight_wave_kernel():
 @pytest.mark.parametrize("kernel", [0, 4, 6, 7])
 def test_gemm_device_side_row_count(kernel):
     """Rows past *m_dev are neither computed into nor stored (the packed token count lives on the device)."""
-    M, N, K, valid = 5000, 768, 768, 3333
-    g = torch.Generator(device="cuda").manual_seed(1)
-    A = torch.randn((M, K), generator=g, device="cuda").half()
-    W = (torch.randn((N, K), generator=g, device="cuda") / K ** 0.5).half()
-    bias = torch.zeros((N,), device="cuda")
-    out = _gemm(A, W, bias, 3, kernel, m_valid=valid)
-    ref = _reference(A, W, bias, 3)
-    assert (out[:valid].double() - ref[:valid]).abs().max().item() <= 2e-3
-    assert bool(torch.isnan(out[valid:]).all())
+    for M, N, K, valid in [(5000, 768, 768, 3333)] + ([(5000, 1024, 4096, 3333)] if kernel in (6, 7) else []):  # + the reader's FFN2
+        g = torch.Generator(device="cuda").manual_seed(1)
+        A = torch.randn((M, K), generator=g, device="cuda").half()
+        W = (torch.randn((N, K), generator=g, device="cuda") / K ** 0.5).half()
+        bias = torch.zeros((N,), device="cuda")
+        out = _gemm(A, W, bias, 3, kernel, m_valid=valid)
+        ref = _reference(A, W, bias, 3)
+        assert (out[:valid].double() - ref[:valid]).abs().max().item() <= 2e-3, (N, K)
+        assert bool(torch.isnan(out[valid:]).all()), (N, K)
 
 
 # (M, N, K) a little over a whole number of rounds of 256x256 tiles on 256 workgroups: the last, partial round runs on 128x128 tiles inside the same
 # persistent kernel (gemm_head_row_tiles / gemm_tail_tile). 86 row tiles: 258 / 774 / 1032 tiles for N = 768 / 2304 / 3072 (remainders 2 / 6 / 8);
 # 171 x 3 = 513 (two complete rounds + 1); 43 x 12 = 516 (remainder 4, rows not a multiple of 128); a tail of several row tiles (N = 768: 90 x 3 = 270).
-TAIL_SHAPES = [(22013, 768, 768), (22013, 2304, 768), (22013, 3072, 768), (22013, 768, 3072), (43700, 768, 768), (10900, 3072, 768), (22990, 768, 768)]
+# The reader's shapes by the same rule: N = 1024 is 4 column tiles, 65 row tiles = 260 (remainder 4, K = 4096) and 130 = 520 (two rounds + 8, K = 1024), rows not a
+# multiple of 128; N = 3072, K = 1024: 43 x 12 = 516.
+TAIL_SHAPES = [(22013, 768, 768), (22013, 2304, 768), (22013, 3072, 768), (22013, 768, 3072), (43700, 768, 768), (10900, 3072, 768), (22990, 768, 768),
+               (16600, 1024, 4096), (33100, 1024, 1024), (10900, 3072, 1024)]
 
 
 @pytest.mark.parametrize("kernel", [6, 7])
@@ -111,13 +145,14 @@ def test_partial_last_round_on_small_tiles_is_bit_identical(shape, epilogue, ker
 @pytest.mark.parametrize("kernel", [6, 7])
 def test_tail_respects_the_device_side_row_count(kernel):
     """The split point is computed on the device from *m_dev: rows past it stay untouched whether they fall in the 256x256 walk or in the tail."""
-    M, N, K = 23000, 768, 768
-    g = torch.Generator(device="cuda").manual_seed(3)
-    A = torch.randn((M, K), generator=g, device="cuda").half()
-    W = (torch.randn((N, K), generator=g, device="cuda") / K ** 0.5).half()
-    bias = torch.zeros((N,), device="cuda")
-    ref = _reference(A, W, bias, 3)
-    for valid in (21761, 21900, 22016, 22017, 22700):  # 86 row tiles (tail of one) ... 89 (tail of four)
-        out = _gemm(A, W, bias, 3, kernel, m_valid=valid)
-        assert (out[:valid].double() - ref[:valid]).abs().max().item() <= 2e-3, valid
-        assert bool(torch.isnan(out[valid:]).all()), valid
+    # N = 768: 86 row tiles (tail of one) ... 89 (tail of four); the reader's FFN2 (N = 1024, K = 4096): 65 row tiles (a tail of one row) ... 67
+    for (M, N, K), valids in (((23000, 768, 768), (21761, 21900, 22016, 22017, 22700)), ((18000, 1024, 4096), (16385, 16500, 16640, 16641, 17000))):
+        g = torch.Generator(device="cuda").manual_seed(3)
+        A = torch.randn((M, K), generator=g, device="cuda").half()
+        W = (torch.randn((N, K), generator=g, device="cuda") / K ** 0.5).half()
+        bias = torch.zeros((N,), device="cuda")
+        ref = _reference(A, W, bias, 3)
+        for valid in valids:
+            out = _gemm(A, W, bias, 3, kernel, m_valid=valid)
+            assert (out[:valid].double() - ref[:valid]).abs().max().item() <= 2e-3, (N, K, valid)
+            assert bool(torch.isnan(out[valid:]).all()), (N, K, valid)
