@@ -1,5 +1,6 @@
-"""Flag sets of the corpus-encoder CLI: `encode_args()` = `common_args()` + two flags, flag for flag as
-/root/reference/mdr/retrieval/config.py:14-69,107-112 (training-only flags are accepted and ignored so
+"""Flag sets of the corpus-encoder CLI and of the retriever's dev-set evaluation: `encode_args()` = `common_args()` + two
+flags, `train_args()` = `common_args()` + the optimisation flags, flag for flag as
+/root/reference/mdr/retrieval/config.py:14-69,71-105,107-112 (training-only flags are accepted and ignored so
 existing command lines keep working)."""
 import argparse
 
@@ -47,4 +48,28 @@ def encode_args(argv=None):
     # predict_batch_size x this many items, sorted by token count inside a window and batched by length; every embedding
     # still lands in its own row. 1 = the reference's order-of-appearance batches.
     p.add_argument("--length_bucket_window", type=int, default=16)
+    return p.parse_args(argv)
+
+
+def train_args(argv=None):
+    """config.py:71-105: the flags of scripts/train_mhop.py (only --do_predict runs here; the README's training argv still parses)."""
+    p = common_args()
+    p.add_argument("--prefix", type=str, default="eval")
+    p.add_argument("--weight_decay", default=0.0, type=float)
+    p.add_argument("--temperature", default=1, type=float)
+    p.add_argument("--output_dir", default="./logs", type=str)
+    p.add_argument("--train_batch_size", default=128, type=int)
+    p.add_argument("--learning_rate", default=1e-5, type=float)
+    p.add_argument("--adam_epsilon", default=1e-8, type=float)
+    p.add_argument("--num_train_epochs", default=50, type=float)
+    p.add_argument("--save_checkpoints_steps", default=20000, type=int)
+    p.add_argument("--iterations_per_loop", default=1000, type=int)
+    p.add_argument("--accumulate_gradients", type=int, default=1)
+    p.add_argument("--seed", type=int, default=3)
+    p.add_argument("--gradient_accumulation_steps", type=int, default=1)
+    p.add_argument("--eval-period", type=int, default=2500)
+    p.add_argument("--max_grad_norm", default=2.0, type=float)
+    p.add_argument("--stop-drop", default=0, type=float)
+    p.add_argument("--use-adam", action="store_true")
+    p.add_argument("--warmup-ratio", default=0, type=float)
     return p.parse_args(argv)

@@ -355,8 +355,16 @@ class RobertaRetriever(_HipRobertaEncoder):
     def encode_q(self, input_ids, q_mask, q_type_ids=None, lane=0):
         return self.encode_seq(input_ids, q_mask, lane)
 
-    def __call__(self, batch):
-        raise NotImplementedError("training forward (six encode_seq calls, mhop_retriever.py:28-38) is outside the retrieval hot path")
+    # output name -> key prefix of mhop_collate's batch, in the reference's order of evaluation (mhop_retriever.py:29-36)
+    FORWARD_INPUTS = (("c1", "c1"), ("c2", "c2"), ("neg_1", "neg1"), ("neg_2", "neg2"), ("q", "q"), ("q_sp1", "q_sp"))
+
+    def forward(self, batch):
+        """mhop_retriever.py:28-38 at inference: the six [B, hidden] fp32 embeddings of one mhop_collate batch, each by encode_seq (so every row
+        is, bit for bit, what a separate encode_seq call gives; a batch above MAX_TOKENS_PER_CALL tokens is encoded in slices there). The batch is
+        right-padded with 0, not with the pad id: rows are delimited by their masks."""
+        return {name: self.encode_seq(batch[f"{key}_input_ids"], batch[f"{key}_mask"]) for name, key in self.FORWARD_INPUTS}
+
+    __call__ = forward
 
 
 class RobertaCtxEncoder(_HipRobertaEncoder):
