@@ -224,6 +224,22 @@ int mdr_upload_host(void* dst_dev, const void* src_host, size_t bytes, int devic
  * ---------------------------------------------------------------------------------------------- */
 int mdr_test_gemm_f16(const void* A_dev, const void* W_dev, const float* bias_dev, int M, const int* m_dev, int N, int K,
                       void* out_dev, int epilogue, int kernel, int device, void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * Test hook: one attention call in isolation, ctx = softmax(Q K^T / 8) V per (sequence, head) -- the self-attention inside
+ * HF RobertaModel / ElectraModel layers, on packed rows. qkv: f16 device [T, 3*hidden], each token's row is Q | K | V;
+ * cu: int32 device [B + 1], cu[0] = 0, cu[B] = T (sequence b owns rows cu[b] .. cu[b+1]-1); order: int32 device [B], a
+ * permutation of 0..B-1 giving the walk order of the ring kernel, or NULL (batch order; the other kernels ignore it);
+ * L: the padded length the dispatch is keyed on; hidden == 64 * heads; ctx: f16 device [T, hidden] (kernel 3: [B, hidden],
+ * the context of each sequence's first query only).
+ * kernel: 0 = exactly the choice mdr_encoder_forward / mdr_reader_forward make for L (one-shot up to 128, ring above),
+ * 1 = the one-shot kernel (whole K / V^T in LDS; 8, 24 or 32 key tiles of 16 by L), 2 = the ring kernel (jobs of 96 keys,
+ * online softmax), 3 = the CLS kernel of the retriever's last layer.
+ * Validated on the host (MDR_E_INVALID + mdr_last_error()): non-NULL qkv / cu / ctx, B >= 1, 1 <= L <= 512,
+ * hidden == 64 * heads, kernel in 0..3. The lengths live on the device, so the hook CANNOT check them: the caller
+ * guarantees 1 <= cu[b+1] - cu[b] <= L for every sequence. Enqueues on `stream` and does not synchronise.
+ * ---------------------------------------------------------------------------------------------- */
+int mdr_test_attention(const void* qkv_dev, const int* cu_dev, const int* order_dev, int B, int L, int hidden, int heads,
+                       int kernel, void* ctx_dev, int device, void* stream);
 /* Measurement hooks that exist only in VARIANT builds of these sources (never in the product library) are declared in
  * include/mdr_hip_measure.h. No environment variable changes what any entry point above computes: MDR_GEMM_CFG, MDR_MIPS_WIDE,
  * MDR_MIPS_I8, MDR_MIPS_I8_CB (the int8 tier's query split forced on / off) and MDR_MIPS_EVEN_GROUPS (how the passes of a > 256-query

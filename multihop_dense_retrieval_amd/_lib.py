@@ -66,6 +66,8 @@ _SIGNATURES = {
     "mdr_encoder_set_fill_hint": (_c.c_int, [_c.c_void_p, _c.c_float]),
     "mdr_test_gemm_f16": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int,
                                      _c.c_int, _c.c_int, _c.c_void_p]),
+    "mdr_test_attention": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                      _c.c_int, _c.c_void_p]),
 }
 # include/mdr_hip_measure.h: exported by measurement builds only (MDR_LIB_PATH=...); bound when present, absent from the product library
 _MEASURE_SIGNATURES = {

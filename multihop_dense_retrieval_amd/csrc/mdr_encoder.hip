@@ -256,6 +256,18 @@ int launch_attention_stream(const _Float16* qkv, const int* cu, const int* order
     return MDR_OK;
 }
 
+// The ONE place that maps the padded length L of a batch to an attention kernel: mdr_encoder_forward, mdr_reader_forward and the mdr_test_attention
+// hook all come through here. sel: 0 (product) = by length -- the one-shot kernel up to 128 tokens, the ring kernel above; 1 = the one-shot kernel, NT from L
+// (the hook, and MDR_ATTN_FORCE=1 measurement builds); 2 = the ring kernel (MDR_ATTN_RING=0 measurement builds: the streaming kernel, chunk size from L).
+constexpr int kOneShotMaxL = 32 * 16;  // keys the largest one-shot instantiation holds
+int launch_attention_for(int sel, const _Float16* qkv, const int* cu, const int* order, int B, int L, int H, int heads, _Float16* ctx, hipStream_t st) {
+    if (sel == 2 || (sel == 0 && L > 128))
+        return L <= 64 ? launch_attention_stream<4>(qkv, cu, order, B, L, H, heads, ctx, st) : launch_attention_stream<16>(qkv, cu, order, B, L, H, heads, ctx, st);
+    if (L <= 128) return launch_attention<8>(qkv, cu, B, L, H, heads, ctx, st);
+    if (L <= 384) return launch_attention<24>(qkv, cu, B, L, H, heads, ctx, st);
+    return launch_attention<32>(qkv, cu, B, L, H, heads, ctx, st);
+}
+
 const mdr_tensor* find_tensor(const mdr_tensor* ts, int n, const std::string& name) {
     for (int i = 0; i < n; ++i)
         if (ts[i].name && name == ts[i].name) return &ts[i];
@@ -395,6 +407,26 @@ int mdr_test_gemm_f16(const void* A_dev, const void* W_dev, const float* bias_de
     if (epilogue == EPI_BIAS_F16) return launch_gemm<EPI_BIAS_F16>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M, ncu, st, nullptr, kernel);
     if (epilogue == EPI_BIAS_GELU_F16) return launch_gemm<EPI_BIAS_GELU_F16>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M, ncu, st, nullptr, kernel);
     return launch_gemm<EPI_BIAS_F32>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M, ncu, st, nullptr, kernel);
+}
+
+int mdr_test_attention(const void* qkv_dev, const int* cu_dev, const int* order_dev, int B, int L, int hidden, int heads, int kernel, void* ctx_dev,
+                       int device, void* stream) {
+    MDR_REQUIRE(qkv_dev && cu_dev && ctx_dev, "NULL pointer");
+    MDR_REQUIRE(B >= 1, "B=%d must be at least 1", B);
+    MDR_REQUIRE(L >= 1 && L <= 512, "L=%d out of range (1..512)", L);
+    MDR_REQUIRE(heads >= 1 && hidden == 64 * heads, "head dim must be 64 (hidden=%d heads=%d)", hidden, heads);
+    MDR_REQUIRE(kernel >= 0 && kernel <= 3, "kernel must be 0, 1, 2 or 3");
+    MDR_REQUIRE(kernel != 1 || L <= kOneShotMaxL, "kernel 1 (one-shot) holds at most %d keys, L=%d", kOneShotMaxL, L);
+    DeviceGuard guard(device);
+    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    const _Float16* qkv = (const _Float16*)qkv_dev;
+    hipStream_t st = (hipStream_t)stream;
+    if (kernel == 3) {  // (the launch of mdr_encoder_forward's last layer)
+        hipLaunchKernelGGL(attention_cls_kernel, dim3(heads, B), dim3(64), 0, st, qkv, cu_dev, hidden, (_Float16*)ctx_dev);
+        MDR_HIP_TRY(hipGetLastError());
+        return MDR_OK;
+    }
+    return launch_attention_for(kernel, qkv, cu_dev, order_dev, B, L, hidden, heads, (_Float16*)ctx_dev, st);
 }
 
 #if MDR_GEMM_ABL == 5  // measurement builds only (include/mdr_hip_measure.h)
@@ -564,13 +596,7 @@ int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* m
             MDR_HIP_TRY(hipGetLastError());
             break;
         }
-        constexpr int attn_sel = MDR_ATTN_FORCE;  // compile-time (measurement builds): 1 = one-shot kernel, 2 = streaming kernel, 0 (product) = by length
-        if (attn_sel == 2 || (attn_sel == 0 && L > 128)) {
-            rc = L <= 64 ? launch_attention_stream<4>(w.qkv, w.cu, order, B, L, H, c.heads, w.ctx, st)
-                         : launch_attention_stream<16>(w.qkv, w.cu, order, B, L, H, c.heads, w.ctx, st);
-        } else if (L <= 128) rc = launch_attention<8>(w.qkv, w.cu, B, L, H, c.heads, w.ctx, st);
-        else if (L <= 384) rc = launch_attention<24>(w.qkv, w.cu, B, L, H, c.heads, w.ctx, st);
-        else rc = launch_attention<32>(w.qkv, w.cu, B, L, H, c.heads, w.ctx, st);
+        rc = launch_attention_for(MDR_ATTN_FORCE, w.qkv, w.cu, order, B, L, H, c.heads, w.ctx, st);
         if (rc) return rc;
         bool res_in = true;
         if (p16) rc = launch_gemm<EPI_BIAS_F16>(w.ctx, H, Ly.wo, Ly.bo, Tcap, w.total, H, H, pre16, H, nullptr, 0, Test, ncu, st);

@@ -448,13 +448,7 @@ int mdr_reader_forward(mdr_reader* h, const int64_t* ids_dev, const int64_t* mas
         const mdr_encoder::Layer& Ly = h->layers[i];
         rc = launch_gemm<EPI_BIAS_F16>(w.h16, H, Ly.wqkv, Ly.bqkv, Tcap, w.total, 3 * H, H, w.qkv, 3 * H, nullptr, 0, Test, ncu, st);
         if (rc) return rc;
-        constexpr int attn_sel = MDR_ATTN_FORCE;
-        if (attn_sel == 2 || (attn_sel == 0 && L > 128)) {
-            rc = L <= 64 ? launch_attention_stream<4>(w.qkv, w.cu, order, B, L, H, c.heads, w.ctx, st)
-                         : launch_attention_stream<16>(w.qkv, w.cu, order, B, L, H, c.heads, w.ctx, st);
-        } else if (L <= 128) rc = launch_attention<8>(w.qkv, w.cu, B, L, H, c.heads, w.ctx, st);
-        else if (L <= 384) rc = launch_attention<24>(w.qkv, w.cu, B, L, H, c.heads, w.ctx, st);
-        else rc = launch_attention<32>(w.qkv, w.cu, B, L, H, c.heads, w.ctx, st);
+        rc = launch_attention_for(MDR_ATTN_FORCE, w.qkv, w.cu, order, B, L, H, c.heads, w.ctx, st);
         if (rc) return rc;
         bool res_in = true;
         if (p16) rc = launch_gemm<EPI_BIAS_F16>(w.ctx, H, Ly.wo, Ly.bo, Tcap, w.total, H, H, pre16, H, nullptr, 0, Test, ncu, st);
