@@ -106,3 +106,17 @@ def check(code):
 def current_stream_ptr(device=None):
     """hipStream_t of torch's current stream as an integer for the `void* stream` arguments."""
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def tensor_table(state_dict, names):
+    """The `mdr_tensor` table of a create call for the keys `names`: (ctypes array, the contiguous fp32 tensors its pointers refer to -- the
+    caller holds them until the call has returned -- and whether all of them live on a device, the call's `weights_on_device`)."""
+    on_dev = all(state_dict[k].is_cuda for k in names)
+    keep = []
+    arr = (Tensor * len(names))()
+    for i, k in enumerate(names):
+        t = state_dict[k].detach().to(dtype=torch.float32)
+        t = t.contiguous() if on_dev else t.cpu().contiguous()
+        keep.append(t)
+        arr[i] = Tensor(k.encode(), ctypes.c_void_p(t.data_ptr()), t.numel())
+    return arr, keep, on_dev

@@ -20,6 +20,10 @@
 //   attention<NT>                       per (sequence, head): K and V^T of the sequence staged in LDS once,
 //                                       S = QK^T on MFMA, fp32 softmax in registers, O = PV on MFMA
 //   layernorm                           fp32 [T,H] -> fp16 (hidden state) or fp32 (final embedding)
+//
+// Host side, in this order: the GEMM / attention launchers (here); the transformer trunk shared with the answer reader -- weights and their
+// upload, workspace, packing prologue, layer body (mdr_encoder_trunk.inl); the encoder's own part -- its embedding launch, the CLS-only last
+// layer, the projection head and the test hooks (here); the reader (mdr_reader.inl, mdr_reader_assemble.inl).
 #include <hip/hip_runtime.h>
 #include <map>
 #include <mutex>
@@ -52,58 +56,11 @@ namespace {
 // ======================================================================================================
 using namespace mdr;
 
-struct mdr_encoder {
-    mdr_encoder_config cfg{};
-    int device = 0;
-    int num_cus = 256;
-    std::vector<void*> allocs;
-    float *word = nullptr, *pos = nullptr, *type0 = nullptr, *emb_g = nullptr, *emb_b = nullptr;
-    struct Layer {
-        _Float16 *wqkv, *wo, *w1, *w2;
-        float *bqkv, *bo, *b1, *b2, *ln1_g, *ln1_b, *ln2_g, *ln2_b;
-    };
-    std::vector<Layer> layers;
-    _Float16* wproj = nullptr;
-    float *bproj = nullptr, *lnp_g = nullptr, *lnp_b = nullptr;
-    float fill_hint = 0.f;  // expected (tokens / (batch * seq_len)) of the next forwards; 0 = unknown (2/3 is assumed)
-};
-
 #ifndef MDR_CU_LANES
 #define MDR_CU_LANES 0  // 1: measurement build with CU-partitioned lanes (include/mdr_hip_measure.h)
 #endif
 
 namespace {
-
-struct Workspace {
-    int *lens, *cu, *total, *tok_src, *tok_pid, *order;  // order: sequences by length, longest first (the ring attention kernel's walk)
-    _Float16 *h16, *qkv, *ctx, *ffn, *cls16;
-    float *pre, *clspre, *h32, *cls32;  // h32 / cls32: the fp32 residual stream (residual_fp32 mode only)
-    size_t bytes;
-};
-
-Workspace carve(const mdr_encoder_config& c, int B, int L, char* base) {
-    Workspace w{};
-    size_t o = 0;
-    const size_t T = (size_t)B * L;
-    auto take = [&](size_t n) { size_t at = o; o += align_up(n, 256); return base ? base + at : (char*)nullptr; };
-    w.lens = (int*)take((size_t)B * 4);
-    w.cu = (int*)take((size_t)(B + 1) * 4);
-    w.total = (int*)take(4);
-    w.order = (int*)take((size_t)B * 4);
-    w.tok_src = (int*)take(T * 4);
-    w.tok_pid = (int*)take(T * 4);
-    w.h16 = (_Float16*)take(T * c.hidden * 2);
-    w.qkv = (_Float16*)take(T * 3 * c.hidden * 2);
-    w.ctx = (_Float16*)take(T * c.hidden * 2);
-    w.ffn = (_Float16*)take(T * c.ffn * 2);
-    w.pre = (float*)take(T * c.hidden * 4);
-    w.cls16 = (_Float16*)take((size_t)B * c.hidden * 2);
-    w.clspre = (float*)take((size_t)B * c.hidden * 4);
-    w.h32 = c.residual_fp32 ? (float*)take(T * c.hidden * 4) : nullptr;
-    w.cls32 = c.residual_fp32 ? (float*)take((size_t)B * c.hidden * 4) : nullptr;
-    w.bytes = o + 256;
-    return w;
-}
 
 template <int EPI, typename C>
 int launch_gemm_cfg(const _Float16* A, int lda, const _Float16* W, const float* bias, int M_cap, const int* M_dev, int N, int K, void* out, int ldo,
@@ -268,120 +225,38 @@ int launch_attention_for(int sel, const _Float16* qkv, const int* cu, const int*
     return launch_attention<32>(qkv, cu, B, L, H, heads, ctx, st);
 }
 
-const mdr_tensor* find_tensor(const mdr_tensor* ts, int n, const std::string& name) {
-    for (int i = 0; i < n; ++i)
-        if (ts[i].name && name == ts[i].name) return &ts[i];
-    return nullptr;
-}
-
 }  // namespace
+
+#include "mdr_encoder_trunk.inl"
+
+struct mdr_encoder {
+    Trunk t;  // t.type: row 0 of the token-type table (type_vocab == 1 for RoBERTa)
+    _Float16* wproj = nullptr;
+    float *bproj = nullptr, *lnp_g = nullptr, *lnp_b = nullptr;
+    float fill_hint = 0.f;  // expected (tokens / (batch * seq_len)) of the next forwards; 0 = unknown (2/3 is assumed)
+};
 
 extern "C" {
 
 int mdr_encoder_create(const mdr_encoder_config* cfg, const mdr_tensor* tensors, int n_tensors, int weights_on_device, int device, void* stream,
                        mdr_encoder** out) {
     MDR_REQUIRE(cfg && tensors && out, "NULL argument");
-    MDR_REQUIRE(cfg->hidden > 0 && cfg->hidden % 128 == 0 && cfg->hidden <= 1024, "hidden=%d unsupported (multiple of 128, <= 1024)", cfg->hidden);
-    MDR_REQUIRE(cfg->heads > 0 && cfg->hidden == cfg->heads * 64, "head dim must be 64 (hidden=%d heads=%d)", cfg->hidden, cfg->heads);
-    MDR_REQUIRE(cfg->ffn > 0 && cfg->ffn % 128 == 0, "ffn=%d must be a multiple of 128", cfg->ffn);
-    MDR_REQUIRE(cfg->layers > 0 && cfg->vocab > 0 && cfg->max_pos > 2, "bad geometry");
-    MDR_REQUIRE(cfg->residual_fp32 >= 0 && cfg->residual_fp32 <= 2, "residual_fp32=%d must be 0, 1 or 2", cfg->residual_fp32);
-    int ndev = 0;
-    MDR_HIP_TRY(hipGetDeviceCount(&ndev));
-    MDR_REQUIRE(device >= 0 && device < ndev, "device %d out of range", device);
+    MDR_REQUIRE(cfg->max_pos > 2, "bad geometry");
+    if (int rc = trunk_check(*cfg, device)) return rc;
     DeviceGuard guard(device);
-    hipStream_t st = (hipStream_t)stream;
     mdr_encoder* h = new (std::nothrow) mdr_encoder();
     MDR_REQUIRE(h != nullptr, "out of host memory");
-    h->cfg = *cfg;
-    h->device = device;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->num_cus = prop.multiProcessorCount;
-    }
-    const int H = cfg->hidden, F = cfg->ffn;
-
-    float* staging = nullptr;
-    size_t staging_elems = (size_t)cfg->vocab * H;
-    if ((size_t)F * H > staging_elems) staging_elems = (size_t)F * H;
-    if ((size_t)H * H > staging_elems) staging_elems = (size_t)H * H;
-    if ((size_t)cfg->max_pos * H > staging_elems) staging_elems = (size_t)cfg->max_pos * H;
-    int rc = MDR_OK;
-    auto fail = [&](int code) {
-        if (staging) (void)hipFree(staging);
+    const size_t H = cfg->hidden;
+    WeightLoader ld{tensors, n_tensors, weights_on_device, (hipStream_t)stream, &h->t.allocs};
+    trunk_upload(h->t, *cfg, device, 1, ld);
+    ld.keep16("project.0.weight", H * H, &h->wproj);
+    ld.keep32("project.0.bias", H, &h->bproj);
+    ld.keep32("project.1.weight", H, &h->lnp_g);
+    ld.keep32("project.1.bias", H, &h->lnp_b);
+    if (int rc = ld.finish()) {
         mdr_encoder_free(h);
-        return code;
-    };
-    if (hipMalloc((void**)&staging, staging_elems * 4) != hipSuccess) return fail(set_error(MDR_E_HIP, "hipMalloc(staging) failed"));
-
-    // fetch `name` (numel checked) into device fp32 memory at dst
-    auto fetch32 = [&](const std::string& name, size_t numel, float* dst) -> int {
-        const mdr_tensor* t = find_tensor(tensors, n_tensors, name);
-        if (!t) return set_error(MDR_E_INVALID, "missing key in state dict: %s", name.c_str());
-        if ((size_t)t->numel != numel) return set_error(MDR_E_INVALID, "size mismatch for %s: expected %zu elements, got %lld", name.c_str(), numel, (long long)t->numel);
-        MDR_HIP_TRY(hipMemcpyAsync(dst, t->data, numel * 4, weights_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        return MDR_OK;
-    };
-    auto alloc = [&](size_t bytes, void** p) -> int {
-        MDR_HIP_TRY(hipMalloc(p, bytes));
-        h->allocs.push_back(*p);
-        return MDR_OK;
-    };
-    auto keep32 = [&](const std::string& name, size_t numel, float** dst) -> int {
-        int r = alloc(numel * 4, (void**)dst);
-        if (r) return r;
-        return fetch32(name, numel, *dst);
-    };
-    // fp32 source -> fp16 at dst (dst already allocated)
-    auto to16 = [&](const std::string& name, size_t numel, _Float16* dst) -> int {
-        int r = fetch32(name, numel, staging);
-        if (r) return r;
-        hipLaunchKernelGGL(f32_to_f16_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, st, (const float*)staging, dst, (long long)numel);
-        MDR_HIP_TRY(hipGetLastError());
-        MDR_HIP_TRY(hipStreamSynchronize(st));  // staging is reused
-        return MDR_OK;
-    };
-#define MDR_TRY(expr) do { rc = (expr); if (rc) return fail(rc); } while (0)
-
-    const std::string E = "encoder.embeddings.";
-    MDR_TRY(keep32(E + "word_embeddings.weight", (size_t)cfg->vocab * H, &h->word));
-    MDR_TRY(keep32(E + "position_embeddings.weight", (size_t)cfg->max_pos * H, &h->pos));
-    MDR_TRY(keep32(E + "token_type_embeddings.weight", (size_t)H, &h->type0));  // row 0 of [type_vocab, H]; type_vocab == 1 for RoBERTa
-    MDR_TRY(keep32(E + "LayerNorm.weight", H, &h->emb_g));
-    MDR_TRY(keep32(E + "LayerNorm.bias", H, &h->emb_b));
-    h->layers.resize(cfg->layers);
-    for (int i = 0; i < cfg->layers; ++i) {
-        mdr_encoder::Layer& Ly = h->layers[i];
-        const std::string P = "encoder.encoder.layer." + std::to_string(i) + ".";
-        MDR_TRY(alloc((size_t)3 * H * H * 2, (void**)&Ly.wqkv));
-        MDR_TRY(alloc((size_t)3 * H * 4, (void**)&Ly.bqkv));
-        const char* qkv_names[3] = {"query", "key", "value"};
-        for (int j = 0; j < 3; ++j) {
-            MDR_TRY(to16(P + "attention.self." + qkv_names[j] + ".weight", (size_t)H * H, Ly.wqkv + (size_t)j * H * H));
-            MDR_TRY(fetch32(P + "attention.self." + qkv_names[j] + ".bias", H, Ly.bqkv + (size_t)j * H));
-        }
-        MDR_TRY(alloc((size_t)H * H * 2, (void**)&Ly.wo));
-        MDR_TRY(to16(P + "attention.output.dense.weight", (size_t)H * H, Ly.wo));
-        MDR_TRY(keep32(P + "attention.output.dense.bias", H, &Ly.bo));
-        MDR_TRY(keep32(P + "attention.output.LayerNorm.weight", H, &Ly.ln1_g));
-        MDR_TRY(keep32(P + "attention.output.LayerNorm.bias", H, &Ly.ln1_b));
-        MDR_TRY(alloc((size_t)F * H * 2, (void**)&Ly.w1));
-        MDR_TRY(to16(P + "intermediate.dense.weight", (size_t)F * H, Ly.w1));
-        MDR_TRY(keep32(P + "intermediate.dense.bias", F, &Ly.b1));
-        MDR_TRY(alloc((size_t)H * F * 2, (void**)&Ly.w2));
-        MDR_TRY(to16(P + "output.dense.weight", (size_t)H * F, Ly.w2));
-        MDR_TRY(keep32(P + "output.dense.bias", H, &Ly.b2));
-        MDR_TRY(keep32(P + "output.LayerNorm.weight", H, &Ly.ln2_g));
-        MDR_TRY(keep32(P + "output.LayerNorm.bias", H, &Ly.ln2_b));
+        return rc;
     }
-    MDR_TRY(alloc((size_t)H * H * 2, (void**)&h->wproj));
-    MDR_TRY(to16("project.0.weight", (size_t)H * H, h->wproj));
-    MDR_TRY(keep32("project.0.bias", H, &h->bproj));
-    MDR_TRY(keep32("project.1.weight", H, &h->lnp_g));
-    MDR_TRY(keep32("project.1.bias", H, &h->lnp_b));
-#undef MDR_TRY
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(set_error(MDR_E_HIP, "stream sync failed after weight upload"));
-    (void)hipFree(staging);
     *out = h;
     return MDR_OK;
 }
@@ -398,9 +273,7 @@ int mdr_test_gemm_f16(const void* A_dev, const void* W_dev, const float* bias_de
 #endif
     DeviceGuard guard(device);
     if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
-    hipDeviceProp_t prop;
-    int ncu = 256;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
+    const int ncu = device_cu_count(device);
     const _Float16* A = (const _Float16*)A_dev;
     const _Float16* W = (const _Float16*)W_dev;
     hipStream_t st = (hipStream_t)stream;
@@ -490,15 +363,14 @@ int mdr_encoder_set_fill_hint(mdr_encoder* h, float fill) {
 
 int mdr_encoder_free(mdr_encoder* h) {
     if (!h) return MDR_OK;
-    DeviceGuard guard(h->device);
-    for (void* p : h->allocs) (void)hipFree(p);
+    trunk_free(h->t);
     delete h;
     return MDR_OK;
 }
 
 size_t mdr_encoder_workspace_bytes(const mdr_encoder* h, int batch, int seq_len) {
     if (!h || batch <= 0 || seq_len <= 0) return 0;
-    return carve(h->cfg, batch, seq_len, nullptr).bytes;
+    return carve(h->t.cfg, batch, seq_len, nullptr).bytes;
 }
 
 int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* mask_dev, int batch, int seq_len, float* out_dev, void* workspace_dev,
@@ -509,18 +381,19 @@ int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* m
     MDR_REQUIRE(ids_dev && mask_dev && out_dev, "NULL pointer");
     MDR_REQUIRE(seq_len <= 512, "seq_len=%d exceeds 512 (RoBERTa has 514 positions)", seq_len);
     MDR_REQUIRE((long long)batch * seq_len < (1ll << 31), "batch*seq_len overflows int32; split the batch");
-    const mdr_encoder_config& c = h->cfg;
-    const size_t need = carve(c, batch, seq_len, nullptr).bytes;
-    if (!workspace_dev || workspace_bytes < need) return set_error(MDR_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    DeviceGuard guard(h->device);
+    const Trunk& t = h->t;
+    const mdr_encoder_config& c = t.cfg;
+    DeviceGuard guard(t.device);
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)(((uintptr_t)workspace_dev + 255) & ~(uintptr_t)255);
-    Workspace w = carve(c, batch, seq_len, base);
-    const int B = batch, L = seq_len, H = c.hidden, F = c.ffn;
+    const long long* ids = (const long long*)ids_dev;
+    Workspace w;
+    if (int rc = trunk_begin(t, ids, (const long long*)mask_dev, batch, seq_len, workspace_dev, workspace_bytes, carve(c, batch, seq_len, nullptr).bytes, st, &w))
+        return rc;
+    const int B = batch, L = seq_len, H = c.hidden;
     const int Tcap = B * L;
     // tile-shape heuristics only: the packed token count is known on the device; the host may pass what it expects
     const int Test = h->fill_hint > 0.f ? std::max(1, (int)(h->fill_hint * (float)Tcap)) : Tcap - Tcap / 3;
-    int ncu = h->num_cus;
+    int ncu = t.num_cus;
 #if MDR_CU_LANES
     {  // CU-partitioned lanes (measurement build): the persistent GEMMs size their grids for the CUs THIS stream may run on. The mask cannot be read while the
        // stream is capturing, so the count of the warm-up call on the same stream is remembered (erased by mdr_stream_destroy); only MASKED streams are rounded
@@ -535,84 +408,31 @@ int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* m
             if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone && hipExtStreamGetCUMask(st, 32, mask) == hipSuccess)
                 for (uint32_t w_ : mask) n += __builtin_popcount(w_);
             else (void)hipGetLastError();
-            if (n >= 8 && n < h->num_cus) ncu = n / 8 * 8;
+            if (n >= 8 && n < t.num_cus) ncu = n / 8 * 8;
             if (cs == hipStreamCaptureStatusNone) g_stream_cus[st] = ncu;
         }
     }
 #endif
-    const long long* ids = (const long long*)ids_dev;
-    const long long* mask = (const long long*)mask_dev;
-
-    hipLaunchKernelGGL(enc_lens_kernel, dim3((B + 3) / 4), dim3(256), 0, st, mask, B, L, w.lens);
-    const int* order = (MDR_ATTN_SORT && B <= 1024) ? w.order : nullptr;
-    hipLaunchKernelGGL(enc_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)w.lens, B, w.cu, w.total, (int*)order);
-    hipLaunchKernelGGL(enc_scatter_kernel, dim3((B + 3) / 4), dim3(256), 0, st, ids, mask, B, L, c.pad_id, (const int*)w.cu, w.tok_src, w.tok_pid);
-    // Residual stream. residual_fp32 = 0: LayerNorm outputs live as fp16 only (GEMM operand AND residual). residual_fp32 = 1:
-    // the apex-O1 regime of the reference -- LayerNorm outputs stay fp32 (w.h32) for the residual adds, and only the copy
-    // that feeds the next Linear is rounded to fp16. In that mode no GEMM epilogue adds the (fp16) residual: every
-    // LayerNorm call takes it from w.h32 and refreshes w.h32 in place.
-    const bool r32 = c.residual_fp32 != 0;
-    const bool p16 = c.residual_fp32 == 2;  // out-projection / FFN2 outputs rounded to fp16 before the residual add (what apex O1's F.linear returns)
-    _Float16* pre16 = (_Float16*)w.pre;     // (the fp16 sums live in the fp32 buffer's memory)
-    _Float16* clspre16 = (_Float16*)w.clspre;
     hipLaunchKernelGGL(embed_ln_kernel, dim3((Tcap + 3) / 4), dim3(256), 0, st, ids, (const int*)w.tok_src, (const int*)w.tok_pid, (const int*)w.total,
-                       (const float*)h->word, (const float*)h->pos, (const float*)h->type0, (const float*)h->emb_g, (const float*)h->emb_b, H, c.vocab,
-                       c.max_pos, c.ln_eps, w.h16, w.h32);
+                       (const float*)t.word, (const float*)t.pos, (const float*)t.type, (const float*)t.emb_g, (const float*)t.emb_b, H, c.vocab, c.max_pos,
+                       c.ln_eps, w.h16, w.h32);
     MDR_HIP_TRY(hipGetLastError());
+    const Rows tokens{w.h16, w.h32, w.pre, Tcap, w.total, Test}, cls{w.cls16, w.cls32, w.clspre, B, nullptr, B};
     int rc;
-    // y = LayerNorm(gemm_out + residual) for `rows` rows: one place that knows where the residual comes from
-    auto post_ln = [&](const float* pre, bool res_in_gemm, const _Float16* res16, float* res32, int rows_cap, const int* rows_dev, const float* g_,
-                       const float* b_, _Float16* out16, float* out32) {
-        if (p16)
-            hipLaunchKernelGGL(layernorm_kernel<_Float16>, dim3((rows_cap + 3) / 4), dim3(256), 0, st, (const _Float16*)pre, (const _Float16*)nullptr,
-                               (const float*)res32, rows_cap, rows_dev, H, g_, b_, c.ln_eps, out16, out32);
-        else
-            hipLaunchKernelGGL(layernorm_kernel<float>, dim3((rows_cap + 3) / 4), dim3(256), 0, st, pre, (const _Float16*)(r32 || res_in_gemm ? nullptr : res16),
-                               (const float*)(r32 ? res32 : nullptr), rows_cap, rows_dev, H, g_, b_, c.ln_eps, out16, (float*)(r32 ? out32 : nullptr));
-    };
-    for (int i = 0; i < c.layers; ++i) {
-        const mdr_encoder::Layer& Ly = h->layers[i];
-        rc = launch_gemm<EPI_BIAS_F16>(w.h16, H, Ly.wqkv, Ly.bqkv, Tcap, w.total, 3 * H, H, w.qkv, 3 * H, nullptr, 0, Test, ncu, st);
+    for (int i = 0; i + 1 < c.layers; ++i) {
+        rc = trunk_layer(t, t.layers[i], w, tokens, B, L, ncu, st);
         if (rc) return rc;
-        if (i + 1 == c.layers) {
-            // ---- last layer: everything after the K/V projection only for the CLS rows ([B, H] instead of [T, H]) ----
-            hipLaunchKernelGGL(gather_cls_kernel, dim3((B * H + 255) / 256), dim3(256), 0, st, (const _Float16*)w.h16, (const float*)w.h32, (const int*)w.cu, B, H,
-                               w.cls16, w.cls32);
-            hipLaunchKernelGGL(attention_cls_kernel, dim3(c.heads, B), dim3(64), 0, st, (const _Float16*)w.qkv, (const int*)w.cu, H, w.ctx);
-            MDR_HIP_TRY(hipGetLastError());
-            bool res_in = true;
-            if (p16) rc = launch_gemm<EPI_BIAS_F16>(w.ctx, H, Ly.wo, Ly.bo, B, nullptr, H, H, clspre16, H, nullptr, 0, B, ncu, st);
-            else if (r32) rc = launch_gemm<EPI_BIAS_F32>(w.ctx, H, Ly.wo, Ly.bo, B, nullptr, H, H, w.clspre, H, nullptr, 0, B, ncu, st);
-            else rc = launch_gemm<EPI_BIAS_RES_F32>(w.ctx, H, Ly.wo, Ly.bo, B, nullptr, H, H, w.clspre, H, w.cls16, H, B, ncu, st, &res_in);
-            if (rc) return rc;
-            post_ln(w.clspre, res_in, w.cls16, w.cls32, B, nullptr, Ly.ln1_g, Ly.ln1_b, w.cls16, w.cls32);
-            rc = launch_gemm<EPI_BIAS_GELU_F16>(w.cls16, H, Ly.w1, Ly.b1, B, nullptr, F, H, w.ffn, F, nullptr, 0, B, ncu, st);
-            if (rc) return rc;
-            if (p16) rc = launch_gemm<EPI_BIAS_F16>(w.ffn, F, Ly.w2, Ly.b2, B, nullptr, H, F, clspre16, H, nullptr, 0, B, ncu, st);
-            else if (r32) rc = launch_gemm<EPI_BIAS_F32>(w.ffn, F, Ly.w2, Ly.b2, B, nullptr, H, F, w.clspre, H, nullptr, 0, B, ncu, st);
-            else rc = launch_gemm<EPI_BIAS_RES_F32>(w.ffn, F, Ly.w2, Ly.b2, B, nullptr, H, F, w.clspre, H, w.cls16, H, B, ncu, st, &res_in);
-            if (rc) return rc;
-            post_ln(w.clspre, res_in, w.cls16, w.cls32, B, nullptr, Ly.ln2_g, Ly.ln2_b, w.cls16, w.cls32);
-            MDR_HIP_TRY(hipGetLastError());
-            break;
-        }
-        rc = launch_attention_for(MDR_ATTN_FORCE, w.qkv, w.cu, order, B, L, H, c.heads, w.ctx, st);
-        if (rc) return rc;
-        bool res_in = true;
-        if (p16) rc = launch_gemm<EPI_BIAS_F16>(w.ctx, H, Ly.wo, Ly.bo, Tcap, w.total, H, H, pre16, H, nullptr, 0, Test, ncu, st);
-        else if (r32) rc = launch_gemm<EPI_BIAS_F32>(w.ctx, H, Ly.wo, Ly.bo, Tcap, w.total, H, H, w.pre, H, nullptr, 0, Test, ncu, st);
-        else rc = launch_gemm<EPI_BIAS_RES_F32>(w.ctx, H, Ly.wo, Ly.bo, Tcap, w.total, H, H, w.pre, H, w.h16, H, Test, ncu, st, &res_in);
-        if (rc) return rc;
-        post_ln(w.pre, res_in, w.h16, w.h32, Tcap, w.total, Ly.ln1_g, Ly.ln1_b, w.h16, w.h32);
-        rc = launch_gemm<EPI_BIAS_GELU_F16>(w.h16, H, Ly.w1, Ly.b1, Tcap, w.total, F, H, w.ffn, F, nullptr, 0, Test, ncu, st);
-        if (rc) return rc;
-        if (p16) rc = launch_gemm<EPI_BIAS_F16>(w.ffn, F, Ly.w2, Ly.b2, Tcap, w.total, H, F, pre16, H, nullptr, 0, Test, ncu, st);
-        else if (r32) rc = launch_gemm<EPI_BIAS_F32>(w.ffn, F, Ly.w2, Ly.b2, Tcap, w.total, H, F, w.pre, H, nullptr, 0, Test, ncu, st);
-        else rc = launch_gemm<EPI_BIAS_RES_F32>(w.ffn, F, Ly.w2, Ly.b2, Tcap, w.total, H, F, w.pre, H, w.h16, H, Test, ncu, st, &res_in);
-        if (rc) return rc;
-        post_ln(w.pre, res_in, w.h16, w.h32, Tcap, w.total, Ly.ln2_g, Ly.ln2_b, w.h16, w.h32);
-        MDR_HIP_TRY(hipGetLastError());
     }
+    // ---- last layer: everything after the K/V projection only for the CLS rows ([B, H] instead of [T, H]) ----
+    const Layer& last = t.layers.back();
+    rc = launch_qkv(t, last, w, tokens, ncu, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(gather_cls_kernel, dim3((B * H + 255) / 256), dim3(256), 0, st, (const _Float16*)w.h16, (const float*)w.h32, (const int*)w.cu, B, H,
+                       w.cls16, w.cls32);
+    hipLaunchKernelGGL(attention_cls_kernel, dim3(c.heads, B), dim3(64), 0, st, (const _Float16*)w.qkv, (const int*)w.cu, H, w.ctx);
+    MDR_HIP_TRY(hipGetLastError());
+    rc = layer_tail(t, last, w.ctx, w.ffn, cls, ncu, st);
+    if (rc) return rc;
     rc = launch_gemm<EPI_BIAS_F32>(w.cls16, H, h->wproj, h->bproj, B, nullptr, H, H, w.clspre, H, nullptr, 0, B, ncu, st);
     if (rc) return rc;
     hipLaunchKernelGGL(layernorm_kernel<float>, dim3((B + 3) / 4), dim3(256), 0, st, (const float*)w.clspre, (const _Float16*)nullptr, (const float*)nullptr, B,

@@ -1,6 +1,7 @@
 // csrc/mdr_reader.inl -- the HotpotQA answer reader (QAModel at inference) on the encoder's kernels. Included at the end of
-// mdr_encoder.hip, after the encoder's host code: it reuses launch_gemm, the attention launchers, layernorm_kernel, the packing
-// kernels, carve() and find_tensor() of that translation unit. Not a translation unit of its own.
+// mdr_encoder.hip, after the encoder's host code. The transformer trunk -- weight upload, workspace, packing and every layer -- is the
+// shared one of mdr_encoder_trunk.inl; this file adds the reader's own embedding kernel, its pooler and heads, and the span search.
+// Not a translation unit of its own.
 //
 // Replaces
 //   /root/reference/mdr/qa/qa_model.py:50-81        encoder(ids, mask, token_type_ids) -> qa_outputs / pooler + rank / sp heads
@@ -199,11 +200,7 @@ __global__ void h16_round_f32_kernel(float* __restrict__ x, int n) {
 
 struct mdr_reader {
     mdr_reader_config cfg{};
-    int device = 0;
-    int num_cus = 256;
-    std::vector<void*> allocs;
-    float *word = nullptr, *pos = nullptr, *type = nullptr, *emb_g = nullptr, *emb_b = nullptr;
-    std::vector<mdr_encoder::Layer> layers;
+    Trunk t;                    // t.type: the whole [type_vocab, H] table
     _Float16* wpool = nullptr;  // pooler dense [H, H]
     float* bpool = nullptr;
     _Float16* whead = nullptr;  // [4, H] rows: start, end, rank, sp
@@ -219,17 +216,16 @@ mdr_encoder_config reader_trunk_config(const mdr_reader_config& c) {
     return e;
 }
 
+// behind the trunk's workspace: the logits, when the caller does not keep them but the span search needs them
 struct ReaderWs {
-    Workspace enc;
-    unsigned short *start16, *end16;  // logits, when the caller does not keep them but the span search needs them
+    unsigned short *start16, *end16;
     size_t bytes;
 };
 
-ReaderWs reader_carve(const mdr_reader_config& c, int B, int L, char* base) {
+ReaderWs reader_carve(const Workspace& enc, int B, int L) {
     ReaderWs r{};
-    r.enc = carve(reader_trunk_config(c), B, L, base);
-    size_t o = align_up(r.enc.bytes, 256);
-    auto take = [&](size_t n) { size_t at = o; o += align_up(n, 256); return base ? base + at : (char*)nullptr; };
+    size_t o = align_up(enc.bytes, 256);
+    auto take = [&](size_t n) { size_t at = o; o += align_up(n, 256); return enc.base ? enc.base + at : (char*)nullptr; };
     r.start16 = (unsigned short*)take((size_t)B * L * 2);
     r.end16 = (unsigned short*)take((size_t)B * L * 2);
     r.bytes = o + 256;
@@ -250,126 +246,53 @@ extern "C" {
 int mdr_reader_create(const mdr_reader_config* cfg, const mdr_tensor* tensors, int n_tensors, int weights_on_device, int device, void* stream,
                       mdr_reader** out) {
     MDR_REQUIRE(cfg && tensors && out, "NULL argument");
-    MDR_REQUIRE(cfg->hidden > 0 && cfg->hidden % 128 == 0 && cfg->hidden <= 1024, "hidden=%d unsupported (multiple of 128, <= 1024)", cfg->hidden);
-    MDR_REQUIRE(cfg->heads > 0 && cfg->hidden == cfg->heads * 64, "head dim must be 64 (hidden=%d heads=%d)", cfg->hidden, cfg->heads);
-    MDR_REQUIRE(cfg->ffn > 0 && cfg->ffn % 128 == 0, "ffn=%d must be a multiple of 128", cfg->ffn);
-    MDR_REQUIRE(cfg->layers > 0 && cfg->vocab > 0 && cfg->max_pos > 0 && cfg->type_vocab > 0, "bad geometry");
-    MDR_REQUIRE(cfg->residual_fp32 >= 0 && cfg->residual_fp32 <= 2, "residual_fp32=%d must be 0, 1 or 2", cfg->residual_fp32);
+    MDR_REQUIRE(cfg->type_vocab > 0, "bad geometry");
     MDR_REQUIRE(cfg->pooler == MDR_READER_POOLER_HEAD || cfg->pooler == MDR_READER_POOLER_ENCODER, "pooler=%d unknown", cfg->pooler);
     for (int i = 0; i < n_tensors; ++i)
         MDR_REQUIRE(!(tensors[i].name && std::strncmp(tensors[i].name, "encoder.embeddings_project.", 27) == 0),
                     "embeddings_project (embedding size != hidden, ELECTRA-small) is not supported");
-    int ndev = 0;
-    MDR_HIP_TRY(hipGetDeviceCount(&ndev));
-    MDR_REQUIRE(device >= 0 && device < ndev, "device %d out of range", device);
+    const mdr_encoder_config tc = reader_trunk_config(*cfg);
+    if (int rc = trunk_check(tc, device)) return rc;
     DeviceGuard guard(device);
     hipStream_t st = (hipStream_t)stream;
     mdr_reader* h = new (std::nothrow) mdr_reader();
     MDR_REQUIRE(h != nullptr, "out of host memory");
     h->cfg = *cfg;
-    h->device = device;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->num_cus = prop.multiProcessorCount;
-    }
-    const int H = cfg->hidden, F = cfg->ffn;
-    float* staging = nullptr;
-    size_t staging_elems = std::max({(size_t)F * H, (size_t)H * H, (size_t)4 * H});
-    int rc = MDR_OK;
-    auto fail = [&](int code) {
-        if (staging) (void)hipFree(staging);
-        mdr_reader_free(h);
-        return code;
-    };
-    if (hipMalloc((void**)&staging, staging_elems * 4) != hipSuccess) return fail(set_error(MDR_E_HIP, "hipMalloc(staging) failed"));
-    auto fetch32 = [&](const std::string& name, size_t numel, float* dst) -> int {
-        const mdr_tensor* t = find_tensor(tensors, n_tensors, name);
-        if (!t) return set_error(MDR_E_INVALID, "missing key in state dict: %s", name.c_str());
-        if ((size_t)t->numel != numel) return set_error(MDR_E_INVALID, "size mismatch for %s: expected %zu elements, got %lld", name.c_str(), numel, (long long)t->numel);
-        MDR_HIP_TRY(hipMemcpyAsync(dst, t->data, numel * 4, weights_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        return MDR_OK;
-    };
-    auto alloc = [&](size_t bytes, void** p) -> int {
-        MDR_HIP_TRY(hipMalloc(p, bytes));
-        h->allocs.push_back(*p);
-        return MDR_OK;
-    };
-    auto keep32 = [&](const std::string& name, size_t numel, float** dst) -> int {
-        int r = alloc(numel * 4, (void**)dst);
-        if (r) return r;
-        return fetch32(name, numel, *dst);
-    };
-    auto to16 = [&](const std::string& name, size_t numel, _Float16* dst) -> int {
-        int r = fetch32(name, numel, staging);
-        if (r) return r;
-        hipLaunchKernelGGL(f32_to_f16_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, st, (const float*)staging, dst, (long long)numel);
-        MDR_HIP_TRY(hipGetLastError());
-        MDR_HIP_TRY(hipStreamSynchronize(st));  // staging is reused
-        return MDR_OK;
-    };
-#define MDR_TRY(expr) do { rc = (expr); if (rc) return fail(rc); } while (0)
-    const std::string E = "encoder.embeddings.";
-    MDR_TRY(keep32(E + "word_embeddings.weight", (size_t)cfg->vocab * H, &h->word));
-    MDR_TRY(keep32(E + "position_embeddings.weight", (size_t)cfg->max_pos * H, &h->pos));
-    MDR_TRY(keep32(E + "token_type_embeddings.weight", (size_t)cfg->type_vocab * H, &h->type));
-    MDR_TRY(keep32(E + "LayerNorm.weight", H, &h->emb_g));
-    MDR_TRY(keep32(E + "LayerNorm.bias", H, &h->emb_b));
-    h->layers.resize(cfg->layers);
-    for (int i = 0; i < cfg->layers; ++i) {
-        mdr_encoder::Layer& Ly = h->layers[i];
-        const std::string P = "encoder.encoder.layer." + std::to_string(i) + ".";
-        MDR_TRY(alloc((size_t)3 * H * H * 2, (void**)&Ly.wqkv));
-        MDR_TRY(alloc((size_t)3 * H * 4, (void**)&Ly.bqkv));
-        const char* qkv_names[3] = {"query", "key", "value"};
-        for (int j = 0; j < 3; ++j) {
-            MDR_TRY(to16(P + "attention.self." + qkv_names[j] + ".weight", (size_t)H * H, Ly.wqkv + (size_t)j * H * H));
-            MDR_TRY(fetch32(P + "attention.self." + qkv_names[j] + ".bias", H, Ly.bqkv + (size_t)j * H));
-        }
-        MDR_TRY(alloc((size_t)H * H * 2, (void**)&Ly.wo));
-        MDR_TRY(to16(P + "attention.output.dense.weight", (size_t)H * H, Ly.wo));
-        MDR_TRY(keep32(P + "attention.output.dense.bias", H, &Ly.bo));
-        MDR_TRY(keep32(P + "attention.output.LayerNorm.weight", H, &Ly.ln1_g));
-        MDR_TRY(keep32(P + "attention.output.LayerNorm.bias", H, &Ly.ln1_b));
-        MDR_TRY(alloc((size_t)F * H * 2, (void**)&Ly.w1));
-        MDR_TRY(to16(P + "intermediate.dense.weight", (size_t)F * H, Ly.w1));
-        MDR_TRY(keep32(P + "intermediate.dense.bias", F, &Ly.b1));
-        MDR_TRY(alloc((size_t)H * F * 2, (void**)&Ly.w2));
-        MDR_TRY(to16(P + "output.dense.weight", (size_t)H * F, Ly.w2));
-        MDR_TRY(keep32(P + "output.dense.bias", H, &Ly.b2));
-        MDR_TRY(keep32(P + "output.LayerNorm.weight", H, &Ly.ln2_g));
-        MDR_TRY(keep32(P + "output.LayerNorm.bias", H, &Ly.ln2_b));
-    }
+    const size_t H = cfg->hidden;
+    WeightLoader ld{tensors, n_tensors, weights_on_device, st, &h->t.allocs};
+    trunk_upload(h->t, tc, device, cfg->type_vocab, ld);
     const std::string PL = cfg->pooler == MDR_READER_POOLER_HEAD ? "pooler.dense." : "encoder.pooler.dense.";
-    MDR_TRY(alloc((size_t)H * H * 2, (void**)&h->wpool));
-    MDR_TRY(to16(PL + "weight", (size_t)H * H, h->wpool));
-    MDR_TRY(keep32(PL + "bias", H, &h->bpool));
+    ld.keep16(PL + "weight", H * H, &h->wpool);
+    ld.keep32(PL + "bias", H, &h->bpool);
     // the four head rows go through the fp32 staging buffer in one [4, H] block (the sp row stays 0 without sp.*)
-    MDR_TRY(alloc((size_t)4 * H * 2, (void**)&h->whead));
-    MDR_TRY(alloc(4 * 4, (void**)&h->bhead));
-    if (hipMemsetAsync(staging, 0, (size_t)4 * H * 4, st) != hipSuccess || hipMemsetAsync(h->bhead, 0, 16, st) != hipSuccess)
-        return fail(set_error(MDR_E_HIP, "hipMemsetAsync failed"));
-    MDR_TRY(fetch32("qa_outputs.weight", (size_t)2 * H, staging));
-    MDR_TRY(fetch32("qa_outputs.bias", 2, h->bhead));
-    MDR_TRY(fetch32("rank.weight", H, staging + (size_t)2 * H));
-    MDR_TRY(fetch32("rank.bias", 1, h->bhead + 2));
+    ld.alloc(4 * H * 2, (void**)&h->whead);
+    ld.alloc(4 * 4, (void**)&h->bhead);
+    if (!ld.rc && (hipMemsetAsync(ld.staging, 0, 4 * H * 4, st) != hipSuccess || hipMemsetAsync(h->bhead, 0, 16, st) != hipSuccess))
+        ld.rc = set_error(MDR_E_HIP, "hipMemsetAsync failed");
+    ld.fetch32("qa_outputs.weight", 2 * H, ld.staging);
+    ld.fetch32("qa_outputs.bias", 2, h->bhead);
+    ld.fetch32("rank.weight", H, ld.staging, 2 * H);
+    ld.fetch32("rank.bias", 1, h->bhead, 2);
     if (cfg->has_sp) {
-        MDR_TRY(fetch32("sp.weight", H, staging + (size_t)3 * H));
-        MDR_TRY(fetch32("sp.bias", 1, h->bhead + 3));
+        ld.fetch32("sp.weight", H, ld.staging, 3 * H);
+        ld.fetch32("sp.bias", 1, h->bhead, 3);
     }
-    hipLaunchKernelGGL(f32_to_f16_kernel, dim3((unsigned)((4 * H + 255) / 256)), dim3(256), 0, st, (const float*)staging, h->whead, (long long)4 * H);
-    hipLaunchKernelGGL(h16_round_f32_kernel, dim3(1), dim3(64), 0, st, h->bhead, 4);
-    if (hipGetLastError() != hipSuccess) return fail(set_error(MDR_E_HIP, "head weight conversion failed"));
-#undef MDR_TRY
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(set_error(MDR_E_HIP, "stream sync failed after weight upload"));
-    (void)hipFree(staging);
+    ld.convert16(4 * H, h->whead);
+    if (!ld.rc) {
+        hipLaunchKernelGGL(h16_round_f32_kernel, dim3(1), dim3(64), 0, st, h->bhead, 4);
+        if (hipGetLastError() != hipSuccess) ld.rc = set_error(MDR_E_HIP, "head weight conversion failed");
+    }
+    if (int rc = ld.finish()) {
+        mdr_reader_free(h);
+        return rc;
+    }
     *out = h;
     return MDR_OK;
 }
 
 int mdr_reader_free(mdr_reader* h) {
     if (!h) return MDR_OK;
-    DeviceGuard guard(h->device);
-    for (void* p : h->allocs) (void)hipFree(p);
+    trunk_free(h->t);
     delete h;
     return MDR_OK;
 }
@@ -377,7 +300,7 @@ int mdr_reader_free(mdr_reader* h) {
 size_t mdr_reader_workspace_bytes(const mdr_reader* h, int batch, int seq_len, int n_sent) {
     (void)n_sent;
     if (!h || batch <= 0 || seq_len <= 0) return 0;
-    return reader_carve(h->cfg, batch, seq_len, nullptr).bytes;
+    return reader_carve(carve(h->t.cfg, batch, seq_len, nullptr), batch, seq_len).bytes;
 }
 
 int mdr_reader_span_search(const uint16_t* start_logits_dev, const uint16_t* end_logits_dev, int batch, int seq_len, int max_ans_len,
@@ -406,65 +329,28 @@ int mdr_reader_forward(mdr_reader* h, const int64_t* ids_dev, const int64_t* mas
     MDR_REQUIRE(!(o->sp_score || o->sp_prob) || rc_.has_sp, "sp outputs requested but the reader has no sp head (has_sp=0)");
     MDR_REQUIRE(max_ans_len >= 0 || !o->span_start, "max_ans_len=%d must be >= 0", max_ans_len);
     MDR_REQUIRE(!o->span_start || (o->span_end && o->span_score), "span_start given without span_end / span_score");
-    const size_t need = reader_carve(rc_, batch, seq_len, nullptr).bytes;
-    if (!workspace_dev || workspace_bytes < need) return set_error(MDR_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", h->device);
+    const Trunk& t = h->t;
+    const mdr_encoder_config& c = t.cfg;
+    DeviceGuard guard(t.device);
+    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", t.device);
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)(((uintptr_t)workspace_dev + 255) & ~(uintptr_t)255);
-    ReaderWs rw = reader_carve(rc_, batch, seq_len, base);
-    Workspace& w = rw.enc;
-    const mdr_encoder_config c = reader_trunk_config(rc_);
-    const int B = batch, L = seq_len, H = c.hidden, F = c.ffn, ncu = h->num_cus;
-    const int Tcap = B * L;
-    const int Test = Tcap - Tcap / 3;  // tile-shape heuristic only
     const long long* ids = (const long long*)ids_dev;
-    const long long* mask = (const long long*)mask_dev;
-
-    // packing as in the encoder (tok_pid, the RoBERTa position ids, is not read here)
-    hipLaunchKernelGGL(enc_lens_kernel, dim3((B + 3) / 4), dim3(256), 0, st, mask, B, L, w.lens);
-    const int* order = (MDR_ATTN_SORT && B <= 1024) ? w.order : nullptr;
-    hipLaunchKernelGGL(enc_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)w.lens, B, w.cu, w.total, (int*)order);
-    hipLaunchKernelGGL(enc_scatter_kernel, dim3((B + 3) / 4), dim3(256), 0, st, ids, mask, B, L, 0, (const int*)w.cu, w.tok_src, w.tok_pid);
+    const size_t need = reader_carve(carve(c, batch, seq_len, nullptr), batch, seq_len).bytes;
+    Workspace w;  // packing as in the encoder (tok_pid, the RoBERTa position ids, is not read here)
+    if (int rc = trunk_begin(t, ids, (const long long*)mask_dev, batch, seq_len, workspace_dev, workspace_bytes, need, st, &w)) return rc;
+    const ReaderWs rw = reader_carve(w, batch, seq_len);
+    const int B = batch, L = seq_len, H = c.hidden, ncu = t.num_cus;
+    const int Tcap = B * L;
     hipLaunchKernelGGL(reader_embed_ln_kernel, dim3((Tcap + 3) / 4), dim3(256), 0, st, ids, (const long long*)token_type_ids_dev, (const int*)w.tok_src,
-                       (const int*)w.total, L, (const float*)h->word, (const float*)h->pos, (const float*)h->type, rc_.type_vocab, (const float*)h->emb_g,
-                       (const float*)h->emb_b, H, c.vocab, c.ln_eps, w.h16, w.h32);
+                       (const int*)w.total, L, (const float*)t.word, (const float*)t.pos, (const float*)t.type, rc_.type_vocab, (const float*)t.emb_g,
+                       (const float*)t.emb_b, H, c.vocab, c.ln_eps, w.h16, w.h32);
     MDR_HIP_TRY(hipGetLastError());
-    // every layer over all packed tokens (the encoder's non-CLS layer body; residual modes as mdr_encoder_forward documents them)
-    const bool r32 = c.residual_fp32 != 0;
-    const bool p16 = c.residual_fp32 == 2;
-    _Float16* pre16 = (_Float16*)w.pre;
-    auto post_ln = [&](const float* g_, const float* b_, bool res_in_gemm) {
-        if (p16)
-            hipLaunchKernelGGL(layernorm_kernel<_Float16>, dim3((Tcap + 3) / 4), dim3(256), 0, st, (const _Float16*)w.pre, (const _Float16*)nullptr,
-                               (const float*)w.h32, Tcap, (const int*)w.total, H, g_, b_, c.ln_eps, w.h16, w.h32);
-        else
-            hipLaunchKernelGGL(layernorm_kernel<float>, dim3((Tcap + 3) / 4), dim3(256), 0, st, (const float*)w.pre,
-                               (const _Float16*)(r32 || res_in_gemm ? nullptr : w.h16), (const float*)(r32 ? w.h32 : nullptr), Tcap, (const int*)w.total, H,
-                               g_, b_, c.ln_eps, w.h16, (float*)(r32 ? w.h32 : nullptr));
-    };
+    // every layer over all packed tokens: the heads need every token's final hidden state
+    const Rows tokens{w.h16, w.h32, w.pre, Tcap, w.total, Tcap - Tcap / 3};
     int rc;
-    for (int i = 0; i < c.layers; ++i) {
-        const mdr_encoder::Layer& Ly = h->layers[i];
-        rc = launch_gemm<EPI_BIAS_F16>(w.h16, H, Ly.wqkv, Ly.bqkv, Tcap, w.total, 3 * H, H, w.qkv, 3 * H, nullptr, 0, Test, ncu, st);
+    for (const Layer& Ly : t.layers) {
+        rc = trunk_layer(t, Ly, w, tokens, B, L, ncu, st);
         if (rc) return rc;
-        rc = launch_attention_for(MDR_ATTN_FORCE, w.qkv, w.cu, order, B, L, H, c.heads, w.ctx, st);
-        if (rc) return rc;
-        bool res_in = true;
-        if (p16) rc = launch_gemm<EPI_BIAS_F16>(w.ctx, H, Ly.wo, Ly.bo, Tcap, w.total, H, H, pre16, H, nullptr, 0, Test, ncu, st);
-        else if (r32) rc = launch_gemm<EPI_BIAS_F32>(w.ctx, H, Ly.wo, Ly.bo, Tcap, w.total, H, H, w.pre, H, nullptr, 0, Test, ncu, st);
-        else rc = launch_gemm<EPI_BIAS_RES_F32>(w.ctx, H, Ly.wo, Ly.bo, Tcap, w.total, H, H, w.pre, H, w.h16, H, Test, ncu, st, &res_in);
-        if (rc) return rc;
-        post_ln(Ly.ln1_g, Ly.ln1_b, res_in);
-        rc = launch_gemm<EPI_BIAS_GELU_F16>(w.h16, H, Ly.w1, Ly.b1, Tcap, w.total, F, H, w.ffn, F, nullptr, 0, Test, ncu, st);
-        if (rc) return rc;
-        res_in = true;
-        if (p16) rc = launch_gemm<EPI_BIAS_F16>(w.ffn, F, Ly.w2, Ly.b2, Tcap, w.total, H, F, pre16, H, nullptr, 0, Test, ncu, st);
-        else if (r32) rc = launch_gemm<EPI_BIAS_F32>(w.ffn, F, Ly.w2, Ly.b2, Tcap, w.total, H, F, w.pre, H, nullptr, 0, Test, ncu, st);
-        else rc = launch_gemm<EPI_BIAS_RES_F32>(w.ffn, F, Ly.w2, Ly.b2, Tcap, w.total, H, F, w.pre, H, w.h16, H, Test, ncu, st, &res_in);
-        if (rc) return rc;
-        post_ln(Ly.ln2_g, Ly.ln2_b, res_in);
-        MDR_HIP_TRY(hipGetLastError());
     }
     // ---- heads on the fp16 final hidden states w.h16 [T, H] ----
     unsigned short* start16 = o->start_logits ? o->start_logits : rw.start16;

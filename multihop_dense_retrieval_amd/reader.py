@@ -20,7 +20,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .retriever import load_saved, move_to_cuda  # noqa: F401  (the reference's utils: module.-prefix strip, exact=False filtering)
+from .retriever import _HipModule, load_saved, move_to_cuda, trunk_state_dict_shapes  # noqa: F401  (load_saved, move_to_cuda: the reference's utils)
 
 _c = ctypes
 
@@ -103,20 +103,8 @@ def model_family(model_name, config):
 def expected_state_dict_shapes(config, family, sp_pred):
     """QAModel.state_dict() of the reference (the encoder's buffers aside): encoder.embeddings.*, encoder.encoder.layer.{i}.*, the
     pooler (QAModel's for ELECTRA, the encoder's for BERT), qa_outputs.*, rank.*, sp.* with --sp-pred."""
-    H, F = config.hidden_size, config.intermediate_size
-    E = "encoder.embeddings."
-    s = {E + "word_embeddings.weight": (config.vocab_size, H), E + "position_embeddings.weight": (config.max_position_embeddings, H),
-         E + "token_type_embeddings.weight": (config.type_vocab_size, H), E + "LayerNorm.weight": (H,), E + "LayerNorm.bias": (H,)}
-    for i in range(config.num_hidden_layers):
-        P = f"encoder.encoder.layer.{i}."
-        for n in ("query", "key", "value"):
-            s[P + f"attention.self.{n}.weight"] = (H, H)
-            s[P + f"attention.self.{n}.bias"] = (H,)
-        s.update({P + "attention.output.dense.weight": (H, H), P + "attention.output.dense.bias": (H,),
-                  P + "attention.output.LayerNorm.weight": (H,), P + "attention.output.LayerNorm.bias": (H,),
-                  P + "intermediate.dense.weight": (F, H), P + "intermediate.dense.bias": (F,),
-                  P + "output.dense.weight": (H, F), P + "output.dense.bias": (H,),
-                  P + "output.LayerNorm.weight": (H,), P + "output.LayerNorm.bias": (H,)})
+    H = config.hidden_size
+    s = trunk_state_dict_shapes(config, config.type_vocab_size)
     pool = "pooler.dense." if family == "electra" else "encoder.pooler.dense."
     s.update({pool + "weight": (H, H), pool + "bias": (H,), "qa_outputs.weight": (2, H), "qa_outputs.bias": (2,),
               "rank.weight": (1, H), "rank.bias": (1,)})
@@ -125,28 +113,21 @@ def expected_state_dict_shapes(config, family, sp_pred):
     return s
 
 
-class QAModel:
+class QAModel(_HipModule):
     """qa_model.py:27-109 at inference. `args` needs model_name and sp_pred (sp_weight is a training knob and is not read)."""
 
+    _KIND = "reader"
     RESIDUAL_FP32_DEFAULT = 2  # mdr_reader_config.residual_fp32: the apex-O1 dataflow around the LayerNorms (as the retrieval encoder)
 
     def __init__(self, config, args):
+        super().__init__()
         self.config = config
         self.model_name = args.model_name
         self.sp_pred = bool(getattr(args, "sp_pred", False))
         self.family = model_family(self.model_name, config)
         self._shapes = expected_state_dict_shapes(config, self.family, self.sp_pred)
         self.residual_fp32 = self.RESIDUAL_FP32_DEFAULT
-        self._h = ctypes.c_void_p()
-        self._pending = None
         self._ws = None
-        self.device = None
-        self.training = False
-
-    # -- nn.Module-like surface ----------------------------------------------------------------------------
-    def state_dict(self):
-        """Key set only (values are shapes): load_saved(exact=False) filters a checkpoint with it."""
-        return self._shapes
 
     def load_state_dict(self, state_dict, strict=True):
         missing = [k for k in self._shapes if k not in state_dict]
@@ -161,29 +142,10 @@ class QAModel:
             self._create()
         return self
 
-    def to(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("the reader runs on a HIP device only (there is no CPU fallback)")
-        self.device = torch.device("cuda", device.index if device.index is not None else torch.cuda.current_device())
-        if self._pending is not None:
-            self._create()
-        return self
-
-    def cuda(self):
-        return self.to("cuda")
-
-    def eval(self):
-        self.training = False
-        return self
-
     def train(self, mode=True):
         if mode:
             raise NotImplementedError("training is not supported: the reader runs inference only")
         return self.eval()
-
-    def half(self):  # apex-O1 numerics are built in
-        return self
 
     # -- forward ---------------------------------------------------------------------------------------------
     def _run(self, batch, max_ans_len=None, want_logits=True):
@@ -252,30 +214,15 @@ class QAModel:
                            c.type_vocab_size, float(getattr(c, "layer_norm_eps", 1e-12)), int(self.residual_fp32), int(self.sp_pred),
                            POOLER_HEAD if self.family == "electra" else POOLER_ENCODER)
         names = list(sd)
-        on_dev = all(sd[k].is_cuda for k in names)
-        keep = []
-        arr = (_lib.Tensor * len(names))()
-        for i, k in enumerate(names):
-            t = sd[k].detach().to(dtype=torch.float32)
-            t = t.contiguous() if on_dev else t.cpu().contiguous()
-            keep.append(t)
-            arr[i] = _lib.Tensor(k.encode(), ctypes.c_void_p(t.data_ptr()), t.numel())
+        arr, keep, on_dev = _lib.tensor_table(sd, names)
         self._free()
         with torch.cuda.device(self.device):
             _lib.check(lib().mdr_reader_create(ctypes.byref(cfg), arr, len(names), int(on_dev), self.device.index, _lib.current_stream_ptr(self.device),
                                                ctypes.byref(self._h)))
         self._pending = None
 
-    def _free(self):
-        if self._h.value:
-            lib().mdr_reader_free(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self._free()
-        except Exception:
-            pass
+    def _release(self, h):
+        lib().mdr_reader_free(h)
 
 
 def span_search(start_logits, end_logits, max_ans_len):

@@ -33,14 +33,15 @@ class RobertaConfig:
         self.max_position_embeddings, self.layer_norm_eps, self.pad_token_id = max_position_embeddings, layer_norm_eps, pad_token_id
 
 
-def expected_state_dict_shapes(config, with_pooler=True):
-    """Keys and shapes of the reference model's state_dict (HF RobertaModel + project head)."""
+def trunk_state_dict_shapes(config, type_rows):
+    """Keys and shapes of the transformer trunk both models share (HF `encoder.embeddings.*` and `encoder.encoder.layer.{i}.*`), in state_dict
+    order; type_rows: rows of the token-type table."""
     H, F = config.hidden_size, config.intermediate_size
     sd = OrderedDict()
     e = "encoder.embeddings."
     sd[e + "word_embeddings.weight"] = (config.vocab_size, H)
     sd[e + "position_embeddings.weight"] = (config.max_position_embeddings, H)
-    sd[e + "token_type_embeddings.weight"] = (1, H)
+    sd[e + "token_type_embeddings.weight"] = (type_rows, H)
     sd[e + "LayerNorm.weight"] = (H,)
     sd[e + "LayerNorm.bias"] = (H,)
     for i in range(config.num_hidden_layers):
@@ -58,6 +59,13 @@ def expected_state_dict_shapes(config, with_pooler=True):
         sd[p + "output.dense.bias"] = (H,)
         sd[p + "output.LayerNorm.weight"] = (H,)
         sd[p + "output.LayerNorm.bias"] = (H,)
+    return sd
+
+
+def expected_state_dict_shapes(config, with_pooler=True):
+    """Keys and shapes of the reference model's state_dict (HF RobertaModel + project head)."""
+    H = config.hidden_size
+    sd = trunk_state_dict_shapes(config, 1)
     if with_pooler:
         sd["encoder.pooler.dense.weight"] = (H, H)
         sd["encoder.pooler.dense.bias"] = (H,)
@@ -68,6 +76,54 @@ def expected_state_dict_shapes(config, with_pooler=True):
     return sd
 
 
+class _HipModule:
+    """The nn.Module-like surface the reference scripts use, over one native handle that holds the weights. A subclass names itself in
+    _KIND, builds self._shapes, keeps its own load_state_dict policy (which leaves the accepted tensors in self._pending), uploads them in
+    _create() and returns a handle to the library in _release()."""
+
+    _KIND = "module"
+
+    def __init__(self):
+        self._h = ctypes.c_void_p()
+        self._pending = None
+        self.device = None
+        self.training = False
+
+    def state_dict(self):
+        """Key set only (values are shapes): load_saved(exact=False) filters a checkpoint with it."""
+        return self._shapes
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"the {self._KIND} runs on a HIP device only (there is no CPU fallback)")
+        self.device = torch.device("cuda", device.index if device.index is not None else torch.cuda.current_device())
+        if self._pending is not None:
+            self._create()
+        return self
+
+    def cuda(self):
+        return self.to("cuda")
+
+    def eval(self):
+        self.training = False
+        return self
+
+    def half(self):  # apex-O1 numerics are built in
+        return self
+
+    def _free(self):
+        if self._h.value:
+            self._release(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self._free()
+        except Exception:
+            pass
+
+
 class _Lane:
     def __init__(self):
         self.ws = None
@@ -75,9 +131,11 @@ class _Lane:
         self.seen = {}
 
 
-class _HipRobertaEncoder:
+class _HipRobertaEncoder(_HipModule):
     """Shared implementation of the two reference classes (they compute the same function,
     SURVEY.md §8a row a23)."""
+
+    _KIND = "encoder"
 
     MAX_TOKENS_PER_CALL = 1 << 17  # workspace bound: larger batches are encoded in slices
     # numerics mode of the residual stream (mdr_encoder_config.residual_fp32): 0 = fp16 residual copy (one rounding more per LayerNorm than apex O1),
@@ -86,10 +144,10 @@ class _HipRobertaEncoder:
     RESIDUAL_FP32_DEFAULT = 2
 
     def __init__(self, config, args=None):
+        super().__init__()
         self.config = config
         self.args = args
         self._shapes = expected_state_dict_shapes(config)
-        self._h = ctypes.c_void_p()
         # per-lane scratch state: a lane = one workspace + its captured graphs. Two forwards may be in flight at once (on two
         # streams) when they use different lanes; the C handle itself only holds the weights.
         self._lanes = {}
@@ -102,13 +160,6 @@ class _HipRobertaEncoder:
         # apex-O1-faithful fp32 residual stream (mdr_encoder_config.residual_fp32); MDR_RESIDUAL_FP32=0/1/2 overrides the default for
         # measurements before the weights are uploaded
         self.residual_fp32 = int(os.environ.get("MDR_RESIDUAL_FP32", str(int(self.RESIDUAL_FP32_DEFAULT))))
-        self.device = None
-        self.training = False
-
-    # -- nn.Module-like surface used by the reference scripts -------------------------------------------
-    def state_dict(self):
-        """Key set only (values are shapes): load_saved(exact=False) filters a checkpoint with it."""
-        return self._shapes
 
     def load_state_dict(self, state_dict, strict=True):
         missing = [k for k in self._shapes if k not in state_dict]
@@ -121,25 +172,6 @@ class _HipRobertaEncoder:
         self._pending = {k: v for k, v in state_dict.items() if k in self._shapes}
         if self.device is not None:
             self._create()
-        return self
-
-    def to(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("the encoder runs on a HIP device only (there is no CPU fallback)")
-        self.device = torch.device("cuda", device.index if device.index is not None else torch.cuda.current_device())
-        if getattr(self, "_pending", None) is not None:
-            self._create()
-        return self
-
-    def cuda(self):
-        return self.to("cuda")
-
-    def eval(self):
-        self.training = False
-        return self
-
-    def half(self):  # apex-O1-equivalent numerics are built in
         return self
 
     # -- the forward ----------------------------------------------------------------------------------------
@@ -305,29 +337,15 @@ class _HipRobertaEncoder:
                                  self.config.intermediate_size, self.config.max_position_embeddings, self.config.pad_token_id,
                                  float(self.config.layer_norm_eps), int(self.residual_fp32))
         names = [k for k in sd if "pooler" not in k]  # the pooler is never evaluated (`[0]` = sequence output)
-        on_dev = all(sd[k].is_cuda for k in names)
-        keep = []
-        arr = (_lib.Tensor * len(names))()
-        for i, k in enumerate(names):
-            t = sd[k].detach().to(dtype=torch.float32)
-            t = t.contiguous() if on_dev else t.cpu().contiguous()
-            keep.append(t)
-            arr[i] = _lib.Tensor(k.encode(), ctypes.c_void_p(t.data_ptr()), t.numel())
-        if self._h.value:
-            _lib.lib().mdr_encoder_free(self._h)
-            self._h = ctypes.c_void_p()
+        arr, keep, on_dev = _lib.tensor_table(sd, names)
+        self._free()
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mdr_encoder_create(ctypes.byref(cfg), arr, len(names), int(on_dev), self.device.index,
                                                      _lib.current_stream_ptr(self.device), ctypes.byref(self._h)))
         self._pending = None
 
-    def __del__(self):
-        try:
-            if self._h.value:
-                _lib.lib().mdr_encoder_free(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
+    def _release(self, h):
+        _lib.lib().mdr_encoder_free(h)
 
     @classmethod
     def random_init(cls, device, seed=0, config=None):
