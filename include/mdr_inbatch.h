@@ -55,4 +55,7 @@ int mdr_inbatch_rank(const float* q_dev, const float* qsp_dev, const float* ctx_
 }
 #endif
 
+/* the in-batch loss with the memory bank and its gradients: same conventions, same modes, its own header */
+#include "mdr_inbatch_loss.h"
+
 #endif /* MDR_INBATCH_H */

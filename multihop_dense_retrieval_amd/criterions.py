@@ -2,6 +2,10 @@
 
     mhop_eval(outputs, args)         :153-182  -> {"rrs_1": [...], "rrs_2": [...]}, on the device (include/mdr_inbatch.h)
     mhop_loss_value(outputs, fp16)   :114-151  the forward value of mhop_loss from the same kernel's log-sum-exp outputs
+    mhop_loss_outputs(outputs, args, queue)    the loss as a 0-d device tensor WITH gradients for the six matrices, over 2B + 2 + K
+                                     columns (K rows of a memory bank): mdr_inbatch_loss_forward / _backward, a torch.autograd.Function
+    mhop_loss(model, batch, args)    :114-151  the reference's signature, with its --momentum branch (score, then enqueue)
+    MemoryBank(k, d, device)         queue / queue_ptr / dequeue_and_enqueue of RobertaMomentumRetriever (mhop_retriever.py:64-106)
     mhop_eval_host(outputs, fp16)    the reference formula stated on the CPU (tests; not a fallback: mhop_eval never calls it)
 
 `outputs` is what RobertaRetriever.forward returns: six [B, d] fp32 matrices q, q_sp1, c1, c2, neg_1, neg_2. Row i of a hop is
@@ -18,7 +22,9 @@ which patches torch.mm / torch.bmm process-wide to cast their operands to fp16; 
 score is fp16(fp32 accumulation of fp16(q) * fp16(c)), and the `.float().masked_fill(-inf).type_as(...)` round trip keeps it fp16.
 CrossEntropyLoss runs in fp32 under O1, so the log-sum-exp is taken in fp32 over those fp16 values. This is apex behaviour as
 remembered (apex is not installable offline, so no O1 run of the reference could be captured): the rounding points are pinned by
-construction and by the exact-grid tests (tests/test_inbatch_rank_gpu.py), as reader.py does for its heads.
+construction and by the exact-grid tests (tests/test_inbatch_rank_gpu.py), as reader.py does for its heads. The backward under O1
+(equally remembered, not captured) rounds g = (p - onehot) * g0 / B to fp16 once, rounds the result of each mm / bmm backward to fp16
+once and adds the terms of one leaf in fp32; csrc/mdr_inbatch_grad.hip lists the points, tests/mhop_loss_ref.py states them in fp64.
 """
 import ctypes
 
@@ -37,15 +43,23 @@ SIGNATURES = {
                                     _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
+# include/mdr_inbatch_loss.h (which include/mdr_inbatch.h ends by including): a table of its own, so that each header is pinned against its own list
+LOSS_SIGNATURES = {
+    "mdr_inbatch_loss_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int64, _c.c_int]),
+    "mdr_inbatch_loss_forward": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int64, _c.c_int, _c.c_int, _c.c_int] + [_c.c_void_p] * 5 + [_c.c_size_t, _c.c_void_p]),
+    "mdr_inbatch_loss_backward": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int64, _c.c_int, _c.c_int, _c.c_int] + [_c.c_void_p] * 8 + [_c.c_size_t, _c.c_void_p]),
+}
+LOSS_EXPORTED_SYMBOLS = tuple(LOSS_SIGNATURES)
 _bound = False
 
 
 def lib():
-    """libmdrhip.so with the signatures of include/mdr_inbatch.h bound (AttributeError if the library lacks one: no fallback)."""
+    """libmdrhip.so with the signatures of include/mdr_inbatch.h and include/mdr_inbatch_loss.h bound (AttributeError if the library lacks one: no
+    fallback)."""
     global _bound
     L = _lib.lib()
     if not _bound:
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **LOSS_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _bound = True
@@ -101,6 +115,99 @@ def mhop_loss_value(outputs, fp16=False):
     t = torch.arange(B)
     ce = torch.nn.CrossEntropyLoss(ignore_index=-1)
     return float((ce(s1.float(), t) + ce(s2.float(), t + B)).item())
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class _InbatchLoss(torch.autograd.Function):
+    """loss = mean(lse1 - t1) + mean(lse2 - t2) over 2B + 2 + K columns. forward: mdr_inbatch_loss_forward; backward:
+    mdr_inbatch_loss_backward with the upstream gradient passed as a device scalar (no synchronisation in either)."""
+
+    @staticmethod
+    def forward(ctx, q, q_sp, c1, c2, neg_1, neg_2, queue, mode):
+        dev = q.device
+        f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+        q, q_sp = f(q), f(q_sp)
+        B, d = q.shape
+        cc = torch.cat([f(c1), f(c2)], dim=0)
+        neg = torch.stack([f(neg_1), f(neg_2)], dim=1).contiguous()
+        if q_sp.shape != (B, d) or cc.shape != (2 * B, d) or neg.shape != (B, 2, d):
+            raise ValueError(f"q {tuple(q.shape)}, q_sp {tuple(q_sp.shape)}, [c1; c2] {tuple(cc.shape)} and the negatives {tuple(neg.shape)} do not fit one batch")
+        if queue is not None:
+            if not (queue.is_cuda and queue.device == dev and queue.dim() == 2 and queue.shape[1] == d):
+                raise ValueError(f"the queue must be a [K, {d}] tensor on {dev}, got {tuple(queue.shape)} on {queue.device}")
+            queue = f(queue) if queue.shape[0] else None  # a view of the caller's tensor when it is fp32 and contiguous: never written
+        K = int(queue.shape[0]) if queue is not None else 0
+        L = lib()
+        out = torch.empty(4, B, dtype=torch.float32, device=dev)  # tscore1, tscore2, lse1, lse2
+        with torch.cuda.device(dev):
+            need = int(L.mdr_inbatch_loss_workspace_bytes(B, d, K, int(mode)))
+            ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+            _lib.check(L.mdr_inbatch_loss_forward(_ptr(q), _ptr(q_sp), _ptr(cc), _ptr(neg), _ptr(queue), K, B, d, int(mode), _ptr(out[0]), _ptr(out[1]),
+                                                  _ptr(out[2]), _ptr(out[3]), _ptr(ws), need, _lib.current_stream_ptr(dev)))
+        ctx.save_for_backward(q, q_sp, cc, neg, out)
+        ctx.queue, ctx.mode, ctx.ws, ctx.need = queue, int(mode), ws, need
+        return (out[2] - out[0]).mean() + (out[3] - out[1]).mean()
+
+    @staticmethod
+    def backward(ctx, grad):
+        q, q_sp, cc, neg, out = ctx.saved_tensors
+        dev = q.device
+        B, d = q.shape
+        queue = ctx.queue
+        K = int(queue.shape[0]) if queue is not None else 0
+        g0 = grad.detach().to(device=dev, dtype=torch.float32).reshape(1).contiguous()
+        dq, dqsp, dctx, dneg = torch.empty_like(q), torch.empty_like(q_sp), torch.empty_like(cc), torch.empty_like(neg)
+        with torch.cuda.device(dev):
+            _lib.check(lib().mdr_inbatch_loss_backward(_ptr(q), _ptr(q_sp), _ptr(cc), _ptr(neg), _ptr(queue), K, B, d, ctx.mode, _ptr(out[2]), _ptr(out[3]),
+                                                       _ptr(g0), _ptr(dq), _ptr(dqsp), _ptr(dctx), _ptr(dneg), _ptr(ctx.ws), ctx.need,
+                                                       _lib.current_stream_ptr(dev)))
+        return dq, dqsp, dctx[:B], dctx[B:], dneg[:, 0], dneg[:, 1], None, None
+
+
+def mhop_loss_outputs(outputs, args, queue=None):
+    """The loss of criterions.py:114-151 as a 0-d fp32 device tensor that differentiates with respect to q, q_sp1, c1, c2, neg_1, neg_2 (whichever
+    carry grad). args.fp16 selects apex O1's numerics; `queue` is a [K, d] device tensor of further negatives (never written, no gradient) or None."""
+    q = outputs["q"]
+    if not (torch.is_tensor(q) and q.is_cuda):
+        raise RuntimeError("the in-batch loss runs on a HIP device only (there is no CPU fallback)")
+    return _InbatchLoss.apply(q, outputs["q_sp1"], outputs["c1"], outputs["c2"], outputs["neg_1"], outputs["neg_2"], queue, _mode(args))
+
+
+def mhop_loss(model, batch, args):
+    """criterions.py:114-151. With args.momentum the K rows of model.queue are scored as further negatives and the batch's [c1; c2] is enqueued
+    afterwards, in the reference's order (score first, enqueue after). `model` is the callable that returns the six matrices; the queue is looked
+    up on model.module first, as the reference does for its DataParallel-wrapped model, then on model."""
+    outputs = model(batch)
+    if not getattr(args, "momentum", False):
+        return mhop_loss_outputs(outputs, args)
+    bank = getattr(model, "module", model)
+    # the backward reads the queue again, after the enqueue below has overwritten rows of it: score a copy, as the reference does (.clone().detach())
+    loss = mhop_loss_outputs(outputs, args, queue=bank.queue.clone())
+    bank.dequeue_and_enqueue(torch.cat([outputs["c1"], outputs["c2"]], dim=0).detach())
+    return loss
+
+
+class MemoryBank:
+    """queue / queue_ptr / dequeue_and_enqueue of RobertaMomentumRetriever (mhop_retriever.py:64-68, :85-106): k earlier passage embeddings,
+    initialised with torch.randn. A batch that would pass the end is TRUNCATED, not wrapped, and the pointer moves by what was written, modulo k."""
+
+    def __init__(self, k, d, device="cpu"):
+        self.k = int(k)
+        self.queue = torch.randn(self.k, int(d)).to(device)
+        self.queue_ptr = torch.zeros(1, dtype=torch.long)
+
+    @torch.no_grad()
+    def dequeue_and_enqueue(self, embeddings):
+        n = embeddings.shape[0]
+        ptr = int(self.queue_ptr)
+        if ptr + n > self.k:
+            n = self.k - ptr
+            embeddings = embeddings[:n]
+        self.queue[ptr:ptr + n, :] = embeddings.to(self.queue.dtype)
+        self.queue_ptr[0] = (ptr + n) % self.k
 
 
 def host_scores(outputs, fp16=False):
