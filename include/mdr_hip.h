@@ -240,6 +240,41 @@ int mdr_test_gemm_f16(const void* A_dev, const void* W_dev, const float* bias_de
  * ---------------------------------------------------------------------------------------------- */
 int mdr_test_attention(const void* qkv_dev, const int* cu_dev, const int* order_dev, int B, int L, int hidden, int heads,
                        int kernel, void* ctx_dev, int device, void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * Test hooks: the remaining kernels of the transformer trunk, each in isolation (HF RobertaModel / ElectraModel embeddings and
+ * LayerNorm, and the un-padded packing in front of them). Each validates on the host (MDR_E_INVALID + mdr_last_error(): NULL
+ * pointers, B < 1, L outside 1..512, H not a multiple of 64 or above 1024), goes through the launcher the forwards use,
+ * enqueues on `stream` and does not synchronise. Values that live on the device (lengths, token indices, ids) cannot be
+ * checked: the caller guarantees that tok_src indexes ids / types and that tok_pid >= 0.
+ *
+ * mdr_test_pack: the packing prologue of a forward. ids, mask: i64 [B, L] (any non-zero mask value is a token; set positions
+ * need not be a prefix). Leaves exactly what a forward leaves in its workspace: lens i32 [B]; cu i32 [B + 1] (exclusive scan,
+ * cu[B] = total); total i32 [1]; order i32 [B], the sequences longest first, ties by lower index -- written only for
+ * B <= 1024 (above, no kernel walks by it and the buffer is left untouched); tok_src i32 [total] = b * L + p of every
+ * token, row-major; tok_pid i32 [total] = its RoBERTa position id (HF create_position_ids_from_input_ids over the whole
+ * row from ids != pad_id). tok_src / tok_pid need room for B * L entries; entries from `total` on are not written.
+ * ---------------------------------------------------------------------------------------------- */
+int mdr_test_pack(const int64_t* ids_dev, const int64_t* mask_dev, int B, int L, int pad_id, int* lens_dev, int* cu_dev, int* total_dev,
+                  int* order_dev, int* tok_src_dev, int* tok_pid_dev, int device, void* stream);
+/* Embedding gather + LayerNorm over packed tokens t < min(*total_dev, launched waves): out = LN(word[clamp(ids[tok_src[t]])] +
+ * pos[p] + type[ty]) * g + b, f16 [cap, H] and (out32 non-NULL) f32 [cap, H]. `cap` sizes the launch (a forward passes B * L).
+ * flavour 0 (the retriever): p = min(tok_pid[t], max_pos - 1), ty = 0 (types, L, type_vocab unused).
+ * flavour 1 (the reader): p = tok_src[t] % L (L <= max_pos), ty = clamp(types[tok_src[t]], 0, type_vocab - 1), or 0 when
+ * types is NULL (tok_pid unused). word f32 [vocab, H], pos f32 [max_pos, H], type f32 [1 or type_vocab, H], g, b f32 [H]. */
+int mdr_test_embed_ln(int flavour, const int64_t* ids_dev, const int64_t* types_dev, const int* tok_src_dev, const int* tok_pid_dev,
+                      const int* total_dev, int cap, int L, const float* word_dev, const float* pos_dev, const float* type_dev, int type_vocab,
+                      const float* g_dev, const float* b_dev, int H, int vocab, int max_pos, float eps, void* out16_dev, float* out32_dev,
+                      int device, void* stream);
+/* LayerNorm over rows t < (rows_dev ? min(*rows_dev, rows_cap) : rows_cap): y = LN(in + residual) * g + b with in f32 or
+ * (in_f16 = 1) f16 [rows_cap, H]; residual: none, res16 (f16) or res32 (f32), at most one; y goes to out16 (f16) and / or
+ * out32 (f32), at least one; out32 may be res32 (in place, as the layers' residual stream is refreshed). */
+int mdr_test_layernorm(const void* in_dev, int in_f16, const void* res16_dev, const float* res32_dev, int rows_cap, const int* rows_dev, int H,
+                       const float* g_dev, const float* b_dev, float eps, void* out16_dev, float* out32_dev, int device, void* stream);
+/* mode 0, the CLS gather: out16[b] = src16[cu[b]] (f16 rows of H) and, when src32 / out32 are given (both or neither),
+ * out32[b] = src32[cu[b]], b < B (n unused). mode 1, the weight conversion at load: out16[i] = (f16) src32[i], i < n,
+ * round to nearest even (src16, cu, B, H, out32 unused). */
+int mdr_test_row_copy(int mode, const void* src16_dev, const float* src32_dev, const int* cu_dev, int B, int H, int64_t n, void* out16_dev,
+                      float* out32_dev, int device, void* stream);
 /* Measurement hooks that exist only in VARIANT builds of these sources (never in the product library) are declared in
  * include/mdr_hip_measure.h. No environment variable changes what any entry point above computes: MDR_GEMM_CFG, MDR_MIPS_WIDE,
  * MDR_MIPS_I8, MDR_MIPS_I8_CB (the int8 tier's query split forced on / off) and MDR_MIPS_EVEN_GROUPS (how the passes of a > 256-query

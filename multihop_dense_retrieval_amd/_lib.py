@@ -68,6 +68,15 @@ _SIGNATURES = {
                                      _c.c_int, _c.c_int, _c.c_void_p]),
     "mdr_test_attention": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
                                       _c.c_int, _c.c_void_p]),
+    "mdr_test_pack": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                 _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    "mdr_test_embed_ln": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p,
+                                     _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_float,
+                                     _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    "mdr_test_layernorm": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                      _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    "mdr_test_row_copy": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_void_p, _c.c_void_p,
+                                     _c.c_int, _c.c_void_p]),
 }
 # include/mdr_hip_measure.h: exported by measurement builds only (MDR_LIB_PATH=...); bound when present, absent from the product library
 _MEASURE_SIGNATURES = {

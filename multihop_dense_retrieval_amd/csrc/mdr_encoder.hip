@@ -23,7 +23,8 @@
 //
 // Host side, in this order: the GEMM / attention launchers (here); the transformer trunk shared with the answer reader -- weights and their
 // upload, workspace, packing prologue, layer body (mdr_encoder_trunk.inl); the encoder's own part -- its embedding launch, the CLS-only last
-// layer, the projection head and the test hooks (here); the reader (mdr_reader.inl, mdr_reader_assemble.inl).
+// layer, the projection head and the GEMM / attention test hooks (here); the reader (mdr_reader.inl, mdr_reader_assemble.inl); the test hooks of
+// the packing / embedding / LayerNorm / row kernels (mdr_encoder_test_rows.inl).
 #include <hip/hip_runtime.h>
 #include <map>
 #include <mutex>
@@ -236,6 +237,18 @@ struct mdr_encoder {
     float fill_hint = 0.f;  // expected (tokens / (batch * seq_len)) of the next forwards; 0 = unknown (2/3 is assumed)
 };
 
+namespace {
+
+// the encoder's embedding launch (RoBERTa position ids from tok_pid, one type row): one wave per packed token, cap = batch * seq_len waves launched
+void launch_embed_ln(const long long* ids, const int* tok_src, const int* tok_pid, const int* total, int cap, const float* word, const float* pos,
+                     const float* type0, const float* g, const float* b, int H, int vocab, int max_pos, float eps, _Float16* out16, float* out32,
+                     hipStream_t st) {
+    hipLaunchKernelGGL(embed_ln_kernel, dim3((cap + 3) / 4), dim3(256), 0, st, ids, tok_src, tok_pid, total, word, pos, type0, g, b, H, vocab, max_pos, eps,
+                       out16, out32);
+}
+
+}  // namespace
+
 extern "C" {
 
 int mdr_encoder_create(const mdr_encoder_config* cfg, const mdr_tensor* tensors, int n_tensors, int weights_on_device, int device, void* stream,
@@ -413,9 +426,7 @@ int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* m
         }
     }
 #endif
-    hipLaunchKernelGGL(embed_ln_kernel, dim3((Tcap + 3) / 4), dim3(256), 0, st, ids, (const int*)w.tok_src, (const int*)w.tok_pid, (const int*)w.total,
-                       (const float*)t.word, (const float*)t.pos, (const float*)t.type, (const float*)t.emb_g, (const float*)t.emb_b, H, c.vocab, c.max_pos,
-                       c.ln_eps, w.h16, w.h32);
+    launch_embed_ln(ids, w.tok_src, w.tok_pid, w.total, Tcap, t.word, t.pos, t.type, t.emb_g, t.emb_b, H, c.vocab, c.max_pos, c.ln_eps, w.h16, w.h32, st);
     MDR_HIP_TRY(hipGetLastError());
     const Rows tokens{w.h16, w.h32, w.pre, Tcap, w.total, Test}, cls{w.cls16, w.cls32, w.clspre, B, nullptr, B};
     int rc;
@@ -427,16 +438,15 @@ int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* m
     const Layer& last = t.layers.back();
     rc = launch_qkv(t, last, w, tokens, ncu, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(gather_cls_kernel, dim3((B * H + 255) / 256), dim3(256), 0, st, (const _Float16*)w.h16, (const float*)w.h32, (const int*)w.cu, B, H,
-                       w.cls16, w.cls32);
+    launch_gather_cls(w.h16, w.h32, w.cu, B, H, w.cls16, w.cls32, st);
     hipLaunchKernelGGL(attention_cls_kernel, dim3(c.heads, B), dim3(64), 0, st, (const _Float16*)w.qkv, (const int*)w.cu, H, w.ctx);
     MDR_HIP_TRY(hipGetLastError());
     rc = layer_tail(t, last, w.ctx, w.ffn, cls, ncu, st);
     if (rc) return rc;
     rc = launch_gemm<EPI_BIAS_F32>(w.cls16, H, h->wproj, h->bproj, B, nullptr, H, H, w.clspre, H, nullptr, 0, B, ncu, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(layernorm_kernel<float>, dim3((B + 3) / 4), dim3(256), 0, st, (const float*)w.clspre, (const _Float16*)nullptr, (const float*)nullptr, B,
-                       (const int*)nullptr, H, (const float*)h->lnp_g, (const float*)h->lnp_b, c.ln_eps, (_Float16*)nullptr, out_dev);
+    launch_layernorm((const float*)w.clspre, (const _Float16*)nullptr, (const float*)nullptr, B, (const int*)nullptr, H, h->lnp_g, h->lnp_b, c.ln_eps,
+                     (_Float16*)nullptr, out_dev, st);
     MDR_HIP_TRY(hipGetLastError());
     return MDR_OK;
 }
@@ -446,3 +456,5 @@ int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* m
 // the answer reader (include/mdr_reader.h) shares this translation unit's file-local kernels and launchers
 #include "mdr_reader.inl"
 #include "mdr_reader_assemble.inl"
+// the mdr_test_* hooks of the packing / embedding / LayerNorm / row kernels (behind the reader: its embedding kernel is one of them)
+#include "mdr_encoder_test_rows.inl"

@@ -21,6 +21,33 @@ struct Trunk {
     std::vector<Layer> layers;
 };
 
+// ---- launchers of the packing / LayerNorm / row kernels: a forward and the mdr_test_* hooks of mdr_encoder_test_rows.inl both come through these, so
+// that grid, block and argument order exist once ----
+
+// lengths, cu_seqlens + total (+ the length order: written only where the ring attention kernel walks by it, B <= 1024 -- pack_order() says whether)
+// and token -> (source index, RoBERTa position id)
+inline int* pack_order(int* order, int B) { return MDR_ATTN_SORT && B <= 1024 ? order : nullptr; }
+void launch_pack(const long long* ids, const long long* mask, int B, int L, int pad_id, int* lens, int* cu, int* total, int* order, int* tok_src,
+                 int* tok_pid, hipStream_t st) {
+    hipLaunchKernelGGL(enc_lens_kernel, dim3((B + 3) / 4), dim3(256), 0, st, mask, B, L, lens);
+    hipLaunchKernelGGL(enc_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)lens, B, cu, total, pack_order(order, B));
+    hipLaunchKernelGGL(enc_scatter_kernel, dim3((B + 3) / 4), dim3(256), 0, st, ids, mask, B, L, pad_id, (const int*)cu, tok_src, tok_pid);
+}
+
+template <typename IN_T>
+void launch_layernorm(const IN_T* in, const _Float16* res16, const float* res32, int rows_cap, const int* rows_dev, int H, const float* g, const float* b,
+                      float eps, _Float16* out16, float* out32, hipStream_t st) {
+    hipLaunchKernelGGL(layernorm_kernel<IN_T>, dim3((rows_cap + 3) / 4), dim3(256), 0, st, in, res16, res32, rows_cap, rows_dev, H, g, b, eps, out16, out32);
+}
+
+void launch_gather_cls(const _Float16* h16, const float* h32, const int* cu, int B, int H, _Float16* out16, float* out32, hipStream_t st) {
+    hipLaunchKernelGGL(gather_cls_kernel, dim3((B * H + 255) / 256), dim3(256), 0, st, h16, h32, cu, B, H, out16, out32);
+}
+
+void launch_f32_to_f16(const float* in, _Float16* out, size_t numel, hipStream_t st) {
+    hipLaunchKernelGGL(f32_to_f16_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, st, in, out, (long long)numel);
+}
+
 int device_cu_count(int device) {
     hipDeviceProp_t prop;
     return hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -96,7 +123,7 @@ struct WeightLoader {
     // staging[0, numel) -> fp16 at dst + at (the stream is drained: staging is reused)
     int convert16(size_t numel, _Float16* dst, size_t at = 0) {
         if (rc) return rc;
-        hipLaunchKernelGGL(f32_to_f16_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, st, (const float*)staging, dst + at, (long long)numel);
+        launch_f32_to_f16(staging, dst + at, numel, st);
         if (hip(hipGetLastError(), "fp16 conversion launch")) return rc;
         return hip(hipStreamSynchronize(st), "hipStreamSynchronize");
     }
@@ -196,10 +223,8 @@ int trunk_begin(const Trunk& t, const long long* ids, const long long* mask, int
                 hipStream_t st, Workspace* w) {
     if (!workspace_dev || workspace_bytes < need) return set_error(MDR_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     *w = carve(t.cfg, B, L, (char*)(((uintptr_t)workspace_dev + 255) & ~(uintptr_t)255));
-    if (!(MDR_ATTN_SORT && B <= 1024)) w->order = nullptr;
-    hipLaunchKernelGGL(enc_lens_kernel, dim3((B + 3) / 4), dim3(256), 0, st, mask, B, L, w->lens);
-    hipLaunchKernelGGL(enc_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)w->lens, B, w->cu, w->total, w->order);
-    hipLaunchKernelGGL(enc_scatter_kernel, dim3((B + 3) / 4), dim3(256), 0, st, ids, mask, B, L, t.cfg.pad_id, (const int*)w->cu, w->tok_src, w->tok_pid);
+    w->order = pack_order(w->order, B);
+    launch_pack(ids, mask, B, L, t.cfg.pad_id, w->lens, w->cu, w->total, w->order, w->tok_src, w->tok_pid, st);
     return MDR_OK;
 }
 
@@ -233,12 +258,10 @@ int gemm_to_pre(const mdr_encoder_config& c, const _Float16* x, int K, const _Fl
 void post_ln(const mdr_encoder_config& c, const Rows& r, bool res_in_gemm, const float* g, const float* b, hipStream_t st) {
     const bool r32 = c.residual_fp32 != 0;
     if (c.residual_fp32 == 2)
-        hipLaunchKernelGGL(layernorm_kernel<_Float16>, dim3((r.cap + 3) / 4), dim3(256), 0, st, (const _Float16*)r.pre, (const _Float16*)nullptr,
-                           (const float*)r.h32, r.cap, r.n_dev, c.hidden, g, b, c.ln_eps, r.h16, r.h32);
+        launch_layernorm((const _Float16*)r.pre, (const _Float16*)nullptr, (const float*)r.h32, r.cap, r.n_dev, c.hidden, g, b, c.ln_eps, r.h16, r.h32, st);
     else
-        hipLaunchKernelGGL(layernorm_kernel<float>, dim3((r.cap + 3) / 4), dim3(256), 0, st, (const float*)r.pre,
-                           (const _Float16*)(r32 || res_in_gemm ? nullptr : r.h16), (const float*)(r32 ? r.h32 : nullptr), r.cap, r.n_dev, c.hidden, g, b,
-                           c.ln_eps, r.h16, (float*)(r32 ? r.h32 : nullptr));
+        launch_layernorm((const float*)r.pre, (const _Float16*)(r32 || res_in_gemm ? nullptr : r.h16), (const float*)(r32 ? r.h32 : nullptr), r.cap, r.n_dev,
+                         c.hidden, g, b, c.ln_eps, r.h16, (float*)(r32 ? r.h32 : nullptr), st);
 }
 
 // out-projection of ctx -> LayerNorm -> FFN1 (GELU) into ffn -> FFN2 -> LayerNorm, over r

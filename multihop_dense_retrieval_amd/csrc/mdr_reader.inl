@@ -239,6 +239,14 @@ int launch_span_search(const unsigned short* start, const unsigned short* end, i
     return MDR_OK;
 }
 
+// the reader's embedding launch (position = source index % L, a type table; types may be null): one wave per packed token, cap = batch * seq_len
+void launch_reader_embed_ln(const long long* ids, const long long* types, const int* tok_src, const int* total, int cap, int L, const float* word,
+                            const float* pos, const float* type_emb, int type_vocab, const float* g, const float* b, int H, int vocab, float eps,
+                            _Float16* out16, float* out32, hipStream_t st) {
+    hipLaunchKernelGGL(reader_embed_ln_kernel, dim3((cap + 3) / 4), dim3(256), 0, st, ids, types, tok_src, total, L, word, pos, type_emb, type_vocab, g, b, H,
+                       vocab, eps, out16, out32);
+}
+
 }  // namespace
 
 extern "C" {
@@ -341,9 +349,8 @@ int mdr_reader_forward(mdr_reader* h, const int64_t* ids_dev, const int64_t* mas
     const ReaderWs rw = reader_carve(w, batch, seq_len);
     const int B = batch, L = seq_len, H = c.hidden, ncu = t.num_cus;
     const int Tcap = B * L;
-    hipLaunchKernelGGL(reader_embed_ln_kernel, dim3((Tcap + 3) / 4), dim3(256), 0, st, ids, (const long long*)token_type_ids_dev, (const int*)w.tok_src,
-                       (const int*)w.total, L, (const float*)t.word, (const float*)t.pos, (const float*)t.type, rc_.type_vocab, (const float*)t.emb_g,
-                       (const float*)t.emb_b, H, c.vocab, c.ln_eps, w.h16, w.h32);
+    launch_reader_embed_ln(ids, (const long long*)token_type_ids_dev, w.tok_src, w.total, Tcap, L, t.word, t.pos, t.type, rc_.type_vocab, t.emb_g, t.emb_b, H,
+                           c.vocab, c.ln_eps, w.h16, w.h32, st);
     MDR_HIP_TRY(hipGetLastError());
     // every layer over all packed tokens: the heads need every token's final hidden state
     const Rows tokens{w.h16, w.h32, w.pre, Tcap, w.total, Tcap - Tcap / 3};
@@ -360,8 +367,7 @@ int mdr_reader_forward(mdr_reader* h, const int64_t* ids_dev, const int64_t* mas
                            (const long long*)paragraph_mask_dev, B, L, H, (const _Float16*)h->whead, (const float*)h->bhead, start16, end16);
     if (o->rank_score) {
         _Float16* dense16 = (_Float16*)w.clspre;  // pooler dense output [B, H] fp16 (apex O1: the Linear returns fp16)
-        hipLaunchKernelGGL(gather_cls_kernel, dim3((B * H + 255) / 256), dim3(256), 0, st, (const _Float16*)w.h16, (const float*)nullptr, (const int*)w.cu, B,
-                           H, w.cls16, (float*)nullptr);
+        launch_gather_cls(w.h16, (const float*)nullptr, w.cu, B, H, w.cls16, (float*)nullptr, st);
         rc = launch_gemm<EPI_BIAS_F16>(w.cls16, H, h->wpool, h->bpool, B, nullptr, H, H, dense16, H, nullptr, 0, B, ncu, st);
         if (rc) return rc;
         hipLaunchKernelGGL(reader_rank_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const _Float16*)dense16, B, H,

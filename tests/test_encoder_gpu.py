@@ -175,6 +175,39 @@ def test_large_batch_is_sliced_and_consistent(models):
     assert np.abs(full[:8].cpu().numpy() - ref).max() <= TOL["tiny"][0]
 
 
+def test_more_than_1024_rows_in_one_forward(models):
+    """B > 1024 in ONE mdr_encoder_forward call: the second trip of enc_scan_kernel's 1024-wide loop (the carry hand-over) and the walk without a
+    length order. Same rows in slices of 256: bit-identical (the bar test_large_batch_kernels_agree_with_small_batch_path observed)."""
+    m, sd = models["tiny"]
+    B, L = 1100, 20
+    assert B * L <= m.MAX_TOKENS_PER_CALL
+    ids, mask = seeded.make_token_batch(13, "b1100", B, L, seeded.TINY["vocab"], min_len=1)
+    ids_t, mask_t = torch.from_numpy(ids), torch.from_numpy(mask)
+    full = m.encode_q(ids_t, mask_t)
+    sliced = torch.cat([m.encode_q(ids_t[i:i + 256], mask_t[i:i + 256]) for i in range(0, B, 256)])
+    assert torch.equal(full, sliced), (full - sliced).abs().max().item()
+    ref = roberta_oracle.encode(sd, seeded.TINY, ids[:8], mask[:8], np.float64)
+    assert np.abs(full[:8].cpu().numpy() - ref).max() <= TOL["tiny"][0]
+
+
+def test_pad_id_tokens_inside_the_masked_prefix(models):
+    """Rows whose masked-in prefix holds pad_id tokens: their position id is pad_id and they are not counted (HF create_position_ids_from_input_ids
+    works from ids != pad_id, not from the mask) -- the branch no seeded batch reaches (oracle/seeded.make_token_batch draws ids from 3..vocab)."""
+    m, sd = models["tiny"]
+    pad = 1  # RobertaConfig.pad_token_id
+    ids, mask = seeded.make_token_batch(14, "padin", 12, 40, seeded.TINY["vocab"], min_len=6)
+    rng = np.random.RandomState(3)
+    for b in range(len(ids)):
+        n = int(mask[b].sum())
+        ids[b, rng.choice(np.arange(1, n), size=max(1, n // 4), replace=False)] = pad
+    assert ((ids == pad) & (mask != 0)).sum() >= 12
+    out = m.encode_q(torch.from_numpy(ids), torch.from_numpy(mask)).cpu().numpy()
+    ref = roberta_oracle.encode(sd, seeded.TINY, ids, mask, np.float64)
+    err = np.abs(out - ref)
+    print(f"pad ids inside the prefix: max abs err {err.max():.3e} mean {err.mean():.3e}")
+    assert err.max() <= TOL["tiny"][0] and err.mean() <= TOL["tiny"][1]
+
+
 def test_errors(models):
     from multihop_dense_retrieval_amd import retriever
     from multihop_dense_retrieval_amd._lib import MdrError
