@@ -1,0 +1,93 @@
+"""Self-attention on the trunk's packed, ragged rows as a differentiable torch function:
+
+    packed_self_attention(qkv, cu, heads, max_len, cls_only=False) -> ctx
+
+qkv is a CUDA fp16 tensor [T, 3 * hidden] (a token's row is Q | K | V, head h in columns 64 h .. 64 h + 63 of each part), cu an int32
+tensor [B + 1] on the same device; sequence b owns rows cu[b] .. cu[b + 1] - 1 and none is longer than max_len. The forward is the kernel
+the encoder launches for max_len (mdr_test_attention of include/mdr_hip.h with kernel = 0; with cls_only the last layer's kernel 3, whose
+context is [B, hidden], the first query of each sequence): the context bits are the encoder's. The backward is mdr_attention_backward
+(include/mdr_attention_grad.h; csrc/mdr_attention_grad.hip lists its rounding points): no atomics, two runs give the same bits. The
+gradient is returned for qkv only. Both directions are enqueued on the current stream and never synchronise. There is no dropout: the
+reference trains with attention dropout 0.1, which needs a training forward this package does not have.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+
+_c = ctypes
+# include/mdr_attention_grad.h -- bound here, apart from _lib._SIGNATURES (include/mdr_hip.h's table, pinned by its own test)
+SIGNATURES = {
+    "mdr_attention_backward_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "mdr_attention_backward": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                          _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p]),
+}
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
+MODE_ALL, MODE_CLS = 0, 3
+_bound = False
+
+
+def lib():
+    """libmdrhip.so with the signatures of include/mdr_attention_grad.h bound (AttributeError if the library lacks one: no fallback)."""
+    global _bound
+    L = _lib.lib()
+    if not _bound:
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
+        _bound = True
+    return L
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def attention_backward(qkv, dctx, cu, heads, max_len, mode=MODE_ALL, out=None):
+    """mdr_attention_backward on device tensors: dqkv, fp16 [T, 3 * hidden] (`out` if given: the call writes every row of the batch's
+    sequences and nothing else). dctx is fp16 [T, hidden], or [B, hidden] in mode 3. Enqueued on the current stream."""
+    dev = qkv.device
+    B, hidden = cu.numel() - 1, qkv.shape[1] // 3
+    dqkv = torch.empty_like(qkv) if out is None else out
+    L = lib()
+    with torch.cuda.device(dev):
+        need = int(L.mdr_attention_backward_workspace_bytes(B, int(max_len), int(heads), int(mode)))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+        _lib.check(L.mdr_attention_backward(_ptr(qkv), _ptr(dctx), _ptr(cu), B, int(max_len), hidden, int(heads), int(mode), _ptr(dqkv), _ptr(ws), need,
+                                            dev.index if dev.index is not None else torch.cuda.current_device(), _lib.current_stream_ptr(dev)))
+    return dqkv
+
+
+class _PackedSelfAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, cu, heads, max_len, cls_only):
+        dev = qkv.device
+        B, hidden = cu.numel() - 1, qkv.shape[1] // 3
+        q = qkv.detach()
+        out = torch.empty((B if cls_only else q.shape[0], hidden), dtype=torch.float16, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mdr_test_attention(_ptr(q), _ptr(cu), None, B, int(max_len), hidden, int(heads), 3 if cls_only else 0, _ptr(out),
+                                                     dev.index if dev.index is not None else torch.cuda.current_device(), _lib.current_stream_ptr(dev)))
+        ctx.save_for_backward(q, cu)
+        ctx.heads, ctx.max_len, ctx.mode = int(heads), int(max_len), MODE_CLS if cls_only else MODE_ALL
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        q, cu = ctx.saved_tensors
+        g = grad.detach().to(dtype=torch.float16).contiguous()
+        return attention_backward(q, g, cu, ctx.heads, ctx.max_len, ctx.mode), None, None, None, None
+
+
+def packed_self_attention(qkv, cu, heads, max_len, cls_only=False):
+    """softmax(Q K^T / 8) V per (sequence, head) on packed rows, differentiable with respect to qkv (module docstring)."""
+    if not (torch.is_tensor(qkv) and qkv.is_cuda):
+        raise RuntimeError("packed self-attention runs on a HIP device only (there is no CPU fallback)")
+    if qkv.dtype != torch.float16 or qkv.dim() != 2 or not qkv.is_contiguous() or qkv.shape[1] != 3 * 64 * int(heads):
+        raise ValueError(f"qkv must be a contiguous fp16 [T, {3 * 64 * int(heads)}] tensor, got {qkv.dtype} {tuple(qkv.shape)}")
+    if not (torch.is_tensor(cu) and cu.device == qkv.device and cu.dtype == torch.int32 and cu.dim() == 1 and cu.numel() >= 2 and cu.is_contiguous()):
+        raise ValueError("cu must be a contiguous int32 [B + 1] tensor on qkv's device")
+    if not 1 <= int(max_len) <= 512:
+        raise ValueError(f"max_len = {max_len} outside 1..512")
+    return _PackedSelfAttention.apply(qkv, cu, int(heads), int(max_len), bool(cls_only))
