@@ -458,3 +458,5 @@ int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* m
 #include "mdr_reader_assemble.inl"
 // the mdr_test_* hooks of the packing / embedding / LayerNorm / row kernels (behind the reader: its embedding kernel is one of them)
 #include "mdr_encoder_test_rows.inl"
+// the backward of the trunk's Linears (include/mdr_linear_grad.h): its dX goes through launch_gemm
+#include "mdr_linear_grad.inl"

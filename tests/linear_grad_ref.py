@@ -1,0 +1,236 @@
+"""Host restatement of ONE Linear backward call (mdr_linear_backward, include/mdr_linear_grad.h): the four formulas in fp64, a derived
+elementwise error bound, an fp32 / fp16 emulation of the kernels' dataflow (with switchable mutations) and makers for the inputs. numpy
+(erfc in float64 through torch's CPU kernel); nothing here is measured from a kernel. Test helper (tests/test_linear_grad_host.py,
+tests/test_linear_grad_gpu.py).
+
+Layout: x float16 [M, K], w float16 [N, K], dy float16 [M, N], pre None or the float16 pre-activation u [M, N], m = valid rows (None: M).
+
+Formulas, on the first m rows (the others do not exist for the call):
+    dZ = dY o gelu'(u),  gelu'(u) = Phi(u) + u phi(u)   (pre None: dZ = dY)
+    dX = dZ W            dW = dZ^T X (+ old)            db = column sums of dZ (+ old)
+
+The bound
+---------
+Derived from the rounding points listed at the top of csrc/mdr_linear_grad.inl. u = 2^-24 (fp32 half ulp), X = 2^-23 (one fp32 ulp: the
+rounding of an MFMA's internal adds is not documented as nearest-even, and the ISA documents v_exp_f32 as accurate to 1 ulp), h = 2^-11
+(fp16 half ulp of a normal), z = 2^-25 (half the fp16 subnormal spacing). Each line bounds the absolute error of the device's value.
+
+1. Operands are fp16: exact. A product of two fp16 is exact in fp32.
+2. gelu'. Phi: the forward's tail polynomial, stated max |Phi error| 2.1e-7 (csrc/mdr_encoder_gemm.inl), + u for the fp32 add of 1/2.
+   phi(u) = exp2(u^2 c) k, c = -log2(e) / 2, k = 1 / sqrt(2 pi): u^2 is exact (22 bits), the product with c errs by 2 u |arg| (the
+   constant and the rounding), which the exponential turns into a relative ln 2 * 2 u |arg|; the exponential itself X; the constant k, its
+   product and the product with u: 3 u; a flushed subnormal result: 2^-126. The final add: u |gelu'|. So
+       dg = 2.1e-7 + u + |u phi(u)| (X + 3 u + 2 ln 2 u |arg|) + |u| 2^-126 + u |gelu'(u)|.
+   dZ = fp16(fp32(dy) * g): the fp32 product u |dy g|, then the fp16 rounding r(y) = max(h y, z) of a value of magnitude at most y:
+       e = |dy| dg + u |dy gelu'|,   EdZ = e + r(|dZ| + e).          (pre None: EdZ = 0)
+3. dX_mk: N products added in fp32 in some order, at most one ulp lost per addition, then the exact + 0.0f and the fp16 rounding:
+       e = sum_n EdZ_mn |w_nk| + N X sum_n (|dZ_mn| + EdZ_mn) |w_nk|,   EdX = e + r(|dX| + e).
+4. dW_nk: the rows of a chunk in slabs of 64 (zero rows behind m are added too), the S chunks in order, then the old value: at most
+   mpad + S + 1 additions, mpad = m rounded up to whole slabs, no fp16 term:
+       EdW = sum_m EdZ_mn |x_mk| + (mpad + S + 1) X (sum_m (|dZ_mn| + EdZ_mn) |x_mk| + |old_nk|).
+5. db_n: fewer additions than that in any order the kernel uses:
+       Edb = sum_m EdZ_mn + (mpad + S + 1) X (sum_m (|dZ_mn| + EdZ_mn) + |old_n|).
+
+Every constant is a format's, a count, the ISA's 1 ulp or the forward's stated 2.1e-7 (which the host test re-checks for the derivative over
+every finite fp16 u); no term was read off a device. The emulation below is a second implementation of the dataflow: the host test shows
+that it stays inside the bound and that each mutation leaves it.
+"""
+import numpy as np
+import torch
+
+U32 = 2.0 ** -24
+X1ULP = 2.0 ** -23
+H16 = 2.0 ** -11
+Z16 = 2.0 ** -25
+PHI_ERR = 2.1e-7
+SLAB = 64        # token rows per staged slab of the weight-gradient kernel
+TILE = 128       # edge of a dW tile
+TARGET_WGS = 512
+F16_MAX = 65504.0
+C_EXP = -0.72134752044448170   # -log2(e) / 2
+K_PHI = 0.3989422804014327     # 1 / sqrt(2 pi)
+
+MUTATIONS = ("extra_row", "missing_row", "drop_last_chunk", "dw_transposed", "dx_from_w", "db_missing_last_slab", "accumulate_ignored",
+             "db_without_dz", "gelu_no_uphi")
+
+# The shapes of the GPU tests (the host test runs the emulation over the same ones).
+SMALL_NK = [(64, 64), (192, 64), (64, 192), (128, 128), (256, 384)]
+MODEL_NK = [(768, 768), (2304, 768), (3072, 768), (768, 3072)]
+M_SWEEP = [1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 300]   # 63 .. 65 and 127 .. 129: -1, 0, +1 around one and two chunks of 64 rows
+
+
+def chunks(M, N, K):
+    """(S, rows_per_chunk) of mdr_linear_backward_chunks: a function of (M, N, K) alone (the host test compares it with the library's)."""
+    tiles = ((N + TILE - 1) // TILE) * ((K + TILE - 1) // TILE)
+    slabs = (M + SLAB - 1) // SLAB
+    want = max(1, min((TARGET_WGS + tiles - 1) // tiles, slabs))
+    per = (slabs + want - 1) // want
+    return (slabs + per - 1) // per, per * SLAB
+
+
+def _r16(y):
+    return np.maximum(H16 * y, Z16)
+
+
+def gelu_grad64(u):
+    """Phi(u) + u phi(u) in float64."""
+    u = np.asarray(u, np.float64)
+    Phi = 0.5 * torch.special.erfc(torch.from_numpy(-u / np.sqrt(2.0))).numpy()
+    return Phi + u * np.exp(-0.5 * u * u) / np.sqrt(2.0 * np.pi)
+
+
+def gelu_grad_bound(u):
+    """dg of the docstring: the absolute error of the device's fp32 gelu'(u)."""
+    u = np.abs(np.asarray(u, np.float64))
+    arg = u * u * -C_EXP
+    uphi = u * np.exp(-0.5 * u * u) / np.sqrt(2.0 * np.pi)
+    return PHI_ERR + U32 + uphi * (X1ULP + 3 * U32 + 2 * np.log(2.0) * U32 * arg) + u * 2.0 ** -126 + U32 * np.abs(gelu_grad64(u))
+
+
+def _fma32(a, b, c):  # one rounding: the fp64 product of two fp32 is exact
+    return (np.asarray(a, np.float32).astype(np.float64) * np.float64(np.float32(b)) + np.float64(np.float32(c))).astype(np.float32)
+
+
+def _fma32v(a, b, c):
+    return (a.astype(np.float64) * b.astype(np.float64) + np.float64(np.float32(c))).astype(np.float32)
+
+
+def _exp2_32(t):
+    with np.errstate(under="ignore", over="ignore"):
+        return np.exp2(t.astype(np.float32)).astype(np.float32)
+
+
+def gelu_grad32(u, mutation=None):
+    """The kernel's fp32 gelu'(u): the forward's tail polynomial at min(|u|, 16) for Phi, one exp2 for phi."""
+    f32 = np.float32
+    u = np.asarray(u, np.float16).astype(f32)
+    a = np.minimum(np.abs(u), f32(16))
+    p = _fma32(a, -1.982813420e-05, 6.620948925e-04)
+    for c in (-7.759194708e-03, 5.296392132e-02, 4.590664427e-01, 1.151119066e+00):
+        p = _fma32v(p, a, c)
+    e = _fma32v(p, a, 1.0)
+    s = np.copysign(f32(0.5) - _exp2_32(-e), u)
+    dens = _exp2_32(u * u * f32(C_EXP)) * f32(K_PHI)
+    if mutation == "gelu_no_uphi":
+        return s + f32(0.5)
+    return (s + f32(0.5)) + u * dens
+
+
+def reference_and_bound(x, w, dy, pre=None, m=None, old_dw=None, old_db=None):
+    """{"dz", "dx", "dw", "db"} -> (reference, bound), float64. dz and dx have m rows. Asserts that nothing leaves the fp16 range (the bound
+    has no term for an overflow)."""
+    M, K = x.shape
+    N = w.shape[0]
+    m = M if m is None else int(m)
+    S, _ = chunks(M, N, K)
+    X, W, DY = x[:m].astype(np.float64), w.astype(np.float64), dy[:m].astype(np.float64)
+    if pre is None:
+        dz, edz = DY, np.zeros_like(DY)
+    else:
+        u = pre[:m].astype(np.float64)
+        g = gelu_grad64(u)
+        dz = DY * g
+        e = np.abs(DY) * gelu_grad_bound(u) + U32 * np.abs(dz)
+        edz = e + _r16(np.abs(dz) + e)
+        assert m == 0 or float((np.abs(dz) + edz).max()) < F16_MAX, "dZ leaves the fp16 range: scale dy down"
+    adz = np.abs(dz) + edz
+    dx = dz @ W
+    e = edz @ np.abs(W) + N * X1ULP * (adz @ np.abs(W))
+    edx = e + _r16(np.abs(dx) + e)
+    assert m == 0 or float((np.abs(dx) + edx).max()) < F16_MAX, "dX leaves the fp16 range: scale w down"
+    cnt = ((m + SLAB - 1) // SLAB * SLAB + S + 1) * X1ULP
+    odw = np.zeros((N, K)) if old_dw is None else old_dw.astype(np.float64)
+    odb = np.zeros(N) if old_db is None else old_db.astype(np.float64)
+    dw = dz.T @ X + odw
+    edw = edz.T @ np.abs(X) + cnt * (adz.T @ np.abs(X) + np.abs(odw))
+    db = dz.sum(axis=0) + odb
+    edb = edz.sum(axis=0) + cnt * (adz.sum(axis=0) + np.abs(odb))
+    return {"dz": (dz, edz), "dx": (dx, edx), "dw": (dw, edw), "db": (db, edb)}
+
+
+def emulate(x, w, dy, pre=None, m=None, old_dw=None, old_db=None, mutation=None):
+    """The kernels' dataflow in numpy: dZ = fp16(fp32 dy * fp32 gelu'), dX = fp16 of an fp32 product over the valid rows, dW and db as fp32 sums
+    slab by slab inside a chunk (rows at or behind m are zero-filled), the chunks added in order, the old value last. Returns (dx float16 [m, K],
+    dw float32 [N, K], db float32 [N]).
+
+    mutation (None: the correct dataflow) switches ONE defect on, for the tests that prove the bound notices it:
+    extra_row: row m (which exists in the buffers) taken as valid; missing_row: row m - 1 zero-filled; drop_last_chunk: the last chunk's partial
+    never added (S > 1); dw_transposed: dW written as [K, N] (N = K); dx_from_w: dX = dZ W^T (N = K); db_missing_last_slab: db without the last
+    slab of rows; accumulate_ignored: the old value not added; db_without_dz: db from dY instead of dZ; gelu_no_uphi: gelu' = Phi alone."""
+    assert mutation is None or mutation in MUTATIONS
+    f32 = np.float32
+    M, K = x.shape
+    N = w.shape[0]
+    m = M if m is None else int(m)
+    S, rpc = chunks(M, N, K)
+    me = m
+    if mutation == "extra_row":
+        me = min(m + 1, M)
+    elif mutation == "missing_row":
+        me = max(m - 1, 0)
+    dyf = dy.astype(f32)
+    if pre is None:
+        dz = dyf
+    else:
+        with np.errstate(over="ignore", invalid="ignore"):
+            dz = (dyf * gelu_grad32(pre, mutation)).astype(np.float16).astype(f32)
+    xf, wf = x.astype(f32), w.astype(f32)
+    with np.errstate(over="ignore"):
+        dx = (dz[:me] @ (wf.T if mutation == "dx_from_w" else wf)).astype(np.float16)[:m]
+    if dx.shape[0] < m:
+        dx = np.concatenate([dx, np.zeros((m - dx.shape[0], K), np.float16)])
+    dbsrc = dyf if mutation == "db_without_dz" else dz
+    dw, db = np.zeros((N, K), f32), np.zeros(N, f32)
+    last_slab = (max(me, 1) - 1) // SLAB * SLAB
+    for c in range(S):
+        if mutation == "drop_last_chunk" and S > 1 and c == S - 1:
+            continue
+        pw, pb = np.zeros((N, K), f32), np.zeros(N, f32)
+        for r0 in range(c * rpc, min((c + 1) * rpc, me), SLAB):
+            r1 = min(r0 + SLAB, me)
+            pw = pw + dz[r0:r1].T @ xf[r0:r1]
+            if not (mutation == "db_missing_last_slab" and r0 == last_slab):
+                pb = pb + dbsrc[r0:r1].sum(axis=0, dtype=f32)
+        dw, db = dw + pw, db + pb
+    if mutation == "dw_transposed":
+        dw = np.ascontiguousarray(dw.T)
+    if mutation != "accumulate_ignored":
+        if old_dw is not None:
+            dw = dw + old_dw.astype(f32)
+        if old_db is not None:
+            db = db + old_db.astype(f32)
+    return dx, dw, db
+
+
+def worst_ratio(got, ref, bnd):
+    """(largest |got - ref| / bound, its index); an element with bound 0 must be exact, a non-finite value where the reference is finite is
+    infinitely far."""
+    got, ref, bnd = (np.atleast_2d(np.asarray(a, np.float64)) for a in (got, ref, bnd))
+    if got.size == 0:
+        return 0.0, (0, 0)
+    err = np.abs(got - ref)
+    err = np.where(np.isfinite(err), err, np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(err == 0, 0.0, err / bnd)
+    i = np.unravel_index(np.argmax(ratio), ratio.shape)
+    return float(ratio[i]), (int(i[0]), int(i[1]))
+
+
+# ---- makers --------------------------------------------------------------------------------------------------------------------------------
+def grid(shape, seed, scale=1.0):
+    """float16: seeded multiples of 1/8 in [-2, 2], times `scale` (a power of two)."""
+    rng = np.random.default_rng([seed, *shape, 7])
+    return (rng.integers(-16, 17, size=shape) / 8.0 * scale).astype(np.float16)
+
+
+def realistic(M, N, K, seed, dy_scale=1.0):
+    """(x, w, dy) float16: N(0, 1) activations, weights x 0.02, N(0, 1) gradients times dy_scale (a loss scale)."""
+    rng = np.random.default_rng([seed, M, N, K, 3])
+    x = rng.standard_normal((M, K)).astype(np.float16)
+    w = (0.02 * rng.standard_normal((N, K))).astype(np.float16)
+    dy = (dy_scale * rng.standard_normal((M, N))).astype(np.float16)
+    return x, w, dy
+
+
+def bias(N, seed):
+    return (0.1 * np.random.default_rng([seed, N, 5]).standard_normal(N)).astype(np.float32)

@@ -1,0 +1,356 @@
+"""GPU (-m gpu): the Linear backward in isolation (mdr_linear_backward, include/mdr_linear_grad.h) against the fp64 statement of
+tests/linear_grad_ref.py, and packed_linear (multihop_dense_retrieval_amd/linear.py) on top of it. EVERY element of dX, dW and db is
+compared; nothing is averaged.
+
+Two bars. On the grid (x, w, dy multiples of 1/8 of magnitude at most 2: every product is a multiple of 1/64 of magnitude at most 4, and
+any fp32 sum of M <= 65536 of them is exact in any order because 4 * 64 * M <= 2^24) dW and db must EQUAL the integer result bit for bit and
+dX its correctly rounded fp16: every index map, the zero-fill, the chunk seams and the reduction without a tolerance. On realistic rows the
+bar is linear_grad_ref's bound, derived from the formats and the rounding points listed in csrc/mdr_linear_grad.inl and shown on the host
+(tests/test_linear_grad_host.py) to hold a second implementation of the dataflow and to throw out each defect. No tolerance here was read
+off a device.
+
+Every output starts as a finite sentinel: dx with 64 guard rows on both sides, dw and db with 64 guard elements on both sides, which must
+keep their bits in every call of this file. Shapes: a whole 64 x 64 quarter tile, a 64-wide remainder on either side of a 128 x 128 tile,
+one whole tile, several tiles with a remainder, each at M = 1 .. 300 around the MFMA k-step, the slab and one and two chunks of 64 rows;
+the four Linears of roberta-base at M = 300.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import linear_grad_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = 777.0  # finite, fp16-exact, far from every expected output
+GUARD = 64        # rows of dx / elements of dw and db in front of and behind the call's own, which must keep their bits
+OK, E_INVALID, E_WORKSPACE = 0, -1, -4
+ALL_NK = [pytest.param(N, K, id=f"N{N}-K{K}") for N, K in ref.SMALL_NK + ref.MODEL_NK]
+
+
+def ms_for(N, K):
+    return ref.M_SWEEP if (N, K) in ref.SMALL_NK else [300]
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def dev(a):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def raw_call(x, w, dy, pre, M, m_dev, N, K, dx, dw, db, accumulate, ws, ws_bytes):
+    from multihop_dense_retrieval_amd import _lib, linear
+    return linear.lib().mdr_linear_backward(_p(x), _p(w), _p(dy), _p(pre), M, _p(m_dev), N, K, _p(dx), _p(dw), _p(db), accumulate, _p(ws), ws_bytes,
+                                            0, _lib.current_stream_ptr())
+
+
+def run(x, w, dy, pre=None, m=None, outs="xwb", old_dw=None, old_db=None, accumulate=False, ws_extra=0):
+    """One call on numpy inputs. Outputs start as SENTINEL (dw / db: the old values if given) inside guards; returns {"dx": float16 [M, K] (rows
+    at or behind m still SENTINEL), "dw": float32 [N, K], "db": float32 [N]} for the outputs asked for, after asserting MDR_OK and that the
+    guards kept their bits."""
+    from multihop_dense_retrieval_amd import _lib, linear
+    M, K = x.shape
+    N = w.shape[0]
+    bx = torch.full((GUARD + M + GUARD, K), SENTINEL, dtype=torch.float16, device="cuda")
+    bw = torch.full((GUARD + N * K + GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
+    bb = torch.full((GUARD + N + GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
+    if old_dw is not None:
+        bw[GUARD:GUARD + N * K] = dev(old_dw.astype(np.float32)).reshape(-1)
+    if old_db is not None:
+        bb[GUARD:GUARD + N] = dev(old_db.astype(np.float32))
+    want = (1 if "x" in outs else 0) | (2 if "w" in outs else 0) | (4 if "b" in outs else 0) | (8 if pre is not None else 0)
+    need = int(linear.lib().mdr_linear_backward_workspace_bytes(M, N, K, want))
+    ws = torch.empty(max(need + ws_extra, 16), dtype=torch.uint8, device="cuda")
+    m_dev = None if m is None else torch.tensor([m], dtype=torch.int32, device="cuda")
+    _lib.check(raw_call(dev(x), dev(w), dev(dy), dev(pre), M, m_dev, N, K, bx[GUARD:GUARD + M] if "x" in outs else None,
+                        bw[GUARD:GUARD + N * K] if "w" in outs else None, bb[GUARD:GUARD + N] if "b" in outs else None, 1 if accumulate else 0, ws,
+                        need + ws_extra))
+    torch.cuda.synchronize()
+    gx, gw, gb = bx.cpu().numpy(), bw.cpu().numpy(), bb.cpu().numpy()
+    s16, s32 = np.float16(SENTINEL), np.float32(SENTINEL)
+    assert (gx[:GUARD] == s16).all() and (gx[GUARD + M:] == s16).all(), "dx rows outside the call were written"
+    assert (gw[:GUARD] == s32).all() and (gw[GUARD + N * K:] == s32).all(), "dw elements outside the call were written"
+    assert (gb[:GUARD] == s32).all() and (gb[GUARD + N:] == s32).all(), "db elements outside the call were written"
+    mm = M if m is None else m
+    if "x" in outs:
+        assert (gx[GUARD + mm:GUARD + M] == s16).all(), "dx rows at or behind the valid count were written"
+    else:
+        assert (gx == s16).all(), "dx written though not asked for"
+    if "w" not in outs and old_dw is None:
+        assert (gw == s32).all(), "dw written though not asked for"
+    if "b" not in outs and old_db is None:
+        assert (gb == s32).all(), "db written though not asked for"
+    return {"dx": gx[GUARD:GUARD + M], "dw": gw[GUARD:GUARD + N * K].reshape(N, K), "db": gb[GUARD:GUARD + N]}
+
+
+def forward_hook(x, w, b, epilogue, m=None):
+    """mdr_test_gemm_f16 with kernel = 0 on numpy inputs -> float16 [M, N] (rows at or behind m: zero)."""
+    from multihop_dense_retrieval_amd import _lib
+    M, K = x.shape
+    N = w.shape[0]
+    out = torch.zeros((M, N), dtype=torch.float16, device="cuda")
+    m_dev = None if m is None else torch.tensor([m], dtype=torch.int32, device="cuda")
+    tx, tw, tb = dev(x), dev(w), dev(b)  # (held until the synchronise below)
+    _lib.check(_lib.lib().mdr_test_gemm_f16(_p(tx), _p(tw), _p(tb), M, _p(m_dev), N, K, _p(out), epilogue, 0, 0, _lib.current_stream_ptr()))
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+def exact_grid(x, w, dz, m=None, old_dw=None, old_db=None):
+    """The integer result of a grid call: (dx float16 correctly rounded [m, K], dw float32, db float32), asserting that everything is exact in
+    fp32 and that no dX leaves the fp16 range. dz may be dy / 2 (multiples of 1/16 times a power of two)."""
+    m = x.shape[0] if m is None else m
+    X, W, DZ = x[:m].astype(np.float64), w.astype(np.float64), dz[:m].astype(np.float64)
+    for a in (X, W, DZ):
+        assert (a * 1024 == np.round(a * 1024)).all()
+    dx, dw, db = DZ @ W, DZ.T @ X, DZ.sum(axis=0)
+    odw, odb = (np.zeros(1) if o is None else o.astype(np.float64) for o in (old_dw, old_db))
+    if old_dw is not None:
+        dw = dw + odw
+    if old_db is not None:
+        db = db + odb
+    # exact in fp32 in any order: every partial sum is a whole number of quanta (the largest power of two all terms are multiples of) and
+    # stays at or below 2^24 of them
+    for total, quantum in ((np.abs(DZ) @ np.abs(W), _quantum(DZ) * _quantum(W)),
+                           (np.abs(DZ).T @ np.abs(X) + np.abs(odw), min(_quantum(DZ) * _quantum(X), _quantum(odw))),
+                           (np.abs(DZ).sum(axis=0) + np.abs(odb), min(_quantum(DZ), _quantum(odb)))):
+        assert total.size == 0 or total.max() / quantum <= 2.0 ** 24, "the grid no longer guarantees exact fp32 sums"
+    assert dx.size == 0 or np.abs(dx).max() < ref.F16_MAX, "an exact dX leaves the fp16 range: shrink w"
+    assert (dw.astype(np.float32) == dw).all() and (db.astype(np.float32) == db).all()
+    return dx.astype(np.float16), dw.astype(np.float32), db.astype(np.float32)
+
+
+def _quantum(a):
+    """the largest power of two every element of `a` is a multiple of (1.0 for an all-zero or empty array)"""
+    nz = np.abs(a[a != 0])
+    if nz.size == 0:
+        return 1.0
+    e = 0
+    while not (nz * 2.0 ** -e == np.round(nz * 2.0 ** -e)).all():
+        e -= 1
+    return 2.0 ** e
+
+
+def assert_equal(got, want, m, label):
+    dx, dw, db = want
+    for name, g, wnt in (("dx", got["dx"][:m], dx), ("dw", got["dw"], dw), ("db", got["db"], db)):
+        bad = np.argwhere(~(g == wnt))
+        if bad.size:
+            i = tuple(bad[0])
+            pytest.fail(f"{label}: {name} differs at {len(bad)} of {g.size} elements; first at {i}: got {float(g[i])!r}, exact {float(wnt[i])!r}")
+        assert g.dtype == wnt.dtype
+
+
+def grid_inputs(M, N, K, seed, loss_scale=False):
+    x, w, dy = ref.grid((M, K), seed), ref.grid((N, K), seed + 1), ref.grid((M, N), seed + 2)
+    if loss_scale:  # dy x 2^8 as under a loss scale; w shrunk by 2^-4 so that no exact dX leaves the fp16 range (asserted in exact_grid)
+        w, dy = (w.astype(np.float32) / 16).astype(np.float16), (dy.astype(np.float32) * 256).astype(np.float16)
+    return x, w, dy
+
+
+def test_some_tested_shape_is_split():
+    from multihop_dense_retrieval_amd import linear
+    split = [(M, N, K) + linear.backward_chunks(M, N, K) for N, K in ref.SMALL_NK + ref.MODEL_NK for M in ms_for(N, K)]
+    assert any(S > 1 for *_, S, _ in split)
+    # M_SWEEP's 63 .. 65 and 127 .. 129 are -1, 0, +1 around one and two chunks wherever the shape is split
+    for M, N, K, S, rpc in split:
+        assert (S, rpc) == ref.chunks(M, N, K)
+        if S > 1 and (N, K) in ref.SMALL_NK:
+            assert rpc == 64, (M, N, K, S, rpc)
+
+
+@pytest.mark.parametrize("loss_scale", [False, True], ids=["unit", "x256"])
+@pytest.mark.parametrize("N,K", ALL_NK)
+def test_exact_grid_equality(N, K, loss_scale):
+    for M in ms_for(N, K):
+        x, w, dy = grid_inputs(M, N, K, 3, loss_scale)
+        assert_equal(run(x, w, dy), exact_grid(x, w, dy), M, f"M={M} N={N} K={K}")
+
+
+@pytest.mark.parametrize("N,K", ALL_NK)
+def test_accumulate_on_the_grid(N, K):
+    for M in ms_for(N, K):
+        x, w, dy = grid_inputs(M, N, K, 5)
+        old_dw, old_db = ref.grid((N, K), 8).astype(np.float32) * 4, ref.grid((N,), 9).astype(np.float32) * 4
+        got = run(x, w, dy, old_dw=old_dw, old_db=old_db, accumulate=True)
+        assert_equal(got, exact_grid(x, w, dy, None, old_dw, old_db), M, f"accumulate M={M} N={N} K={K}")
+        got = run(x, w, dy, old_dw=old_dw, old_db=old_db, accumulate=False)
+        assert_equal(got, exact_grid(x, w, dy), M, f"overwrite M={M} N={N} K={K}")
+
+
+def check_bound(got, rb, m, label):
+    fails = []
+    for name in ("dx", "dw", "db"):
+        g = got[name][:m] if name == "dx" else got[name]
+        r, bnd = rb[name]
+        worst, at = ref.worst_ratio(g, r, bnd)
+        print(f"RATIO {label} {name} worst |err| / bound = {worst:.4f}")
+        if worst > 1.0:
+            g2, r2, b2 = (np.atleast_2d(a) for a in (g, r, bnd))
+            fails.append(f"{name} outside the bound: worst {worst:.3f} at row {at[0]}, column {at[1]}: got {float(g2[at])!r}, reference {r2[at]!r}, bound {b2[at]:.3e}")
+    if fails:
+        pytest.fail(f"{label}: " + "; ".join(fails))
+
+
+@pytest.mark.parametrize("scale", [1.0, 256.0], ids=["unit", "x256"])
+@pytest.mark.parametrize("N,K", ALL_NK)
+def test_realistic_rows_within_the_derived_bound(N, K, scale):
+    """Identity and GELU path (u from the forward hook with epilogue 0), and the GELU path with one invalid row of NaN behind m = M - 1."""
+    for M in ms_for(N, K):
+        x, w, dy = ref.realistic(M, N, K, 11, scale)
+        check_bound(run(x, w, dy), ref.reference_and_bound(x, w, dy), M, f"identity M={M} N={N} K={K} scale={scale}")
+        u = forward_hook(x, w, ref.bias(N, 11), 0)
+        check_bound(run(x, w, dy, u), ref.reference_and_bound(x, w, dy, u), M, f"gelu M={M} N={N} K={K} scale={scale}")
+    if M > 1:
+        xb, dyb, ub = x.copy(), dy.copy(), u.copy()
+        xb[M - 1], dyb[M - 1], ub[M - 1] = np.nan, np.inf, np.nan
+        got = run(xb, w, dyb, ub, m=M - 1)
+        check_bound(got, ref.reference_and_bound(x, w, dy, u, M - 1), M - 1, f"gelu m=M-1 M={M} N={N} K={K} scale={scale}")
+
+
+@pytest.mark.parametrize("N,K", ALL_NK)
+def test_gelu_at_zero_is_exactly_one_half(N, K):
+    """u = 0 everywhere: gelu'(0) = 1/2 exactly (the polynomial gives 2^-1 at 0), dZ = dY / 2, and all three outputs are bit-exact on the grid."""
+    for M in ms_for(N, K):
+        x, w, dy = grid_inputs(M, N, K, 13)
+        dz = (dy.astype(np.float32) / 2).astype(np.float16)
+        assert_equal(run(x, w, dy, np.zeros((M, N), np.float16)), exact_grid(x, w, dz), M, f"gelu0 M={M} N={N} K={K}")
+
+
+@pytest.mark.parametrize("N,K", [pytest.param(128, 128, id="N128-K128"), pytest.param(256, 384, id="N256-K384"), pytest.param(768, 768, id="N768-K768")])
+@pytest.mark.parametrize("gelu0", [False, True], ids=["identity", "gelu0"])
+def test_rows_behind_m_dev_do_not_exist(N, K, gelu0):
+    """m in {0, 1, M - 1, M}, rows at or behind m of x, dy and pre NaN and Inf: outputs finite and equal, bit for bit, to the call on the
+    first m rows alone (on the grid every sum is exact, so the different split of the shorter call does not matter); dx rows at or behind m
+    keep the sentinel (run() asserts it); m = 0 gives zeros, or the old value with accumulate."""
+    M = 200
+    x, w, dy = grid_inputs(M, N, K, 17)
+    pre = np.zeros((M, N), np.float16) if gelu0 else None
+    old_dw, old_db = ref.grid((N, K), 18).astype(np.float32), ref.grid((N,), 19).astype(np.float32)
+    for m in (0, 1, M - 1, M):
+        xb, dyb = x.copy(), dy.copy()
+        xb[m:], dyb[m:] = np.nan, np.inf
+        xb[m + 1::2], dyb[m + 1::2] = -np.inf, np.nan
+        pb = None
+        if gelu0:
+            pb = pre.copy()
+            pb[m:] = np.nan
+            pb[m + 1::2] = np.inf
+        got = run(xb, w, dyb, pb, m=m)
+        assert all(np.isfinite(got[k]).all() for k in ("dw", "db")) and np.isfinite(got["dx"][:m]).all()
+        if m == 0:
+            assert not got["dw"].any() and not got["db"].any()
+            acc = run(xb, w, dyb, pb, m=0, old_dw=old_dw, old_db=old_db, accumulate=True)
+            assert np.array_equal(acc["dw"], old_dw) and np.array_equal(acc["db"], old_db)
+        else:
+            alone = run(x[:m], w, dy[:m], None if pre is None else pre[:m])
+            for k in ("dw", "db"):
+                assert np.array_equal(got[k], alone[k]), (m, k)
+            assert np.array_equal(got["dx"][:m], alone["dx"]), (m, "dx")
+            dz = (dy.astype(np.float32) / 2).astype(np.float16) if gelu0 else dy
+            assert_equal(got, exact_grid(x, w, dz, m), m, f"m={m} M={M} N={N} K={K}")
+
+
+def test_nan_in_a_valid_row_reaches_only_what_it_touches():
+    M, N, K = 150, 192, 128
+    x, w, dy = grid_inputs(M, N, K, 23)
+    clean = run(x, w, dy)
+    xb = x.copy()
+    xb[70, 5] = np.nan  # dW[:, 5] only
+    got = run(xb, w, dy)
+    assert np.isnan(got["dw"][:, 5]).all()
+    keep = np.ones(K, bool)
+    keep[5] = False
+    assert np.array_equal(got["dw"][:, keep], clean["dw"][:, keep]) and np.array_equal(got["db"], clean["db"]) and np.array_equal(got["dx"], clean["dx"])
+    dyb = dy.copy()
+    dyb[70, 9] = np.nan  # dX[70, :], dW[9, :], db[9]
+    got = run(x, w, dyb)
+    assert np.isnan(got["dx"][70]).all() and np.isnan(got["dw"][9]).all() and np.isnan(got["db"][9])
+    rows, cols = np.arange(M) != 70, np.arange(N) != 9
+    assert np.array_equal(got["dx"][rows], clean["dx"][rows]) and np.array_equal(got["dw"][cols], clean["dw"][cols])
+    assert np.array_equal(got["db"][cols], clean["db"][cols])
+
+
+@pytest.mark.parametrize("N,K", [pytest.param(256, 384, id="N256-K384"), pytest.param(768, 768, id="N768-K768")])
+def test_two_runs_and_a_larger_workspace_give_the_same_bits(N, K):
+    M = 300
+    x, w, dy = ref.realistic(M, N, K, 29)
+    u = forward_hook(x, w, ref.bias(N, 29), 0)
+    for pre in (None, u):
+        a, b, c = run(x, w, dy, pre), run(x, w, dy, pre), run(x, w, dy, pre, ws_extra=4096 + 16)
+        for k in ("dx", "dw", "db"):
+            assert np.array_equal(a[k].view(np.uint16 if k == "dx" else np.uint32), b[k].view(np.uint16 if k == "dx" else np.uint32)), k
+            assert np.array_equal(a[k].view(np.uint16 if k == "dx" else np.uint32), c[k].view(np.uint16 if k == "dx" else np.uint32)), k
+
+
+def test_single_outputs_match_the_full_call():
+    """each output alone (the other pointers NULL) gives the bits of the call that computes all three"""
+    M, N, K = 129, 192, 64
+    x, w, dy = ref.realistic(M, N, K, 31)
+    full = run(x, w, dy)
+    for outs, k in (("x", "dx"), ("w", "dw"), ("b", "db")):
+        assert np.array_equal(run(x, w, dy, outs=outs)[k], full[k]), k
+
+
+def test_host_validation_writes_nothing():
+    from multihop_dense_retrieval_amd import _lib, linear
+    lib = linear.lib()
+    M, N, K = 70, 128, 64
+    x, w, dy = (dev(a) for a in grid_inputs(M, N, K, 37))
+    pre = torch.zeros((M, N), dtype=torch.float16, device="cuda")
+    dx = torch.full((M, K), SENTINEL, dtype=torch.float16, device="cuda")
+    dw = torch.full((N, K), SENTINEL, dtype=torch.float32, device="cuda")
+    db = torch.full((N,), SENTINEL, dtype=torch.float32, device="cuda")
+    need = int(lib.mdr_linear_backward_workspace_bytes(M, N, K, 15))
+    ws = torch.full((need,), 0x5A, dtype=torch.uint8, device="cuda")
+    cases = [
+        ("NULL x", E_INVALID, dict(x=None)), ("NULL w", E_INVALID, dict(w=None)), ("NULL dy", E_INVALID, dict(dy=None)),
+        ("no outputs", E_INVALID, dict(dx=None, dw=None, db=None)), ("M = 0", E_INVALID, dict(M=0)), ("M < 0", E_INVALID, dict(M=-3)),
+        ("N = 0", E_INVALID, dict(N=0)), ("N = 96", E_INVALID, dict(N=96)), ("K = 0", E_INVALID, dict(K=0)), ("K = 100", E_INVALID, dict(K=100)),
+        ("N < 0", E_INVALID, dict(N=-64)), ("short workspace", E_WORKSPACE, dict(ws_bytes=need - 1)), ("NULL workspace", E_WORKSPACE, dict(ws=None)),
+    ]
+    for label, code, change in cases:
+        a = dict(x=x, w=w, dy=dy, pre=pre, M=M, m_dev=None, N=N, K=K, dx=dx, dw=dw, db=db, accumulate=0, ws=ws, ws_bytes=need)
+        a.update(change)
+        rc = raw_call(**a)
+        assert rc == code, (label, rc)
+        assert lib.mdr_last_error(), label
+    torch.cuda.synchronize()
+    assert (dx == SENTINEL).all() and (dw == SENTINEL).all() and (db == SENTINEL).all() and (ws == 0x5A).all(), "a rejected call wrote something"
+    with pytest.raises(ValueError, match=r"\(70, 128\)|\[70, 128\]"):
+        linear.linear_backward(x, w, dy[:, :64].contiguous())
+    with pytest.raises(ValueError):
+        linear.packed_linear(x, w.float()[:, :32].contiguous(), torch.zeros(N, device="cuda"))
+    with pytest.raises(ValueError):
+        linear.packed_linear(x, w, torch.zeros(N, device="cuda"))  # the weight must be the fp32 master
+
+
+@pytest.mark.parametrize("rows", [False, True], ids=["all-rows", "rows"])
+@pytest.mark.parametrize("gelu", [False, True], ids=["identity", "gelu"])
+def test_packed_linear(gelu, rows):
+    from multihop_dense_retrieval_amd import linear
+    M, N, K = 150, 256, 384
+    m = M - 3 if rows else None
+    x, w16, g = ref.realistic(M, N, K, 41)
+    b = ref.bias(N, 41)
+    w32 = w16.astype(np.float32) * np.float32(1 + 2.0 ** -13)  # an fp32 master that is NOT fp16-exact and rounds to w16 (under a quarter of an fp16 ulp away)
+    assert np.array_equal(w32.astype(np.float16), w16)
+    tx = dev(x).requires_grad_(True)
+    tw, tb = dev(w32).requires_grad_(True), dev(b).requires_grad_(True)
+    tr = None if m is None else torch.tensor([m], dtype=torch.int32, device="cuda")
+    y = linear.packed_linear(tx, tw, tb, gelu=gelu, rows=tr)
+    assert y.dtype == torch.float16 and tuple(y.shape) == (M, N)
+    assert np.array_equal(y.detach().cpu().numpy().view(np.uint16), forward_hook(x, w16, b, 1 if gelu else 0, m).view(np.uint16)), "forward bits differ from the encoder's GEMM"
+    (y.float() * dev(g).float()).sum().backward()
+    torch.cuda.synchronize()
+    assert tx.grad.dtype == torch.float16 and tw.grad.dtype == torch.float32 and tb.grad.dtype == torch.float32
+    assert tuple(tx.grad.shape) == (M, K) and tuple(tw.grad.shape) == (N, K) and tuple(tb.grad.shape) == (N,)
+    mm = M if m is None else m
+    u = forward_hook(x, w16, b, 0, m) if gelu else None
+    got = {"dx": tx.grad.cpu().numpy(), "dw": tw.grad.cpu().numpy(), "db": tb.grad.cpu().numpy()}
+    assert not got["dx"][mm:].any()
+    check_bound(got, ref.reference_and_bound(x, w16, g, u, m), mm, f"packed_linear gelu={gelu} rows={rows}")

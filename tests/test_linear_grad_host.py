@@ -1,0 +1,148 @@
+"""CPU: the fp64 statement of the Linear backward (tests/linear_grad_ref.py) against torch.autograd in float64, the fp32 gelu' formula over
+every finite fp16 pre-activation, the emulation of the kernels' dataflow against the derived bound, each mutation against the same bound,
+and the header / binding / split contract of include/mdr_linear_grad.h. No device and no kernel runs here."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import linear_grad_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUTPUTS = ("dx", "dw", "db")
+
+
+def _pre(x, w, b):
+    """the fp16 pre-activation of the forward, on the host: fp16(x w^T + b) from an fp32 product"""
+    return (x.astype(np.float32) @ w.astype(np.float32).T + b).astype(np.float16)
+
+
+def _ratios(got, rb):
+    return {k: ref.worst_ratio(g, *rb[k]) for k, g in zip(OUTPUTS, got)}
+
+
+@pytest.mark.parametrize("gelu", [False, True])
+def test_fp64_statement_agrees_with_torch_autograd(gelu):
+    """Both sides are fp64 and differ only in summation order: |a - b| <= 1e-10 max|b| per output."""
+    M, N, K = 37, 128, 64
+    x, w, dy = ref.realistic(M, N, K, 1)
+    w = (w.astype(np.float32) * 20).astype(np.float16)  # pre-activations of order 1, where gelu' is not flat
+    b = ref.bias(N, 1)
+    pre = _pre(x, w, b)
+    tx, tw = (torch.from_numpy(a.astype(np.float64)).requires_grad_(True) for a in (x, w))
+    tb = torch.zeros(N, dtype=torch.float64, requires_grad=True)
+    if gelu:
+        # the statement takes the pre-activation as given: feed autograd the same u by making the Linear reproduce it exactly
+        tu = torch.from_numpy(pre.astype(np.float64)).requires_grad_(True)
+        y = torch.nn.functional.gelu(tu)
+        (dz,) = torch.autograd.grad(y, tu, torch.from_numpy(dy.astype(np.float64)))
+        want_dz = dz.numpy()
+    else:
+        want_dz = dy.astype(np.float64)
+    lin = torch.nn.functional.linear(tx, tw, tb)
+    want = [g.numpy() for g in torch.autograd.grad(lin, (tx, tw, tb), torch.from_numpy(want_dz))]
+    rb = ref.reference_and_bound(x, w, dy, pre if gelu else None)
+    assert np.abs(rb["dz"][0] - want_dz).max() <= 1e-10 * np.abs(want_dz).max()
+    for k, wnt in zip(OUTPUTS, want):
+        assert np.abs(rb[k][0] - wnt).max() <= 1e-10 * np.abs(wnt).max(), (k, np.abs(rb[k][0] - wnt).max())
+    if gelu:  # and end to end through F.gelu(F.linear) with an exactly representable pre-activation: b = 0, u = x w^T in fp64
+        tx2, tw2 = (torch.from_numpy(a.astype(np.float64)).requires_grad_(True) for a in (x, w))
+        y2 = torch.nn.functional.gelu(torch.nn.functional.linear(tx2, tw2))
+        want2 = torch.autograd.grad(y2, (tx2, tw2), torch.from_numpy(dy.astype(np.float64)))
+        u64 = x.astype(np.float64) @ w.astype(np.float64).T
+        dz2 = dy.astype(np.float64) * ref.gelu_grad64(u64)
+        assert np.abs(dz2 @ w.astype(np.float64) - want2[0].numpy()).max() <= 1e-10 * np.abs(want2[0].numpy()).max()
+        assert np.abs(dz2.T @ x.astype(np.float64) - want2[1].numpy()).max() <= 1e-10 * np.abs(want2[1].numpy()).max()
+
+
+def test_gelu_grad_formula_over_every_finite_fp16():
+    """The fp32 formula of the kernel (Phi from the forward's tail polynomial, phi from one exp2) against fp64 over ALL finite fp16 u: inside the
+    dZ term of the bound. This pins the forward's 2.1e-7 claim for the derivative, and the clamp of the polynomial's argument."""
+    u = np.arange(65536, dtype=np.uint32).astype(np.uint16).view(np.float16)
+    u = u[np.isfinite(u)]
+    assert u.size == 63488
+    got = ref.gelu_grad32(u).astype(np.float64)
+    want = ref.gelu_grad64(u.astype(np.float64))
+    err, bnd = np.abs(got - want), ref.gelu_grad_bound(u.astype(np.float64))
+    i = int(np.argmax(err / bnd))
+    print(f"RATIO gelu' worst |err| / bound = {err[i] / bnd[i]:.4f} at u = {float(u[i])} (|err| {err[i]:.3e}, largest |err| {err.max():.3e})")
+    assert np.isfinite(got).all()
+    assert (err <= bnd).all(), (float(u[i]), got[i], want[i], bnd[i])
+    assert ref.gelu_grad32(np.zeros(1, np.float16))[0] == np.float32(0.5)  # the structural case of the GPU tests: exactly 1/2 at 0
+    wrong = np.abs(ref.gelu_grad32(u, "gelu_no_uphi").astype(np.float64) - want)
+    assert (wrong > bnd).any()
+
+
+@pytest.mark.parametrize("N,K", ref.SMALL_NK + ref.MODEL_NK)
+def test_emulation_stays_inside_the_bound(N, K):
+    """A second implementation of the listed dataflow, on every shape the GPU tests use, identity and GELU, unit and loss scale."""
+    for M in (ref.M_SWEEP if (N, K) in ref.SMALL_NK else [300]):
+        for scale in (1.0, 256.0):
+            x, w, dy = ref.realistic(M, N, K, 11, scale)
+            pre = _pre(x, w, ref.bias(N, 11))
+            old_dw, old_db = ref.realistic(N, 64, K, 12)[0].astype(np.float32), ref.bias(N, 12)
+            for p, m, odw, odb in ((None, None, None, None), (pre, None, None, None), (pre, max(M - 1, 0), old_dw, old_db)):
+                rb = ref.reference_and_bound(x, w, dy, p, m, odw, odb)
+                for k, (worst, at) in _ratios(ref.emulate(x, w, dy, p, m, odw, odb), rb).items():
+                    assert worst <= 1.0, (M, N, K, scale, k, worst, at)
+
+
+@pytest.mark.parametrize("mutation", ref.MUTATIONS)
+def test_each_mutation_leaves_the_bound(mutation):
+    """The bound is worth something: every row-count, chunk, index, accumulate and gelu' defect is thrown out."""
+    M, N, K = 200, 128, 128
+    assert ref.chunks(M, N, K)[0] > 1
+    x, w, dy = ref.realistic(M, N, K, 21)
+    w = (w.astype(np.float32) * 20).astype(np.float16)
+    pre = _pre(x, w, ref.bias(N, 21))
+    old_dw, old_db = ref.realistic(N, 64, K, 22)[0].astype(np.float32), ref.bias(N, 22)
+    m = M - 1
+    rb = ref.reference_and_bound(x, w, dy, pre, m, old_dw, old_db)
+    assert max(v[0] for v in _ratios(ref.emulate(x, w, dy, pre, m, old_dw, old_db), rb).values()) <= 1.0
+    r = _ratios(ref.emulate(x, w, dy, pre, m, old_dw, old_db, mutation), rb)
+    print(f"mutation {mutation}: worst |err| / bound " + ", ".join(f"{k} {v[0]:.3g}" for k, v in r.items()))
+    assert max(v[0] for v in r.values()) > 1.0, mutation
+
+
+def test_header_binding_and_library_agree():
+    """include/mdr_linear_grad.h declares exactly what linear.SIGNATURES binds and the library exports, apart from include/mdr_hip.h's table."""
+    from multihop_dense_retrieval_amd import _lib, build, linear
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mdr_linear_grad.h")).read(), flags=re.S)
+    declared = sorted(set(re.findall(r"\b(mdr_[a-z0-9_]+)\s*\(", text)))
+    assert sorted(linear.EXPORTED_SYMBOLS) == declared == ["mdr_linear_backward", "mdr_linear_backward_chunks", "mdr_linear_backward_workspace_bytes"]
+    assert not set(linear.EXPORTED_SYMBOLS) & set(_lib.EXPORTED_SYMBOLS)
+    lib = ctypes.CDLL(build.build_lib())
+    for name in declared:
+        assert hasattr(lib, name), f"{name} declared in include/mdr_linear_grad.h but not exported"
+    linear.lib()
+
+
+def test_split_is_a_function_of_the_shape_and_workspace_covers_it():
+    """mdr_linear_backward_chunks equals the helper's restatement, S > 1 on a tested shape, the workspace holds what the header says."""
+    from multihop_dense_retrieval_amd import linear
+    lib = linear.lib()
+    some_split = False
+    for N, K in ref.SMALL_NK + ref.MODEL_NK:
+        for M in ref.M_SWEEP + [8608, 20000]:
+            S, rpc = linear.backward_chunks(M, N, K)
+            assert (S, rpc) == ref.chunks(M, N, K) and S >= 1 and rpc % 64 == 0 and (S - 1) * rpc < M <= S * rpc, (M, N, K, S, rpc)
+            some_split |= S > 1
+            full = lib.mdr_linear_backward_workspace_bytes(M, N, K, 15)
+            assert full >= M * N * 2 + N * K * 2 + K * 4 + (S * N * K * 4 + S * N * 4 if S > 1 else 0)
+            assert lib.mdr_linear_backward_workspace_bytes(M, N, K, 4) == (0 if S == 1 else (S * N * 4 + 255) // 256 * 256)
+    assert some_split
+    for M, N, K in ((0, 64, 64), (-1, 64, 64), (5, 0, 64), (5, 64, 0), (5, 96, 64), (5, 64, 100), (5, -64, 64)):
+        assert lib.mdr_linear_backward_workspace_bytes(M, N, K, 15) == 0
+        assert linear.backward_chunks(M, N, K) == (0, 0)
+
+
+def test_module_fails_loudly_without_a_device():
+    from multihop_dense_retrieval_amd import linear
+    x, w, b = torch.zeros(4, 64, dtype=torch.float16), torch.zeros(64, 64), torch.zeros(64)
+    with pytest.raises(RuntimeError):
+        linear.packed_linear(x, w, b)
+    with pytest.raises(RuntimeError):
+        linear.linear_backward(x, w.half(), torch.zeros(4, 64, dtype=torch.float16))
