@@ -218,12 +218,25 @@ int mdr_upload_host(void* dst_dev, const void* src_host, size_t bytes, int devic
  * Test hook: one encoder GEMM in isolation, out[M, N] = epilogue(A[M, K] . W[N, K]^T + bias[N]) -- the torch.nn.Linear
  * inside HF RobertaModel's layers (the reference reaches them through model.encode_q, mhop_retriever.py:23-26).
  * A, W: f16 device, K-contiguous; bias f32. epilogue: 0 = bias -> f16 out, 1 = bias + erf-GELU -> f16 out,
- * 3 = bias -> f32 out. kernel: 0 = the shape heuristic the encoder uses, 1 = 64x64 tiles, 2 = 128x128, 4 = persistent
- * 256x128, 6 = persistent 256x256 (N % 256 == 0). m_dev (may be NULL) is a device int holding the
- * number of valid rows (<= M), as the packed token count is only known on the device.
+ * 3 = bias -> f32 out. kernel: 0 = the shape heuristic the encoder uses, 1 = 64x64 tiles, 2 = 128x128 (N % 128 == 0), 4 = persistent
+ * 256x128 (N % 128 == 0, N <= 3072), 6 = persistent 256x256 on eight waves (also N % 256 == 0), 7 = persistent 256x256 on four waves
+ * (also K % 128 == 0, K >= 256). A forced kernel whose condition the shape does not meet falls back: 7 and 6 to 4, 4 and 2 to 1; every
+ * kernel returns the same bits. m_dev (may be NULL) is a device int holding the
+ * number of valid rows (<= M), as the packed token count is only known on the device: rows at or behind it are neither read as values nor written.
+ * The erf-GELU evaluates its tail polynomial at min(|u|, 16): exactly u or +-0 from |u| = 16 on.
  * ---------------------------------------------------------------------------------------------- */
 int mdr_test_gemm_f16(const void* A_dev, const void* W_dev, const float* bias_dev, int M, const int* m_dev, int N, int K,
                       void* out_dev, int epilogue, int kernel, int device, void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * Test hook: mdr_test_gemm_f16 with everything the encoder's GEMM launcher takes. epilogue 0..3 as above, and 2 = bias + residual -> f32 out
+ * with the residual res16_dev (f16 [M, N]; required for epilogue 2, NULL otherwise). M_est >= 1 is the HOST's estimate of the valid row count
+ * (the encoder derives it from the fill hint): kernel 0 picks its flavour from M_est, N and K, never from M or *m_dev. Kernels 0, 1, 2, 4, 6, 7 as
+ * above. res_added_host (may be NULL) receives whether the output holds the residual: 1 from the one-tile kernels (1, 2), 0 from the persistent
+ * ones (4, 6, 7), which leave it to the LayerNorm that follows -- so epilogue 2 on a persistent kernel with res_added_host == NULL is MDR_E_STATE,
+ * as in the encoder. Strides are the encoder's: lda = K, ldo = N, ldr = N.
+ * ---------------------------------------------------------------------------------------------- */
+int mdr_test_gemm_ex(const void* A_dev, const void* W_dev, const float* bias_dev, const void* res16_dev, int M, int M_est, const int* m_dev,
+                     int N, int K, void* out_dev, int epilogue, int kernel, int* res_added_host, int device, void* stream);
 /* ------------------------------------------------------------------------------------------------
  * Test hook: one attention call in isolation, ctx = softmax(Q K^T / 8) V per (sequence, head) -- the self-attention inside
  * HF RobertaModel / ElectraModel layers, on packed rows. qkv: f16 device [T, 3*hidden], each token's row is Q | K | V;

@@ -66,6 +66,8 @@ _SIGNATURES = {
     "mdr_encoder_set_fill_hint": (_c.c_int, [_c.c_void_p, _c.c_float]),
     "mdr_test_gemm_f16": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int,
                                      _c.c_int, _c.c_int, _c.c_void_p]),
+    "mdr_test_gemm_ex": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int,
+                                    _c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.c_int, _c.c_void_p]),
     "mdr_test_attention": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
                                       _c.c_int, _c.c_void_p]),
     "mdr_test_pack": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,

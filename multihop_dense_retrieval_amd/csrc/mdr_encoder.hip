@@ -120,6 +120,10 @@ int launch_gemm_quad(const _Float16* A, int lda, const _Float16* W, const float*
 template <int EPI>
 int launch_gemm(const _Float16* A, int lda, const _Float16* W, const float* bias, int M_cap, const int* M_dev, int N, int K, void* out, int ldo,
                 const _Float16* res, int ldr, int M_est, int num_cus, hipStream_t st, bool* res_added = nullptr, int force = -1) {
+    // K: any multiple of 64 from 64 on for the one-tile kernel (2 to 4 stages), gemm_tail_tile, gemm_persist_kernel and gemm_big_kernel -- their prologues
+    // skip the stages past K / 64, their counted waits never allow more batches in flight than were issued (the persistent kernels issue surplus batches so
+    // that the count is constant) and a tile's pending stores are flushed when the next tile has fewer K-steps than pairs of fragments; the four-wave kernel
+    // needs an even K / 64 >= 4 and is routed around below.
     // experiment knob: 1 small, 2 mid, 3 big tiles; 4 persistent 256x128 / 6 persistent 256x256 for the large-M calls (the others keep the heuristic)
     static int env_sel = getenv("MDR_GEMM_CFG") ? atoi(getenv("MDR_GEMM_CFG")) : 0;
     int sel = force >= 0 ? force : env_sel;
@@ -179,7 +183,9 @@ int launch_gemm(const _Float16* A, int lda, const _Float16* W, const float* bias
     // bytes the busiest CU pulls through its L2 path: rounds of blocks x (BM + BN) rows of K; ties go to the small tile
     // (measured at 2.4 k rows: QKV / FFN1 faster on 128x128, out-projection / FFN2 on 64x64)
     const long long c_mid = (mid_blocks + num_cus - 1) / num_cus * 256, c_small = (small_blocks + num_cus - 1) / num_cus * 128;
-    if (sel == 2 || (sel == 0 && N % 128 == 0 && c_mid < c_small))
+    // (a forced 128x128 selection whose N is no multiple of 128 takes the 64x64 kernel, as the forced persistent selections do: the grid of the
+    // 128x128 kernel would leave the last 64 columns unwritten)
+    if (N % 128 == 0 && (sel == 2 || (sel == 0 && c_mid < c_small)))
         return launch_gemm_cfg<EPI, GemmMid>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
     return launch_gemm_cfg<EPI, GemmSmall>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
 }
@@ -293,6 +299,32 @@ int mdr_test_gemm_f16(const void* A_dev, const void* W_dev, const float* bias_de
     if (epilogue == EPI_BIAS_F16) return launch_gemm<EPI_BIAS_F16>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M, ncu, st, nullptr, kernel);
     if (epilogue == EPI_BIAS_GELU_F16) return launch_gemm<EPI_BIAS_GELU_F16>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M, ncu, st, nullptr, kernel);
     return launch_gemm<EPI_BIAS_F32>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M, ncu, st, nullptr, kernel);
+}
+
+int mdr_test_gemm_ex(const void* A_dev, const void* W_dev, const float* bias_dev, const void* res16_dev, int M, int M_est, const int* m_dev, int N, int K,
+                     void* out_dev, int epilogue, int kernel, int* res_added_host, int device, void* stream) {
+    MDR_REQUIRE(A_dev && W_dev && bias_dev && out_dev, "NULL pointer");
+    MDR_REQUIRE(M > 0 && N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0, "bad GEMM shape M=%d N=%d K=%d (N, K multiples of 64)", M, N, K);
+    MDR_REQUIRE(M_est >= 1, "M_est=%d must be at least 1", M_est);
+    MDR_REQUIRE(epilogue >= EPI_BIAS_F16 && epilogue <= EPI_BIAS_F32, "epilogue must be 0, 1, 2 or 3");
+    MDR_REQUIRE((epilogue == EPI_BIAS_RES_F32) == (res16_dev != nullptr), "res16_dev goes with epilogue 2 and with no other");
+    MDR_REQUIRE(kernel == 0 || kernel == 1 || kernel == 2 || kernel == 4 || kernel == 6 || kernel == 7, "kernel must be 0, 1, 2, 4, 6 or 7");
+    DeviceGuard guard(device);
+    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    const int ncu = device_cu_count(device);
+    const _Float16* A = (const _Float16*)A_dev;
+    const _Float16* W = (const _Float16*)W_dev;
+    const _Float16* res = (const _Float16*)res16_dev;
+    hipStream_t st = (hipStream_t)stream;
+    bool added = true;
+    bool* ra = res_added_host ? &added : nullptr;
+    int rc;
+    if (epilogue == EPI_BIAS_F16) rc = launch_gemm<EPI_BIAS_F16>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M_est, ncu, st, ra, kernel);
+    else if (epilogue == EPI_BIAS_GELU_F16) rc = launch_gemm<EPI_BIAS_GELU_F16>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M_est, ncu, st, ra, kernel);
+    else if (epilogue == EPI_BIAS_RES_F32) rc = launch_gemm<EPI_BIAS_RES_F32>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, res, N, M_est, ncu, st, ra, kernel);
+    else rc = launch_gemm<EPI_BIAS_F32>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M_est, ncu, st, ra, kernel);
+    if (res_added_host) *res_added_host = added ? 1 : 0;
+    return rc;
 }
 
 int mdr_test_attention(const void* qkv_dev, const int* cu_dev, const int* order_dev, int B, int L, int hidden, int heads, int kernel, void* ctx_dev,

@@ -11,13 +11,23 @@
 enum { EPI_BIAS_F16 = 0, EPI_BIAS_GELU_F16 = 1, EPI_BIAS_RES_F32 = 2, EPI_BIAS_F32 = 3 };
 constexpr int BK = 64;
 
-// erf-GELU(x) = x Phi(x) with the normal tail written as a power of two: Phi(-a) = 2^-(1 + a P(a)), a = |x|, P a degree-5
-// polynomial fitted to -log2(erfc(a / sqrt 2)) / a on [0, 6], weighted by the tail itself (scripts/fit_gelu_tail.py; it
-// extrapolates monotonically beyond 6). max |Phi error| 2.1e-7, max |GELU error| 6.9e-7 over [-8, 8] evaluated in fp32
+// erf-GELU(x) = x Phi(x) with the normal tail written as a power of two: Phi(-a) = 2^-(1 + a P(a)), a = min(|x|, 16), P a degree-5
+// polynomial fitted to -log2(erfc(a / sqrt 2)) / a on [0, 6], weighted by the tail itself (scripts/fit_gelu_tail.py). Where it holds: on [0, 6] by the
+// fit; up to a = 16 the exponent e = 1 + a P(a) keeps growing (e > 25 from a = 5.6, so t = 2^-e is below half an ulp of 1/2, and t underflows to 0 from
+// a ~ 13.5); beyond that the polynomial is NOT monotonic -- e peaks near a = 19, falls below 1 at a = 23.55 and is negative from a ~ 23.6 (GELU(+-24) came
+// out as 2.2e21, GELU(+-25) as inf) -- so the argument is CLAMPED to 16, where Phi(-16) = 0 in fp32 anyway: |x| <= 16 keeps the bits of the unclamped
+// form, |x| >= 16 gives exactly x or +-0, NaN stays NaN. max |Phi error| 2.1e-7, max |GELU error| 6.9e-7 over [-8, 8] evaluated in fp32
 // (the Abramowitz-Stegun 7.1.26 erf used before: 2.1e-7): 7 packed FMAs per PAIR of values + one v_exp_f32 + 4 simple ops
 // per value, against ~18 ops + v_rcp_f32 + v_exp_f32 per value. Measured (round 2, MDR_GEMM_ABL=5 timeline, FFN1 shape): the
 // epilogue of a 256x256 tile 16.4 k -> 14.0 k cycles, the kernel -3 % wall -- the GELU arithmetic was NOT what makes that
 // epilogue long (with GELU or without the kernel now takes the same time). libm's erff: ~60 divergent instructions per value.
+// Rounding points of gelu_erf2 on an exact fp32 x (tests/gemm_ref.py derives gelu_bound from this list):
+//   1. a = min(|x|, 16): exact.
+//   2. t = Phi(-a): six FMAs and one v_exp_f32 (1 ulp by the ISA); |t - Phi(-a)| <= 2.1e-7 for the correctly rounded chain, + 2^-23 t for the exponential.
+//   3. s = copysign(1/2 - t, x): one rounding of a value of magnitude at most 1/2.
+//   4. x s + x / 2: x / 2 is exact; the product and the sum round once each (a packed multiply and a packed add; contracted into an FMA they would round
+//      once together, inside the same bound). For x < -5 the result is what is left of the cancellation: an absolute error of up to 2^-25 |x|, not a relative one.
+//   5. the epilogue's conversion to fp16: one round-to-nearest-even.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // d = a * b + (c, c): hipcc scalarises a 2-vector FMA whose addend is a literal (VOP3P takes no literal), so the packed
 // form is spelled out with the constant pair in SGPRs
@@ -27,8 +37,10 @@ __device__ inline f32x2 pk_fma_c(f32x2 a, f32x2 b, float c) {
     asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(cc));
     return d;
 }
-__device__ inline f32x2 gelu_erf2(f32x2 x) {
-    const f32x2 a = __builtin_elementwise_abs(x);
+// Phi(x) - 1/2 for a pair of values (shared with the Linear backward's gelu', mdr_linear_grad.inl). The |x| is a source modifier of the minimum: the clamp
+// replaces the abs of the unclamped form.
+__device__ inline f32x2 gelu_phi_m_half2(f32x2 x) {
+    const f32x2 a = __builtin_elementwise_min(__builtin_elementwise_abs(x), (f32x2){16.f, 16.f});
     f32x2 p = pk_fma_c(a, (f32x2){-1.982813420e-05f, -1.982813420e-05f}, 6.620948925e-04f);
     p = pk_fma_c(p, a, -7.759194708e-03f);
     p = pk_fma_c(p, a, 5.296392132e-02f);
@@ -36,9 +48,12 @@ __device__ inline f32x2 gelu_erf2(f32x2 x) {
     p = pk_fma_c(p, a, 1.151119066e+00f);
     const f32x2 e = pk_fma_c(p, a, 1.0f);
     f32x2 t;
-    t[0] = __builtin_amdgcn_exp2f(-e[0]);  // Phi(-|x|); raw v_exp_f32: the argument is <= -1, underflow to 0 is the right answer
+    t[0] = __builtin_amdgcn_exp2f(-e[0]);  // Phi(-a); raw v_exp_f32: the argument is <= -1, underflow to 0 is the right answer
     t[1] = __builtin_amdgcn_exp2f(-e[1]);
-    const f32x2 s = __builtin_elementwise_copysign(0.5f - t, x);  // Phi(x) - 1/2
+    return __builtin_elementwise_copysign(0.5f - t, x);
+}
+__device__ inline f32x2 gelu_erf2(f32x2 x) {
+    const f32x2 s = gelu_phi_m_half2(x);
     return x * s + 0.5f * x;
 }
 __device__ inline f32x4 gelu_erf4(f32x4 x) {
@@ -75,6 +90,7 @@ struct GemmCfg {
     static_assert(BM * 8 % THREADS == 0 && BN * 8 % THREADS == 0, "tile must split evenly over the threads");
 };
 
+// K: any multiple of 64 from 64 on (KT = K / 64 >= 1): the prologue skips the stages past KT and the counted wait never allows more batches in flight than were issued.
 template <int EPI, typename C>
 __global__ void __launch_bounds__(C::THREADS)
 gemm_f16_kernel(const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W, const float* __restrict__ bias, int M_cap,
@@ -220,6 +236,7 @@ __device__ __forceinline__ void gemm_tail_settle(f32x4 (&acc)[4][4]) {
 // One 128x128 tile by WGM x WGN waves (tg = thread 0..64 WGM WGN - 1, wg = wave index) on a ring of SLOTS 32 KiB stages at `ring` (SLOTS - 1 DMA batches in
 // flight: with two slots a K-step is one L2 round trip, 1.3 us measured; four bring it to the LDS / MFMA time). Contains workgroup barriers: every wave of the
 // WORKGROUP must call it the same number of times with the same K. A call without a tile (m0 >= M): loads on the clamped last row, no stores.
+// K: any multiple of 64 from 64 on (the one-tile kernel's prologue and counted waits).
 template <int EPI, int WGM, int WGN, int SLOTS>
 __device__ __forceinline__ void gemm_tail_tile(const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W, const float* __restrict__ bias, int M,
                                                int K, void* __restrict__ out, int ldo, int m0, int n0, char* ring, int tg, int wg, int lane) {
@@ -329,6 +346,9 @@ using GemmP = GemmCfg<256, 128, 4, 2, 3>;   // 3 slots of 48 KiB: two batches in
 #ifndef MDR_GEMM_EPI
 #define MDR_GEMM_EPI 2
 #endif
+// K: any multiple of 64 from 64 on. Every K-step issues exactly one batch (surplus ones past the end of the stream), so the counted wait is exact for any KT; with fewer
+// than eight K-steps a tile the fragments the next tile's steps did not carry out are flushed behind its K-loop (tests/test_gemm_exact_gpu.py runs K = 64 .. 448 with
+// two tiles per workgroup).
 constexpr int kPersistBiasMax = 3072;  // floats of bias kept in LDS behind the ring (12 KiB)
 
 template <int EPI, typename C>
@@ -574,6 +594,8 @@ using GemmB2 = GemmCfg<256, 256, 2, 4, 2>;
 #if MDR_GEMM_ABL == 5
 __device__ unsigned long long g_gemm_stamp[8];
 #endif
+// K: any multiple of 64 from 64 on: the prologue's "K-tile 1" is the next tile's first one when KT = 1 (or a surplus copy of this one when there is no next tile), and
+// barrier A's vmcnt(2) counts pieces, not K-tiles.
 template <int EPI, int ABL = MDR_GEMM_ABL>
 __global__ void __launch_bounds__(512)
 gemm_big_kernel(const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W, const float* __restrict__ bias, int M_cap,

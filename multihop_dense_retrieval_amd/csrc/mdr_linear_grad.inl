@@ -210,20 +210,8 @@ lg_transpose_kernel(const _Float16* __restrict__ w, int N, int K, _Float16* __re
     }
 }
 
-// Phi(u) - 1/2 from the forward's tail polynomial (gelu_erf2: the same coefficients and packed FMAs), for a pair of values
-__device__ inline f32x2 lg_phi_m_half2(f32x2 u) {
-    const f32x2 a = __builtin_elementwise_min(__builtin_elementwise_abs(u), (f32x2){16.f, 16.f});
-    f32x2 p = pk_fma_c(a, (f32x2){-1.982813420e-05f, -1.982813420e-05f}, 6.620948925e-04f);
-    p = pk_fma_c(p, a, -7.759194708e-03f);
-    p = pk_fma_c(p, a, 5.296392132e-02f);
-    p = pk_fma_c(p, a, 4.590664427e-01f);
-    p = pk_fma_c(p, a, 1.151119066e+00f);
-    const f32x2 e = pk_fma_c(p, a, 1.0f);
-    f32x2 t;
-    t[0] = __builtin_amdgcn_exp2f(-e[0]);
-    t[1] = __builtin_amdgcn_exp2f(-e[1]);
-    return __builtin_elementwise_copysign(0.5f - t, u);
-}
+// Phi(u) - 1/2 from the forward's tail polynomial, for a pair of values: the forward's own helper (mdr_encoder_gemm.inl), clamp included
+__device__ inline f32x2 lg_phi_m_half2(f32x2 u) { return gelu_phi_m_half2(u); }
 
 // one 16-byte piece per thread: dz = fp16(dy * (Phi(u) + u phi(u))); rows at or behind the valid count: zeros, nothing read
 __global__ void __launch_bounds__(256)

@@ -116,6 +116,12 @@ def gelu_grad32(u, mutation=None):
     return (s + f32(0.5)) + u * dens
 
 
+def gemm_accum_bound(abs_a, abs_b, terms):
+    """The fp32 accumulation term of a GEMM whose operands are exact: `terms` products added in some order, at most one ulp lost per addition
+    (line 3 of the docstring). Shared with tests/gemm_ref.py: dX IS a forward GEMM."""
+    return terms * X1ULP * (abs_a @ abs_b)
+
+
 def reference_and_bound(x, w, dy, pre=None, m=None, old_dw=None, old_db=None):
     """{"dz", "dx", "dw", "db"} -> (reference, bound), float64. dz and dx have m rows. Asserts that nothing leaves the fp16 range (the bound
     has no term for an overflow)."""
@@ -135,7 +141,7 @@ def reference_and_bound(x, w, dy, pre=None, m=None, old_dw=None, old_db=None):
         assert m == 0 or float((np.abs(dz) + edz).max()) < F16_MAX, "dZ leaves the fp16 range: scale dy down"
     adz = np.abs(dz) + edz
     dx = dz @ W
-    e = edz @ np.abs(W) + N * X1ULP * (adz @ np.abs(W))
+    e = edz @ np.abs(W) + gemm_accum_bound(adz, np.abs(W), N)
     edx = e + _r16(np.abs(dx) + e)
     assert m == 0 or float((np.abs(dx) + edx).max()) < F16_MAX, "dX leaves the fp16 range: scale w down"
     cnt = ((m + SLAB - 1) // SLAB * SLAB + S + 1) * X1ULP
