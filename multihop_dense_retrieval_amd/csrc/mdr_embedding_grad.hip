@@ -1,0 +1,566 @@
+// csrc/mdr_embedding_grad.hip -- the backward of the retriever's embedding layer on packed rows (include/mdr_embedding_grad.h): the plan
+// (a stable sort of the tokens by table row, built once per forward), the segmented sum of d rows into the word and position tables, and
+// the LayerNorm backward fused with the gather in front of it. The forward is embed_ln_kernel of csrc/mdr_encoder_pack_ln.inl,
+//     x = (word[clamp(id)] + pos[min(pid, max_pos - 1)]) + type0,   y = (x - mu) * rstd * g + b,
+// and it saves nothing: the backward recomputes x, mu and rstd from the tables.
+//
+// emb_keys_kernel: one thread per token t < total: its clamped word row and position row (the forward's clamps); writes the plan's header.
+// emb_rank_kernel: rank by counting. A workgroup of four waves owns 64 tokens of one table, one per lane in every wave. The keys of all
+//   tokens pass through LDS in tiles of 4096; wave w counts, over quarter w of each tile, the t' whose (row, t') is smaller than the lane's
+//   (row, t): row' < row + (t' < t). Where a quarter lies wholly in front of or behind the workgroup's tokens the bound is hoisted.
+//   The four counts are added through LDS and order[rank] = t. No data-dependent control flow, stable by construction.
+// emb_segments_kernel: one workgroup per table walks the sorted tokens 1024 at a time, marks the heads (the row differs from the
+//   predecessor's), numbers them by a ballot scan with a carry, and writes seg_start, seg_row and the number of segments.
+// emb_scatter_kernel: a workgroup of eight waves owns a segment (a grid-stride loop over the segments of one table). A wave owns a piece
+//   of P tokens: lane l holds columns l + 64 i and adds the piece's d rows from 0 in token order. The pieces go through LDS eight at a
+//   time and thread e adds them from 0 in ascending piece order. The old value enters last. accumulate = 0: the table is zeroed on the stream first, then the same kernel writes the rows that own a segment.
+// emb_ln_grad_kernel: the rows are cut into S chunks (eg_chunks: a function of (cap, H) alone); one workgroup of four waves owns a chunk,
+//   a wave a token, with the forward's columns l + 64 i at every H. Wave w walks tokens w, w + 4, ... of the chunk in order, writes d of
+//   each and keeps its lanes' dg, db and dtype0 columns in registers; the four waves' columns are added through LDS in wave order and go
+//   to the workspace [S][3][H]. emb_colsum_kernel does the same for dtype0 alone from a given d ([S][1][H]): mdr_embedding_scatter.
+// emb_reduce_kernel: strand j of sixteen adds chunks j, j + 16, ... in order, the min(S, 16) strands are added in order, then the old value.
+// Every output element has one owner and one summation order: no floating-point atomics, two runs give the same bits.
+//
+// Rounding points (tests/embedding_grad_ref.py derives its bound from this list; every operation is fp32, and a multiply feeding an add
+// may be fused or not):
+//   1. x = (w + p) + t0: two rounded adds. The forward's expression.
+//   2. mu = wave_sum(s) / H: s adds the lane's H / 64 elements in index order, wave_sum is the xor butterfly 32, 16, .. 1; var the same
+//      over (x - mu)^2; rstd = rsqrtf(var / H + eps). The forward's expressions in the forward's order.
+//   3. dy = fp32(dy16) + fp32(dy2): one rounded add, none when only one is given.
+//   4. xhat = (x - mu) * rstd, a = dy * g: one rounding each.
+//   5. c1 = wave_sum(sum of a) / H and c2 = wave_sum(sum of a * xhat) / H: every term passes through at most H / 64 + 6 additions.
+//   6. d = rstd * ((a - c1) - xhat * c2): not rounded again; the workspace holds it in fp32.
+//   7. A table row: the pieces' sums (at most P - 1 roundings: the first add is to 0), the pieces in order (at most ceil(n / P) - 1
+//      roundings), the old value (one): at most P - 1 + ceil(n / P) + 1 additions per term.
+//   8. dg += dy * xhat, db += dy and dtype0 += d per token in the wave's order; ((w0 + w1) + w2) + w3 over the waves; the chunks strand
+//      by strand, the strands in order; the old value last. At most rows_per_chunk / 4 + 4 + S + 1 additions per element.
+// Non-finite values propagate by IEEE rules alone: nothing float is clamped, compared or used as an index.
+#include <algorithm>
+#include <climits>
+#include <initializer_list>
+
+#include "mdr_common.h"
+#include "../../include/mdr_embedding_grad.h"
+
+namespace mdr {
+namespace {
+
+typedef int eg_int4 __attribute__((ext_vector_type(4)));
+
+constexpr int kEgMaxCap = 1 << 20;
+constexpr int kEgMaxVocab = 1 << 20;
+constexpr int kEgMaxPos = 1 << 16;
+constexpr int kEgMaxH = 1024;
+constexpr int kEgPerLane = kEgMaxH / 64;
+constexpr int kEgWaves = 4;
+constexpr int kEgThreads = 64 * kEgWaves;
+constexpr int kEgPiece = MDR_EMBEDDING_PIECE;
+constexpr int kEgHeader = MDR_EMBEDDING_PLAN_HEADER;
+constexpr int kEgRankQuarter = 1024;                    // keys a wave counts over per tile
+constexpr int kEgRankTile = kEgRankQuarter * kEgWaves;  // keys in LDS at a time
+constexpr int kEgSegThreads = 1024;
+constexpr int kEgScatterWaves = 8;                      // pieces of a segment summed side by side
+constexpr int kEgScatterThreads = 64 * kEgScatterWaves;
+constexpr int kEgScatterGrid = 1 << 16;                 // most workgroups of emb_scatter_kernel per table
+constexpr int kEgStrands = 16;
+constexpr int kEgMaxChunks = 1024;                      // target number of workgroups ...
+constexpr size_t kEgMaxPartialBytes = (size_t)4 << 20;  // ... as far as the partial sums [S][3][H] stay within 4 MiB
+
+enum { kHdrMagic = 0, kHdrTotal, kHdrSegWord, kHdrSegPos, kHdrCap, kHdrVocab, kHdrMaxPos, kHdrPadRow };
+
+__host__ __device__ inline int eg_table_stride(int cap) { return (3 * cap + 1 + 3) / 4 * 4; }
+__host__ __device__ inline int eg_table_off(int cap, int tbl) { return kEgHeader + tbl * eg_table_stride(cap); }
+__host__ __device__ inline int eg_keys_off(int cap, int tbl) { return kEgHeader + 2 * eg_table_stride(cap) + tbl * cap; }
+inline size_t eg_plan_words(int cap) { return (size_t)kEgHeader + 2 * (size_t)eg_table_stride(cap) + 2 * (size_t)cap; }
+
+bool eg_hidden_ok(int H) { return H >= 64 && H <= kEgMaxH && H % 64 == 0; }
+bool eg_cap_ok(int cap) { return cap >= 1 && cap <= kEgMaxCap; }
+
+// (S, rows per chunk) of a shape inside the limits (lg_chunks of csrc/mdr_layernorm_grad.hip with three planes of partial sums)
+int eg_chunks(int M, int H, int* rpc_out) {
+    const int most = (int)std::min<size_t>(kEgMaxChunks, kEgMaxPartialBytes / (3 * sizeof(float) * (size_t)H));
+    const int rpc = ((M + most - 1) / most + 3) / 4 * 4;
+    *rpc_out = rpc;
+    return (M + rpc - 1) / rpc;
+}
+
+__device__ __forceinline__ float eg_wave_sum(float v) {  // (wave_sum of csrc/mdr_encoder_pack_ln.inl)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ __forceinline__ int eg_total(const int* __restrict__ total, int cap) { return min(max(*total, 0), cap); }
+
+// ---- the plan ----------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) emb_keys_kernel(const long long* __restrict__ ids, const int* __restrict__ tok_src, const int* __restrict__ tok_pid,
+                                                       const int* __restrict__ total_dev, int cap, int vocab, int max_pos, int pad_row, int* __restrict__ plan) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int total = eg_total(total_dev, cap);
+    if (t < kEgHeader) {
+        int v = 0;
+        if (t == kHdrMagic) v = MDR_EMBEDDING_PLAN_MAGIC;
+        if (t == kHdrTotal) v = total;
+        if (t == kHdrCap) v = cap;
+        if (t == kHdrVocab) v = vocab;
+        if (t == kHdrMaxPos) v = max_pos;
+        if (t == kHdrPadRow) v = pad_row;
+        if (t != kHdrSegWord && t != kHdrSegPos) plan[t] = v;  // (the segment counts are emb_segments_kernel's)
+    }
+    if (t >= total) return;
+    long long id = ids[tok_src[t]];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    int pid = tok_pid[t];
+    pid = pid >= max_pos ? max_pos - 1 : (pid < 0 ? 0 : pid);
+    plan[eg_keys_off(cap, 0) + t] = (int)id;
+    plan[eg_keys_off(cap, 1) + t] = pid;
+}
+
+__global__ void __launch_bounds__(kEgThreads) emb_rank_kernel(int* __restrict__ plan, int cap) {
+    __shared__ __attribute__((aligned(16))) int tile[kEgRankTile];
+    __shared__ int counts[kEgWaves][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tbl = blockIdx.y;
+    const int total = plan[kHdrTotal];
+    const int b0 = blockIdx.x * 64;
+    if (b0 >= total) return;  // (uniform over the workgroup)
+    const int* keys = plan + eg_keys_off(cap, tbl);
+    const int t = b0 + lane;
+    const int my = t < total ? keys[t] : 0;
+    int cnt = 0;
+    for (int base = 0; base < total; base += kEgRankTile) {
+#pragma unroll
+        for (int j = 0; j < kEgRankTile / kEgThreads; ++j) {
+            const int idx = base + j * kEgThreads + tid;
+            tile[j * kEgThreads + tid] = idx < total ? keys[idx] : INT_MAX;  // (INT_MAX is below no bound: bounds are at most 2^20)
+        }
+        __syncthreads();
+        const int k0 = base + wave * kEgRankQuarter;
+        if (k0 < total) {
+            const eg_int4* q = (const eg_int4*)(tile + wave * kEgRankQuarter);
+            if (k0 + kEgRankQuarter <= b0 || k0 >= b0 + 64) {  // every t' of the quarter on one side of every t of the workgroup
+                const int bound = my + (k0 < b0 ? 1 : 0);
+#pragma unroll 8
+                for (int i = 0; i < kEgRankQuarter / 4; ++i) {
+                    const eg_int4 v = q[i];
+                    cnt += (v[0] < bound) + (v[1] < bound) + (v[2] < bound) + (v[3] < bound);
+                }
+            } else {
+#pragma unroll 4
+                for (int i = 0; i < kEgRankQuarter / 4; ++i) {
+                    const eg_int4 v = q[i];
+                    const int tt = k0 + 4 * i;
+                    cnt += (v[0] < my + (tt < t)) + (v[1] < my + (tt + 1 < t)) + (v[2] < my + (tt + 2 < t)) + (v[3] < my + (tt + 3 < t));
+                }
+            }
+        }
+        __syncthreads();
+    }
+    counts[wave][lane] = cnt;
+    __syncthreads();
+    if (wave == 0 && t < total) {
+        const int r = ((counts[0][lane] + counts[1][lane]) + counts[2][lane]) + counts[3][lane];
+        plan[eg_table_off(cap, tbl) + r] = t;  // r < total: the number of smaller tokens
+    }
+}
+
+__global__ void __launch_bounds__(kEgSegThreads) emb_segments_kernel(int* __restrict__ plan, int cap) {
+    __shared__ int wsum[kEgSegThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, tbl = blockIdx.x;
+    const int total = plan[kHdrTotal], pad_row = plan[kHdrPadRow];
+    const int* keys = plan + eg_keys_off(cap, tbl);
+    int* order = plan + eg_table_off(cap, tbl);
+    int* seg_start = order + cap;
+    int* seg_row = order + 2 * cap + 1;
+    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    int carry = 0;  // segments in front of this round (every thread keeps the same value)
+    for (int base = 0; base < total; base += kEgSegThreads) {
+        const int i = base + tid;
+        int k = -1;
+        bool head = false;
+        if (i < total) {
+            k = keys[min((unsigned)order[i], (unsigned)(total - 1))];  // (order is a permutation of 0 .. total - 1; the clamps keep a broken one in bounds)
+            head = i == 0 || keys[min((unsigned)order[i - 1], (unsigned)(total - 1))] != k;
+        }
+        const unsigned long long bm = __ballot(head);
+        if (lane == 0) wsum[w] = __popcll(bm);
+        __syncthreads();
+        int off = carry, all = 0;
+#pragma unroll
+        for (int j = 0; j < kEgSegThreads / 64; ++j) {
+            const int c = wsum[j];
+            if (j < w) off += c;
+            all += c;
+        }
+        if (head) {
+            const int s = off + __popcll(bm & lt);
+            seg_start[s] = i;
+            seg_row[s] = k == pad_row ? -1 - k : k;
+        }
+        carry += all;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        seg_start[carry] = total;
+        plan[kHdrSegWord + tbl] = carry;
+    }
+}
+
+// ---- the segmented sum ---------------------------------------------------------------------------------------------------------------
+// the sum of the d rows of tokens ord[0 .. n), n <= P, from 0 in token order: the lane's columns lane + 64 i. The loads of four rows are issued
+// before their adds (one row at a time left the wave waiting for memory once per token); the order of the adds is the tokens'.
+__device__ __forceinline__ void eg_piece_sum(const float* __restrict__ d32, int cap, const int* __restrict__ ord, int n, int H, int nl, int lane, float* acc) {
+#pragma unroll
+    for (int i = 0; i < kEgPerLane; ++i) acc[i] = 0.f;
+    const unsigned last = (unsigned)(cap - 1);  // (ord[j] < total <= cap; the clamp keeps a broken plan in bounds)
+    int j = 0;
+    for (; j + 4 <= n; j += 4) {
+        const float* r0 = d32 + (size_t)min((unsigned)ord[j], last) * H + lane;
+        const float* r1 = d32 + (size_t)min((unsigned)ord[j + 1], last) * H + lane;
+        const float* r2 = d32 + (size_t)min((unsigned)ord[j + 2], last) * H + lane;
+        const float* r3 = d32 + (size_t)min((unsigned)ord[j + 3], last) * H + lane;
+        float v0[kEgPerLane], v1[kEgPerLane], v2[kEgPerLane], v3[kEgPerLane];
+#pragma unroll
+        for (int i = 0; i < kEgPerLane; ++i)
+            if (i < nl) { v0[i] = r0[64 * i]; v1[i] = r1[64 * i]; v2[i] = r2[64 * i]; v3[i] = r3[64 * i]; }
+#pragma unroll
+        for (int i = 0; i < kEgPerLane; ++i)
+            if (i < nl) { acc[i] += v0[i]; acc[i] += v1[i]; acc[i] += v2[i]; acc[i] += v3[i]; }
+    }
+    for (; j < n; ++j) {
+        const float* r = d32 + (size_t)min((unsigned)ord[j], last) * H + lane;
+#pragma unroll
+        for (int i = 0; i < kEgPerLane; ++i)
+            if (i < nl) acc[i] += r[64 * i];
+    }
+}
+
+__global__ void __launch_bounds__(kEgScatterThreads)
+emb_scatter_kernel(const float* __restrict__ d32, const int* __restrict__ plan, int cap, int H, int vocab, int max_pos, float* dword, float* dpos, int accumulate) {
+    __shared__ float red[kEgScatterWaves][kEgMaxH];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tbl = blockIdx.y;
+    float* out = tbl ? dpos : dword;
+    if (!out) return;  // (uniform over the workgroup, as is every branch below but those on `wave`, `lane` and `tid`)
+    if (plan[kHdrMagic] != MDR_EMBEDDING_PLAN_MAGIC || plan[kHdrCap] != cap || plan[kHdrVocab] != vocab || plan[kHdrMaxPos] != max_pos) return;
+    const int nseg = min(plan[kHdrSegWord + tbl], plan[kHdrTotal]);
+    const int* order = plan + eg_table_off(cap, tbl);
+    const int* seg_start = order + cap;
+    const int* seg_row = order + 2 * cap + 1;
+    const int nl = H >> 6, nrows = tbl ? max_pos : vocab;
+    for (int s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const int row = seg_row[s];
+        if (row < 0) continue;  // pad_row: no gradient
+        const int a = seg_start[s], n = seg_start[s + 1] - a;
+        if (row >= nrows || a < 0 || n < 1 || a + n > cap) continue;  // (never in a plan of mdr_embedding_plan)
+        float* o = out + (size_t)row * H;
+        const int pieces = (n + kEgPiece - 1) / kEgPiece;
+        float tot[kEgMaxH / kEgScatterThreads];
+#pragma unroll
+        for (int c = 0; c < kEgMaxH / kEgScatterThreads; ++c) tot[c] = 0.f;
+        for (int p0 = 0; p0 < pieces; p0 += kEgScatterWaves) {
+            const int p = p0 + wave;
+            if (p < pieces) {
+                float acc[kEgPerLane];
+                eg_piece_sum(d32, cap, order + a + p * kEgPiece, min(kEgPiece, n - p * kEgPiece), H, nl, lane, acc);
+#pragma unroll
+                for (int i = 0; i < kEgPerLane; ++i)
+                    if (i < nl) red[wave][lane + 64 * i] = acc[i];
+            }
+            __syncthreads();
+            const int np = min(kEgScatterWaves, pieces - p0);
+#pragma unroll
+            for (int c = 0; c < kEgMaxH / kEgScatterThreads; ++c) {
+                const int e = tid + kEgScatterThreads * c;
+                if (e < H)
+                    for (int w = 0; w < np; ++w) tot[c] += red[w][e];
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int c = 0; c < kEgMaxH / kEgScatterThreads; ++c) {
+            const int e = tid + kEgScatterThreads * c;
+            if (e < H) o[e] = accumulate ? tot[c] + o[e] : tot[c];
+        }
+    }
+}
+
+// ---- sums over all valid tokens --------------------------------------------------------------------------------------------------------
+// the four waves' per-lane columns v[plane][i] (column lane + 64 i) -> part[chunk][NP][H], ((w0 + w1) + w2) + w3
+template <int NP>
+__device__ __forceinline__ void eg_store_partials(float (*red)[3][kEgMaxH], const float (*v)[kEgPerLane], int nl, int H, float* __restrict__ part) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int pl = 0; pl < NP; ++pl)
+#pragma unroll
+        for (int i = 0; i < kEgPerLane; ++i)
+            if (i < nl) red[wave][pl][lane + 64 * i] = v[pl][i];
+    __syncthreads();
+#pragma unroll
+    for (int pl = 0; pl < NP; ++pl)
+        for (int e = tid; e < H; e += kEgThreads)
+            part[((size_t)blockIdx.x * NP + pl) * H + e] = ((red[0][pl][e] + red[1][pl][e]) + red[2][pl][e]) + red[3][pl][e];
+}
+
+__global__ void __launch_bounds__(kEgThreads)
+emb_ln_grad_kernel(const long long* __restrict__ ids, const int* __restrict__ tok_src, const int* __restrict__ tok_pid, const int* __restrict__ total_dev,
+                   int cap, const float* __restrict__ word, const float* __restrict__ pos, const float* __restrict__ type0, const float* __restrict__ g, int H,
+                   int vocab, int max_pos, float eps, const _Float16* __restrict__ dy16, const void* __restrict__ dy2, int dy2_f32, int rpc,
+                   float* __restrict__ d32, float* __restrict__ part) {
+    __shared__ float red[kEgWaves][3][kEgMaxH];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nl = H >> 6;
+    const int total = eg_total(total_dev, cap);
+    const int r0 = blockIdx.x * rpc, r1 = min(r0 + rpc, total);
+
+    float gv[kEgPerLane], tv[kEgPerLane], sums[3][kEgPerLane];  // sums: dg, db, dtype0
+#pragma unroll
+    for (int i = 0; i < kEgPerLane; ++i) {
+        if (i < nl) { gv[i] = g[lane + 64 * i]; tv[i] = type0[lane + 64 * i]; }
+        sums[0][i] = sums[1][i] = sums[2][i] = 0.f;
+    }
+    for (int t = r0 + wave; t < r1; t += kEgWaves) {
+        long long id = ids[tok_src[t]];
+        id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+        int pid = tok_pid[t];
+        pid = pid >= max_pos ? max_pos - 1 : (pid < 0 ? 0 : pid);
+        const float* wr = word + (size_t)id * H;
+        const float* pr = pos + (size_t)pid * H;
+        const size_t off = (size_t)t * H;
+        float x[kEgPerLane], dy[kEgPerLane];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < kEgPerLane; ++i)
+            if (i < nl) {
+                const int e = lane + 64 * i;
+                x[i] = wr[e] + pr[e] + tv[i];
+                s += x[i];
+                if (dy16) {
+                    dy[i] = (float)dy16[off + e];
+                    if (dy2) dy[i] += dy2_f32 ? ((const float*)dy2)[off + e] : (float)((const _Float16*)dy2)[off + e];
+                } else {
+                    dy[i] = dy2_f32 ? ((const float*)dy2)[off + e] : (float)((const _Float16*)dy2)[off + e];
+                }
+            }
+        const float mu = eg_wave_sum(s) / H;
+        float v = 0.f;
+#pragma unroll
+        for (int i = 0; i < kEgPerLane; ++i)
+            if (i < nl) { const float dlt = x[i] - mu; v += dlt * dlt; }
+        const float rstd = rsqrtf(eg_wave_sum(v) / H + eps);
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < kEgPerLane; ++i)
+            if (i < nl) {
+                const float xh = (x[i] - mu) * rstd;
+                const float a = dy[i] * gv[i];
+                s1 += a;
+                s2 += a * xh;
+                sums[0][i] += dy[i] * xh;
+                sums[1][i] += dy[i];
+                x[i] = xh;
+                dy[i] = a;
+            }
+        const float c1 = eg_wave_sum(s1) / H, c2 = eg_wave_sum(s2) / H;
+#pragma unroll
+        for (int i = 0; i < kEgPerLane; ++i)
+            if (i < nl) {
+                const float d = rstd * ((dy[i] - c1) - x[i] * c2);
+                sums[2][i] += d;
+                d32[off + lane + 64 * i] = d;
+            }
+    }
+    if (part) eg_store_partials<3>(red, sums, nl, H, part);
+}
+
+__global__ void __launch_bounds__(kEgThreads)
+emb_colsum_kernel(const float* __restrict__ d32, const int* __restrict__ plan, int cap, int H, int rpc, float* __restrict__ part) {
+    __shared__ float red[kEgWaves][3][kEgMaxH];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nl = H >> 6;
+    const int total = plan[kHdrMagic] == MDR_EMBEDDING_PLAN_MAGIC && plan[kHdrCap] == cap ? min(max(plan[kHdrTotal], 0), cap) : 0;
+    const int r0 = blockIdx.x * rpc, r1 = min(r0 + rpc, total);
+    float sums[1][kEgPerLane];
+#pragma unroll
+    for (int i = 0; i < kEgPerLane; ++i) sums[0][i] = 0.f;
+    for (int t = r0 + wave; t < r1; t += kEgWaves) {
+        const float* r = d32 + (size_t)t * H + lane;
+#pragma unroll
+        for (int i = 0; i < kEgPerLane; ++i)
+            if (i < nl) sums[0][i] += r[64 * i];
+    }
+    eg_store_partials<1>(red, sums, nl, H, part);
+}
+
+// part [S][NP][H] -> the NP outputs. A workgroup owns 64 columns of one plane, a wave is a strand.
+__global__ void __launch_bounds__(64 * kEgStrands)
+emb_reduce_kernel(const float* __restrict__ part, int S, int NP, int H, float* o0, float* o1, float* o2, int accumulate) {
+    __shared__ float st[kEgStrands][64];
+    const int col = threadIdx.x & 63, strand = threadIdx.x >> 6;
+    const int i = blockIdx.x * 64 + col;  // < NP H: the grid is NP H / 64 workgroups
+    const int pl = i / H, e = i - pl * H;  // (pl is uniform over the workgroup: H is a multiple of 64)
+    float* out = pl == 0 ? o0 : (pl == 1 ? o1 : o2);
+    if (!out) return;
+    const float* p = part + (size_t)pl * H + e;
+    float acc = 0.f;
+#pragma unroll 8
+    for (int c = strand; c < S; c += kEgStrands) acc += p[(size_t)c * NP * H];
+    st[strand][col] = acc;
+    __syncthreads();
+    if (strand != 0) return;
+    const int ns = min(S, kEgStrands);
+    for (int j = 1; j < ns; ++j) acc += st[j][col];
+    out[e] = accumulate ? acc + out[e] : acc;
+}
+
+bool eg_aligned16(std::initializer_list<const void*> ps) {
+    uintptr_t all = 0;
+    for (const void* p : ps) all |= (uintptr_t)p;
+    return (all & 15) == 0;
+}
+
+// the table half of both entry points: accumulate = 0 zeroes the given tables first
+int eg_launch_tables(const float* d32, const int* plan, int cap, int H, int vocab, int max_pos, float* dword, float* dpos, int accumulate, hipStream_t st) {
+    if (!dword && !dpos) return MDR_OK;
+    if (!accumulate) {
+        if (dword) MDR_HIP_TRY(hipMemsetAsync(dword, 0, (size_t)vocab * H * sizeof(float), st));
+        if (dpos) MDR_HIP_TRY(hipMemsetAsync(dpos, 0, (size_t)max_pos * H * sizeof(float), st));
+    }
+    hipLaunchKernelGGL(emb_scatter_kernel, dim3(std::min(cap, kEgScatterGrid), 2), dim3(kEgScatterThreads), 0, st, d32, plan, cap, H, vocab, max_pos, dword, dpos, accumulate);
+    MDR_HIP_TRY(hipGetLastError());
+    return MDR_OK;
+}
+
+}  // namespace
+}  // namespace mdr
+
+extern "C" {
+
+size_t mdr_embedding_plan_bytes(int cap) {
+    using namespace mdr;
+    return eg_cap_ok(cap) ? align_up(eg_plan_words(cap) * sizeof(int), 256) : 0;
+}
+
+int mdr_embedding_plan(const int64_t* ids_dev, const int* tok_src_dev, const int* tok_pid_dev, const int* total_dev, int cap, int vocab, int max_pos,
+                       int pad_row, void* plan_dev, size_t plan_bytes, int device, void* stream) {
+    using namespace mdr;
+    const char* fn = "mdr_embedding_plan";
+    MDR_REQUIRE(ids_dev && tok_src_dev && tok_pid_dev && total_dev, "%s: NULL pointer (ids, tok_src, tok_pid and total are required)", fn);
+    MDR_REQUIRE(eg_cap_ok(cap), "%s: cap=%d out of range (1 .. 2^20)", fn, cap);
+    MDR_REQUIRE(vocab >= 1 && vocab <= kEgMaxVocab, "%s: vocab=%d out of range (1 .. 2^20)", fn, vocab);
+    MDR_REQUIRE(max_pos >= 1 && max_pos <= kEgMaxPos, "%s: max_pos=%d out of range (1 .. 2^16)", fn, max_pos);
+    MDR_REQUIRE(pad_row >= -1 && pad_row < kEgMaxVocab, "%s: pad_row=%d out of range (-1 .. 2^20 - 1)", fn, pad_row);
+    MDR_REQUIRE(eg_aligned16({plan_dev}), "%s: the plan must be 16-byte aligned", fn);
+    const size_t need = eg_plan_words(cap) * sizeof(int);
+    if (!(plan_dev && plan_bytes >= need))
+        return set_error(MDR_E_WORKSPACE, "%s: plan buffer of %zu bytes, need %zu (mdr_embedding_plan_bytes)", fn, plan_dev ? plan_bytes : (size_t)0, need);
+    DeviceGuard guard(device);
+    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = (hipStream_t)stream;
+    int* plan = (int*)plan_dev;
+    hipLaunchKernelGGL(emb_keys_kernel, dim3((std::max(cap, kEgHeader) + 255) / 256), dim3(256), 0, st, (const long long*)ids_dev, tok_src_dev, tok_pid_dev, total_dev,
+                       cap, vocab, max_pos, pad_row, plan);
+    MDR_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(emb_rank_kernel, dim3((cap + 63) / 64, 2), dim3(kEgThreads), 0, st, plan, cap);
+    MDR_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(emb_segments_kernel, dim3(2), dim3(kEgSegThreads), 0, st, plan, cap);
+    MDR_HIP_TRY(hipGetLastError());
+    return MDR_OK;
+}
+
+int mdr_embedding_backward_chunks(int cap, int H, int* rows_per_chunk) {
+    using namespace mdr;
+    int rpc = 0, S = 0;
+    if (eg_cap_ok(cap) && eg_hidden_ok(H)) S = eg_chunks(cap, H, &rpc);
+    if (rows_per_chunk) *rows_per_chunk = rpc;
+    return S;
+}
+
+size_t mdr_embedding_scatter_workspace_bytes(int cap, int H) {
+    using namespace mdr;
+    if (!(eg_cap_ok(cap) && eg_hidden_ok(H))) return 0;
+    int rpc;
+    return align_up((size_t)eg_chunks(cap, H, &rpc) * H * sizeof(float), 256);
+}
+
+size_t mdr_embedding_backward_workspace_bytes(int cap, int H) {
+    using namespace mdr;
+    if (!(eg_cap_ok(cap) && eg_hidden_ok(H))) return 0;
+    int rpc;
+    return align_up((size_t)cap * H * sizeof(float), 256) + align_up((size_t)eg_chunks(cap, H, &rpc) * 3 * H * sizeof(float), 256);
+}
+
+int mdr_embedding_scatter(const float* d32_dev, const void* plan_dev, int cap, int H, int vocab, int max_pos, float* dword_dev, float* dpos_dev,
+                          float* dtype0_dev, int accumulate, void* workspace_dev, size_t workspace_bytes, int device, void* stream) {
+    using namespace mdr;
+    const char* fn = "mdr_embedding_scatter";
+    MDR_REQUIRE(d32_dev && plan_dev, "%s: NULL pointer (d32 and the plan are required)", fn);
+    MDR_REQUIRE(dword_dev || dpos_dev || dtype0_dev, "%s: NULL pointer (every output: at least one is required)", fn);
+    MDR_REQUIRE(accumulate == 0 || accumulate == 1, "%s: accumulate must be 0 or 1, got %d", fn, accumulate);
+    MDR_REQUIRE(eg_cap_ok(cap), "%s: cap=%d out of range (1 .. 2^20)", fn, cap);
+    MDR_REQUIRE(eg_hidden_ok(H), "%s: H=%d unsupported (a multiple of 64, 64 .. 1024)", fn, H);
+    MDR_REQUIRE(vocab >= 1 && vocab <= kEgMaxVocab, "%s: vocab=%d out of range (1 .. 2^20)", fn, vocab);
+    MDR_REQUIRE(max_pos >= 1 && max_pos <= kEgMaxPos, "%s: max_pos=%d out of range (1 .. 2^16)", fn, max_pos);
+    MDR_REQUIRE(eg_aligned16({d32_dev, plan_dev, dword_dev, dpos_dev, dtype0_dev, workspace_dev}), "%s: every pointer must be 16-byte aligned", fn);
+    int rpc;
+    const int S = eg_chunks(cap, H, &rpc);
+    const size_t need = dtype0_dev ? (size_t)S * H * sizeof(float) : 0;
+    if (need && !(workspace_dev && workspace_bytes >= need))
+        return set_error(MDR_E_WORKSPACE, "%s: workspace of %zu bytes, need %zu (mdr_embedding_scatter_workspace_bytes)", fn,
+                         workspace_dev ? workspace_bytes : (size_t)0, need);
+    DeviceGuard guard(device);
+    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = (hipStream_t)stream;
+    const int* plan = (const int*)plan_dev;
+    if (dtype0_dev) {
+        float* part = (float*)workspace_dev;
+        hipLaunchKernelGGL(emb_colsum_kernel, dim3(S), dim3(kEgThreads), 0, st, d32_dev, plan, cap, H, rpc, part);
+        MDR_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(emb_reduce_kernel, dim3(H / 64), dim3(64 * kEgStrands), 0, st, part, S, 1, H, dtype0_dev, (float*)nullptr, (float*)nullptr, accumulate);
+        MDR_HIP_TRY(hipGetLastError());
+    }
+    return eg_launch_tables(d32_dev, plan, cap, H, vocab, max_pos, dword_dev, dpos_dev, accumulate, st);
+}
+
+int mdr_embedding_backward(const int64_t* ids_dev, const int* tok_src_dev, const int* tok_pid_dev, const int* total_dev, int cap, const float* word_dev,
+                           const float* pos_dev, const float* type0_dev, const float* g_dev, int H, int vocab, int max_pos, float eps, const void* dy16_dev,
+                           const void* dy2_dev, int dy2_f32, const void* plan_dev, float* dword_dev, float* dpos_dev, float* dtype0_dev, float* dg_dev,
+                           float* db_dev, float* d32_dev, int accumulate, void* workspace_dev, size_t workspace_bytes, int device, void* stream) {
+    using namespace mdr;
+    const char* fn = "mdr_embedding_backward";
+    MDR_REQUIRE(ids_dev && tok_src_dev && tok_pid_dev && total_dev, "%s: NULL pointer (ids, tok_src, tok_pid and total are required)", fn);
+    MDR_REQUIRE(word_dev && pos_dev && type0_dev && g_dev, "%s: NULL pointer (word, pos, type0 and g are required)", fn);
+    MDR_REQUIRE(dy16_dev || dy2_dev, "%s: NULL pointer (dy16 and dy2: at least one is required)", fn);
+    MDR_REQUIRE(dword_dev || dpos_dev || dtype0_dev || dg_dev || db_dev || d32_dev, "%s: NULL pointer (every output: at least one is required)", fn);
+    MDR_REQUIRE(plan_dev || !(dword_dev || dpos_dev), "%s: NULL pointer (dword and dpos need the plan)", fn);
+    MDR_REQUIRE(dy2_f32 == 0 || dy2_f32 == 1, "%s: dy2_f32 must be 0 or 1, got %d", fn, dy2_f32);
+    MDR_REQUIRE(accumulate == 0 || accumulate == 1, "%s: accumulate must be 0 or 1, got %d", fn, accumulate);
+    MDR_REQUIRE(eg_cap_ok(cap), "%s: cap=%d out of range (1 .. 2^20)", fn, cap);
+    MDR_REQUIRE(eg_hidden_ok(H), "%s: H=%d unsupported (a multiple of 64, 64 .. 1024)", fn, H);
+    MDR_REQUIRE(vocab >= 1 && vocab <= kEgMaxVocab, "%s: vocab=%d out of range (1 .. 2^20)", fn, vocab);
+    MDR_REQUIRE(max_pos >= 1 && max_pos <= kEgMaxPos, "%s: max_pos=%d out of range (1 .. 2^16)", fn, max_pos);
+    MDR_REQUIRE(eg_aligned16({word_dev, pos_dev, type0_dev, g_dev, dy16_dev, dy2_dev, plan_dev, dword_dev, dpos_dev, dtype0_dev, dg_dev, db_dev, d32_dev,
+                              workspace_dev}),
+                "%s: every float, plan and workspace pointer must be 16-byte aligned", fn);
+    int rpc;
+    const int S = eg_chunks(cap, H, &rpc);
+    const size_t d_bytes = align_up((size_t)cap * H * sizeof(float), 256);
+    const size_t need = d_bytes + (size_t)S * 3 * H * sizeof(float);
+    if (!(workspace_dev && workspace_bytes >= need))
+        return set_error(MDR_E_WORKSPACE, "%s: workspace of %zu bytes, need %zu (mdr_embedding_backward_workspace_bytes)", fn,
+                         workspace_dev ? workspace_bytes : (size_t)0, need);
+    DeviceGuard guard(device);
+    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = (hipStream_t)stream;
+    float* d32 = d32_dev ? d32_dev : (float*)workspace_dev;  // d goes where the caller wants to see it
+    const bool sums = dtype0_dev || dg_dev || db_dev;
+    float* part = sums ? (float*)((char*)workspace_dev + d_bytes) : nullptr;
+    hipLaunchKernelGGL(emb_ln_grad_kernel, dim3(S), dim3(kEgThreads), 0, st, (const long long*)ids_dev, tok_src_dev, tok_pid_dev, total_dev, cap, word_dev, pos_dev,
+                       type0_dev, g_dev, H, vocab, max_pos, eps, (const _Float16*)dy16_dev, dy2_dev, dy2_f32, rpc, d32, part);
+    MDR_HIP_TRY(hipGetLastError());
+    if (part) {
+        hipLaunchKernelGGL(emb_reduce_kernel, dim3(3 * H / 64), dim3(64 * kEgStrands), 0, st, part, S, 3, H, dg_dev, db_dev, dtype0_dev, accumulate);
+        MDR_HIP_TRY(hipGetLastError());
+    }
+    return eg_launch_tables(d32, (const int*)plan_dev, cap, H, vocab, max_pos, dword_dev, dpos_dev, accumulate, st);
+}
+
+}  // extern "C"
