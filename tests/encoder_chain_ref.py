@@ -1,0 +1,324 @@
+"""Host statements of the WHOLE retriever encoder's backward, for the tests that chain the differentiable functions of the package
+(tests/test_encoder_chain_host.py, tests/test_encoder_chain_gpu.py). CPU only, torch and numpy; nothing here imports the product and nothing
+here was measured on a kernel.
+
+model64    the fp64 model with no rounding anywhere: oracle/roberta_torch.encode (o1 = None) on fp64 leaf tensors; its loss is loss64, the
+           formula of tests/mhop_loss_ref.py written with differentiable torch ops. Its gradients are the reference g64.
+regime     an independent restatement of the device chain's numerics in plain torch autograd: fp64 arithmetic, and an fp16 rounding of the
+           VALUE (forward) and of the INCOMING GRADIENT (backward) at every tensor the device chain holds in fp16:
+             each Linear's input, its fp16 weight (value only: dW is fp32) and its fp16 output; the scores' gradient dS (the operand of the
+             dQ / dK contractions); P as operand of P V (value only) and ctx; the GELU output, with GELU' taken at the fp16 pre-activation and
+             dZ rounded; the fp16 copy of each LayerNorm output next to the unrounded one (the fp32 residual stream); the head's fp16
+             pre-activation (project.0 through the fp16 Linear). The in-batch loss rounds as `o1` of tests/mhop_loss_ref.py does.
+           The dataflow is the default mode of the product's trunk (residual_fp32 = 2): a Linear's fp16 output meets the fp32 stream in the
+           LayerNorm; the last layer runs its query, its attention and its tail on the CLS rows alone.
+regime_b   a second correct implementation: the same in fp32 arithmetic with the batch reversed.
+MUTATIONS  wiring defects of `regime`, one at a time (what a wrong composition of correct functions looks like).
+
+Criterion E (criterion_e). For every parameter tensor p, e(p) = |g(p) - g64(p)|_2 / |g64(p)|_2, and e_pool the same ratio over all compared
+tensors at once. A candidate passes when e_cand(p) <= 2 max(e_reg(p), e_pool) for every p: the yardstick is the reference regime's own error.
+The factor 2: the candidate and `regime` share the rounding points but not the summation orders, so their errors against fp64 are two draws of
+one size. The floor e_pool: a few tensors have e_reg = 0 (project.1.bias is a plain sum of the cotangent).
+
+Not compared by a ratio (ZERO_GRAD): attention.self.key.bias of every layer. Softmax is invariant under a shift of a row of scores, and the key
+bias adds q_i . b_k to every score of query i: its gradient is mathematically zero, what a computation returns is rounding noise, and no
+relative criterion over it can hold. Rows of word_embeddings that own no token, and padding_idx's row, are exactly zero on both sides
+(zero_rows): equality is asserted there.
+"""
+import math
+
+import numpy as np
+import torch
+
+from oracle import roberta_torch, seeded
+
+GEOM = seeded.TINY
+WEIGHT_SEED = 23
+KEYS = ("q", "q_sp1", "c1", "c2", "neg_1", "neg_2")
+# (L, lengths): 501 tokens in 1280 slots, the ring attention kernel, row counts on both sides of the 64-row chunks; and the one-shot kernel
+BATCHES = {"L160": (160, (1, 2, 17, 63, 64, 65, 129, 160)), "L48": (48, (1, 5, 16, 17, 33, 48))}
+# the six encodes of the in-batch loss: 4 sequences each, two padded lengths
+LOSS_L = {"q": 48, "q_sp1": 48, "c1": 160, "c2": 160, "neg_1": 48, "neg_2": 160}
+MUTATIONS = ("res_dropped_ln1", "res_dropped_ln2", "cls_rows_not_added", "dy2_dropped", "dw_qk_swapped", "last_call_only", "gelu_grad_at_output",
+             "pos_from_padded_index")
+
+
+def param_names(geom=GEOM):
+    return [k for k in seeded.state_dict_shapes(geom, with_pooler=False)]
+
+
+def zero_grad_names(geom=GEOM):
+    return [k for k in param_names(geom) if k.endswith("attention.self.key.bias")]
+
+
+def state_dict(geom=GEOM, seed=WEIGHT_SEED):
+    return seeded.make_state_dict(seed, geom, with_pooler=False)
+
+
+def make_batch(L, lens, seed, vocab=GEOM["vocab"]):
+    """ids, mask int64 [B, L]: <s> tokens </s> then pad (a sequence of one token is <s> alone)"""
+    B = len(lens)
+    body = seeded.integers(seed, f"chain.tok.{L}", (B, L), 3, vocab)
+    ids, mask = np.full((B, L), GEOM["pad_id"], np.int64), np.zeros((B, L), np.int64)
+    for b, n in enumerate(lens):
+        ids[b, :n] = body[b, :n]
+        ids[b, 0] = 0
+        if n >= 2:
+            ids[b, n - 1] = 2
+        mask[b, :n] = 1
+    return ids, mask
+
+
+def batch(name):
+    L, lens = BATCHES[name]
+    return make_batch(L, lens, 31)
+
+
+def loss_batches():
+    return {k: seeded.make_token_batch(37 + i, "chain." + k, 4, LOSS_L[k], GEOM["vocab"]) for i, k in enumerate(KEYS)}
+
+
+def cotangent(B, H=GEOM["hidden"]):
+    return seeded.normal(41, f"chain.G.{B}", (B, H)).astype(np.float32)
+
+
+def zero_rows(batches, vocab=GEOM["vocab"], pad=GEOM["pad_id"]):
+    """bool [vocab]: the rows of word_embeddings whose gradient is exactly zero -- no masked-in token of any batch reads them, or padding_idx"""
+    used = np.zeros(vocab, bool)
+    for ids, mask in batches:
+        used[np.asarray(ids)[np.asarray(mask) != 0]] = True
+    used[pad] = False
+    return ~used
+
+
+# ---- rounding points -----------------------------------------------------------------------------------------------------------------------
+def _h(t):
+    return t.to(torch.float16).to(t.dtype)
+
+
+class _Round(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, value, grad):
+        ctx.grad = grad
+        return _h(x) if value else x.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return (_h(g) if ctx.grad else g), None, None
+
+
+def R(x):
+    """a tensor the device holds in fp16: its value and its gradient are rounded"""
+    return _Round.apply(x, True, True)
+
+
+def Rv(x):
+    """an fp16 operand made from an fp32 tensor whose gradient stays fp32 (a weight, P)"""
+    return _Round.apply(x, True, False)
+
+
+def Rg(x):
+    """an fp32 value whose gradient the device rounds to fp16 (the scores, the GELU's pre-activation)"""
+    return _Round.apply(x, False, True)
+
+
+def _gelu(z):
+    return 0.5 * z * (1.0 + torch.erf(z / math.sqrt(2.0)))
+
+
+def _gelu_grad(u):
+    return 0.5 * torch.erfc(-u / math.sqrt(2.0)) + u * torch.exp(-0.5 * u * u) / math.sqrt(2.0 * math.pi)
+
+
+class _GeluAt(torch.autograd.Function):
+    """gelu(z), differentiated at the fp16 pre-activation as the device does (at_output: at the rounded OUTPUT, a defect)"""
+    @staticmethod
+    def forward(ctx, z, at_output):
+        y = _gelu(z)
+        ctx.save_for_backward(_h(y) if at_output else _h(z))
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (at,) = ctx.saved_tensors
+        return g * _gelu_grad(at), None
+
+
+# ---- the encoders --------------------------------------------------------------------------------------------------------------------------
+def leaves(sd, dtype=torch.float64):
+    return {k: torch.tensor(np.asarray(v), dtype=dtype, requires_grad=True) for k, v in sd.items() if "pooler" not in k}
+
+
+def model64(W, geom, ids, mask):
+    """[B, hidden] fp64, differentiable with respect to the fp64 leaves W: nothing is rounded"""
+    return roberta_torch.encode(W, geom, ids, mask, torch.float64, o1=None)
+
+
+def regime_encode(W, geom, ids, mask, mutation=None):
+    """[B, hidden] in the dtype of the leaves W (module docstring)"""
+    dtype = W["project.1.bias"].dtype
+    H, nh, eps, pad, nl = geom["hidden"], geom["heads"], geom["ln_eps"], geom["pad_id"], geom["layers"]
+    hd = H // nh
+    ids, mask = torch.as_tensor(ids), torch.as_tensor(mask)
+    B, L = ids.shape
+    m = (ids != pad).long()
+    pos = torch.cumsum(m, 1) * m + pad
+    if mutation == "pos_from_padded_index":
+        pos = torch.arange(L).expand(B, L)
+    ln = roberta_torch.layer_norm
+    e = "encoder.embeddings."
+    x = (W[e + "word_embeddings.weight"][ids] + W[e + "position_embeddings.weight"][pos]) + W[e + "token_type_embeddings.weight"][0]
+    h32 = ln(x, W[e + "LayerNorm.weight"], W[e + "LayerNorm.bias"], eps)
+    h16 = R(h32)
+    add_mask = ((1.0 - mask.to(dtype)) * -10000.0)[:, None, None, :]
+
+    def linear(t, name, gelu=False):
+        z = R(t) @ Rv(W[name + ".weight"]).T + W[name + ".bias"]
+        return R(_GeluAt.apply(Rg(z), mutation == "gelu_grad_at_output")) if gelu else R(z)
+
+    def heads(t):
+        return t.reshape(B, -1, nh, hd).permute(0, 2, 1, 3)
+
+    def tail(p, ctx, h32, first):
+        res = h32.detach() if (mutation == "res_dropped_ln1" and first) else h32
+        a32 = ln(linear(ctx, p + "attention.output.dense") + res, W[p + "attention.output.LayerNorm.weight"], W[p + "attention.output.LayerNorm.bias"], eps)
+        f = linear(linear(R(a32), p + "intermediate.dense", True), p + "output.dense")
+        res = a32.detach() if (mutation == "res_dropped_ln2" and first) or (mutation == "dy2_dropped" and not first) else a32
+        o32 = ln(f + res, W[p + "output.LayerNorm.weight"], W[p + "output.LayerNorm.bias"], eps)
+        return R(o32), o32
+
+    for i in range(nl):
+        p = f"encoder.encoder.layer.{i}."
+        last = i == nl - 1
+        q, k, v = (heads(linear(h16, p + "attention.self." + n)) for n in ("query", "key", "value"))
+        if last:  # the query, the attention and the tail of the CLS rows alone
+            q = q[:, :, :1]
+        s = Rg(q @ k.transpose(-1, -2) / math.sqrt(hd) + add_mask)
+        ctx = R(Rv(torch.softmax(s, -1)) @ v).permute(0, 2, 1, 3).reshape(B, -1, H)
+        if last:
+            cls32 = h32[:, 0]
+            h16, h32 = tail(p, ctx[:, 0], cls32.detach() if mutation == "cls_rows_not_added" else cls32, False)
+        else:
+            h16, h32 = tail(p, ctx, h32, i == 0)
+    y = linear(h16, "project.0")
+    return ln(y, W["project.1.weight"], W["project.1.bias"], eps)
+
+
+# ---- the loss ------------------------------------------------------------------------------------------------------------------------------
+def _loss(o, mm, bmm):
+    B = o["q"].shape[0]
+    rows = torch.arange(B)
+    total = 0.0
+    for h, x in enumerate((o["q"], o["q_sp1"])):
+        s = torch.cat([mm(x, torch.cat([o["c1"], o["c2"]])), bmm(x, torch.stack([o["neg_1"], o["neg_2"]], 1))], 1)
+        if h == 0:
+            hide = torch.zeros_like(s, dtype=torch.bool)
+            hide[rows, B + rows] = True
+            s = s.masked_fill(hide, float("-inf"))
+        total = total + (torch.logsumexp(s, 1) - s[rows, rows + (B if h else 0)]).mean()
+    return total
+
+
+def loss64(o):
+    """the formula of tests/mhop_loss_ref.py (no queue) on six [B, d] tensors, differentiable, nothing rounded"""
+    return _loss(o, lambda x, c: x @ c.T, lambda x, n: torch.einsum("bd,bnd->bn", x, n))
+
+
+def loss_regime(o):
+    """mode O1 of tests/mhop_loss_ref.py: fp16 operands, fp16 scores, g rounded to fp16, every contraction's backward result rounded to fp16 per
+    call, the terms of one leaf added unrounded"""
+    return _loss(o, lambda x, c: R(R(x) @ R(c).T), lambda x, n: R(torch.einsum("bd,bnd->bn", R(x), R(n))))
+
+
+# ---- gradients -----------------------------------------------------------------------------------------------------------------------------
+def _encoder(kind):
+    if kind == "model64":
+        return torch.float64, False, model64
+    if kind == "regime":
+        return torch.float64, False, regime_encode
+    if kind == "regime_b":
+        return torch.float32, True, regime_encode
+    raise ValueError(kind)
+
+
+def _finish(W, mutation):
+    g = {k: (np.zeros(tuple(v.shape)) if v.grad is None else v.grad.detach().to(torch.float64).numpy().copy()) for k, v in W.items()}
+    if mutation == "dw_qk_swapped":
+        for k in [k for k in g if k.endswith("attention.self.query.weight")]:
+            k2 = k.replace("query", "key")
+            g[k], g[k2] = g[k2], g[k]
+    return g
+
+
+def grads_cotangent(kind, sd, geom, ids, mask, G, scale=1.0, mutation=None):
+    """(embeddings float64 [B, hidden], {parameter: d <embeddings, G> / d parameter, float64}): the backward runs on scale * G (a loss scale
+    riding in the gradient, a power of two) and the result is divided by it"""
+    dtype, flip, enc = _encoder(kind)
+    W = leaves(sd, dtype)
+    ids, mask, G = np.asarray(ids), np.asarray(mask), np.asarray(G)
+    if flip:
+        ids, mask, G = ids[::-1].copy(), mask[::-1].copy(), G[::-1].copy()
+    out = enc(W, geom, ids, mask, mutation) if enc is regime_encode else enc(W, geom, ids, mask)
+    out.backward(torch.tensor(G * scale, dtype=dtype))
+    emb = out.detach().to(torch.float64).numpy()
+    return (emb[::-1].copy() if flip else emb), {k: v / scale for k, v in _finish(W, mutation).items()}
+
+
+def grads_loss(kind, sd, geom, batches, mutation=None):
+    """(loss, {parameter: gradient}, {name: embeddings}, {name: d loss / d embeddings}) of the in-batch loss over six encodes that share the
+    weights. Each encode differentiates into leaves of its own; the parameter's gradient is their sum (last_call_only: the last one's alone)."""
+    dtype, flip, enc = _encoder(kind)
+    Ws, o = [], {}
+    for k in KEYS:
+        ids, mask = batches[k]
+        if flip:
+            ids, mask = ids[::-1].copy(), mask[::-1].copy()
+        W = leaves(sd, dtype)
+        Ws.append(W)
+        out = enc(W, geom, ids, mask, mutation) if enc is regime_encode else enc(W, geom, ids, mask)
+        o[k] = (out.flip(0) if flip else out)
+        o[k].retain_grad()
+    loss = (loss64 if kind == "model64" else loss_regime)(o)
+    loss.backward()
+    per = [_finish(W, mutation) for W in Ws]
+    keep = per[-1:] if mutation == "last_call_only" else per
+    g = {k: sum(p[k] for p in keep) for k in per[0]}
+    return (float(loss.detach()), g, {k: v.detach().to(torch.float64).numpy() for k, v in o.items()},
+            {k: v.grad.detach().to(torch.float64).numpy() for k, v in o.items()})
+
+
+# ---- criterion E ---------------------------------------------------------------------------------------------------------------------------
+def _norm(a):
+    return float(np.sqrt((np.asarray(a, np.float64) ** 2).sum()))
+
+
+def rel_errors(g, g64, names):
+    """({p: |g - g64| / |g64|}, the same ratio over all of `names` at once)"""
+    per = {k: _norm(np.asarray(g[k], np.float64) - g64[k]) / _norm(g64[k]) for k in names}
+    num = math.sqrt(sum(_norm(np.asarray(g[k], np.float64) - g64[k]) ** 2 for k in names))
+    return per, num / math.sqrt(sum(_norm(g64[k]) ** 2 for k in names))
+
+
+def criterion_e(g_cand, g_reg, g64, geom=GEOM):
+    """[(p, e_cand, e_reg, bar, e_cand / bar)] over every parameter but ZERO_GRAD's, and e_pool of the regime. Passing: every ratio <= 1."""
+    skip = set(zero_grad_names(geom))
+    names = [k for k in param_names(geom) if k not in skip]
+    e_reg, e_pool = rel_errors(g_reg, g64, names)
+    e_cand, _ = rel_errors(g_cand, g64, names)
+    rows = []
+    for k in names:
+        bar = 2.0 * max(e_reg[k], e_pool)
+        rows.append((k, e_cand[k], e_reg[k], bar, e_cand[k] / bar))
+    return rows, e_pool
+
+
+def failures(rows):
+    return [r for r in rows if not r[4] <= 1.0]
+
+
+def table(rows, e_pool, title):
+    short = lambda k: k.replace("encoder.encoder.layer.", "L").replace("encoder.embeddings.", "emb.").replace("attention.", "att.")  # noqa: E731
+    out = [f"{title}: e_pool(regime) = {e_pool:.3e}", "| tensor | e_cand | e_reg | e_cand / e_reg | e_cand / bar |", "|---|---|---|---|---|"]
+    for k, ec, er, bar, share in rows:
+        out.append(f"| {short(k)} | {ec:.3e} | {er:.3e} | {(ec / er if er > 0 else float('inf')):.2f} | {share:.2f} |")
+    return "\n".join(out)
