@@ -1,6 +1,6 @@
 """A Linear of the trunk on packed rows as a differentiable torch function:
 
-    packed_linear(x, weight, bias, gelu=False, rows=None) -> y = act(x weight^T + bias)
+    packed_linear(x, weight, bias, gelu=False, rows=None, weight16=None) -> y = act(x weight^T + bias)
 
 x is a CUDA fp16 tensor [M, K], weight the fp32 master [N, K] (rounded to fp16 inside, as apex O1's cast does), bias fp32 [N]; N and K are
 multiples of 64. rows is an optional int32 device scalar tensor, the forward's m_dev: only the first rows[0] rows are valid, the others are
@@ -9,7 +9,8 @@ epilogue 0, or 1 with gelu): the output bits are the encoder's. The backward is 
 csrc/mdr_linear_grad.inl lists its rounding points): dx fp16, dweight and dbias fp32, no atomics, two runs give the same bits. With gelu the
 backward first recomputes the pre-activation u = fp16(x weight^T + bias) with epilogue 0 into a temporary -- one more forward GEMM instead of
 M x N fp16 kept alive per layer. Both directions are enqueued on the current stream and never synchronise. There is no
-dropout and no CPU fallback.
+dropout and no CPU fallback. weight16, when given, is the caller's fp16 copy of weight (same shape and device; optim.FusedAdam keeps one
+current): the forward and the saved tensor use it in place of the cast inside, and the gradient still goes to weight.
 """
 import ctypes
 
@@ -118,9 +119,9 @@ def _forward_gemm(x, w16, bias, rows, epilogue):
 
 class _PackedLinear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, gelu, rows):
+    def forward(ctx, x, weight, bias, gelu, rows, weight16=None):
         xd = x.detach()
-        w16 = weight.detach().to(dtype=torch.float16).contiguous()
+        w16 = weight.detach().to(dtype=torch.float16).contiguous() if weight16 is None else weight16.detach()
         b32 = bias.detach().contiguous()
         ctx.save_for_backward(xd, w16, b32, rows)
         ctx.gelu = bool(gelu)
@@ -133,22 +134,22 @@ class _PackedLinear(torch.autograd.Function):
         pre = _forward_gemm(x, w16, b32, rows, 0) if ctx.gelu else None
         need_dx, need_dw, need_db = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         if not (need_dx or need_dw or need_db):
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         dw = torch.empty(w16.shape, dtype=torch.float32, device=x.device) if need_dw else None
         db = torch.empty(w16.shape[0], dtype=torch.float32, device=x.device) if need_db else None
         dx, dw, db = linear_backward(x, w16, g, pre, rows, need_dx, dw, db, False)
-        return dx, dw, db, None, None
+        return dx, dw, db, None, None, None
 
 
-def packed_linear(x, weight, bias, gelu=False, rows=None):
+def packed_linear(x, weight, bias, gelu=False, rows=None, weight16=None):
     """act(x weight^T + bias) on packed rows through the encoder's GEMM, differentiable with respect to x, weight and bias (module docstring)."""
     if not (torch.is_tensor(weight) and weight.dim() == 2):
         raise ValueError("weight must be a 2-d tensor")
     N, K = int(weight.shape[0]), int(weight.shape[1])
-    _check_operands(x, None, N, K)
+    _check_operands(x, weight16, N, K)
     if weight.dtype != torch.float32 or weight.device != x.device:
         raise ValueError(f"weight must be the fp32 master [{N}, {K}] on x's device, got {weight.dtype} {tuple(weight.shape)} on {weight.device}")
     if not (torch.is_tensor(bias) and bias.dtype == torch.float32 and bias.device == x.device and tuple(bias.shape) == (N,)):
         raise ValueError(f"bias must be an fp32 [{N}] tensor on x's device, got {getattr(bias, 'dtype', None)} {tuple(getattr(bias, 'shape', ()))}")
     _check_rows(rows, x)
-    return _PackedLinear.apply(x, weight, bias, bool(gelu), rows)
+    return _PackedLinear.apply(x, weight, bias, bool(gelu), rows, weight16)
