@@ -120,7 +120,7 @@ def reference_and_bound(qkv, dctx, cu, heads, mode=0):
     return ref, bnd
 
 
-def _one_sequence(Q, K, V, dO):
+def _one_sequence(Q, K, V, dO, feed=False):
     """(the three gradients, their three bounds) of one sequence: torch float64 [heads, n, 64] in, numpy out."""
     def amax(x):
         return x.amax(dim=2, keepdim=True)
@@ -168,7 +168,28 @@ def _one_sequence(Q, K, V, dO):
                    (p.transpose(1, 2) @ dO, (dp16 + a * (p + dp16)).transpose(1, 2) @ aO)):
         out.append(val.numpy())
         err.append((e + r16(val.abs() + e)).numpy())
+    if feed:  # the fp16 rounding point of dS: the least and the largest magnitude the device's fp32 dS_ij can have in front of it
+        return out, err, [[x.amax(dim=2, keepdim=True).expand(-1, -1, 64).numpy(), x.amax(dim=1).unsqueeze(2).expand(-1, -1, 64).numpy(),
+                           torch.zeros_like(K).numpy()] for x in (adS - d32, adS + d32)]
     return out, err
+
+
+def ds_feed(qkv, dctx, cu, heads, mode=0):
+    """(lo, hi): float64 [T, 3 * hidden] each, in the outputs' layout. For every dQ | dK element the largest |dS_ij| among the dS that feed it (dQ
+    row i: over the keys j; dK row j: over the queries i), less (lo) and plus (hi) the bound d32 of the fp32 dS: with dctx multiplied by a power
+    of two s, the fp16 rounding of a dS that feeds the element CERTAINLY overflows if s lo >= 65520 and POSSIBLY if s hi >= 65520. dV is fed
+    by p and dO alone and p <= 1 never leaves fp16: 0 there. (tests/overflow_ref.py)"""
+    T = int(cu[-1])
+    lo, hi = np.zeros((T, 3 * 64 * heads)), np.zeros((T, 3 * 64 * heads))
+    for b in range(len(cu) - 1):
+        if cu[b + 1] == cu[b]:
+            continue
+        Qs, Ks, Vs = (torch.from_numpy(x.astype(np.float64)) for x in split(qkv, cu, heads, b))
+        dOs = torch.from_numpy(split_do(dctx, cu, heads, b, mode).astype(np.float64))
+        _, _, (l, h) = _one_sequence(Qs[:, :1] if mode == 3 else Qs, Ks, Vs, dOs, feed=True)
+        _store(lo, cu, b, heads, *l)
+        _store(hi, cu, b, heads, *h)
+    return lo, hi
 
 
 def reference(qkv, dctx, cu, heads, mode=0):

@@ -1,0 +1,151 @@
+"""The device side that tests/test_encoder_chain_gpu.py and tests/test_overflow_chain_gpu.py share: the retriever encoder as ONE chain of the
+package's differentiable functions (Chain, with a tape of every call and a hook on every output), its leaves (params), the NaN seeding of the
+caching allocator (poison), the bit comparisons, and criterion E's assertion (check_e). The host side is tests/encoder_chain_ref.py."""
+import ctypes
+import functools
+
+import numpy as np
+import torch
+
+import encoder_chain_ref as ch
+
+GEOM = ch.GEOM
+H, NH, F, EPS, PAD = GEOM["hidden"], GEOM["heads"], GEOM["ffn"], GEOM["ln_eps"], GEOM["pad_id"]
+E_ = "encoder.embeddings."
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _np(t):
+    return None if t is None else t.detach().cpu().numpy()
+
+
+def _ibits(t):
+    t = t.detach().contiguous()
+    return t.view({2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and bool(torch.equal(_ibits(a), _ibits(b)))
+
+
+def params():
+    sd = ch.state_dict()
+    return {k: torch.from_numpy(v).cuda().requires_grad_(True) for k, v in sd.items()}
+
+
+def poison(mib=64):
+    """allocate, fill with NaN bit patterns and free blocks of the sizes the chain's torch.empty calls ask for (and many more): the caching
+    allocator hands them out again, so a read of an unwritten row shows as a NaN. Nothing here can fault."""
+    held, total = [], 0
+    rows = (1280, 640, 288, 192, 8, 6, 4)
+    shapes = [(r, c) for r in rows for c in (H, 3 * H, F)] + [(H, H), (3 * H, H), (F, H), (H, F), (GEOM["vocab"], H), (GEOM["max_pos"], H), (H,), (3 * H,), (F,)]
+    while total < mib << 20:
+        for s in shapes:
+            held.append(torch.full(s, float("nan"), dtype=torch.float16, device="cuda"))
+            held.append(torch.full(s, float("nan"), dtype=torch.float32, device="cuda"))
+            total += 6 * int(np.prod(s))
+        for n in (512, 4096, 65536, 1 << 20, 4 << 20):
+            held.append(torch.full((n,), 0xFF, dtype=torch.uint8, device="cuda"))
+            total += n
+    torch.cuda.synchronize()
+    del held
+
+
+class Chain:
+    """one encode through the public functions, with a tape of every call and hooks on every output. half: None, or a function from a weight
+    leaf to the fp16 copy that every Linear is handed as weight16 (optim.FusedAdam.half)"""
+
+    def __init__(self, P, ids, mask, half=None):
+        from multihop_dense_retrieval_amd import _lib
+        from multihop_dense_retrieval_amd.attention import packed_self_attention
+        from multihop_dense_retrieval_amd.embedding import packed_embedding_layer_norm
+        from multihop_dense_retrieval_amd.layernorm import packed_layer_norm
+        from multihop_dense_retrieval_amd.linear import packed_linear
+        self.tape, self.P = [], P
+        self.ids_np, self.mask_np = ids, mask
+        B, L = ids.shape
+        self.B, self.L, self.cap = B, L, B * L
+        tids, tmask = torch.from_numpy(ids).cuda(), torch.from_numpy(mask).cuda()
+        i32 = lambda n: torch.zeros(n, dtype=torch.int32, device="cuda")  # noqa: E731
+        lens, cu, total, order, src, pid = i32(B), i32(B + 1), i32(1), i32(B), i32(self.cap), i32(self.cap)
+        _lib.check(_lib.lib().mdr_test_pack(_p(tids), _p(tmask), B, L, PAD, _p(lens), _p(cu), _p(total), _p(order), _p(src), _p(pid), 0, _lib.current_stream_ptr()))
+        self.ids, self.cu, self.total, self.src, self.pid = tids, cu, total, src, pid
+        self.T = int(mask.sum())
+        self.starts = torch.from_numpy(np.concatenate([[0], np.cumsum(mask.sum(1))[:-1]]).astype(np.int64)).cuda()
+
+        def linear(x, names, gelu=False, rows=None, label=""):
+            w = P[names[0] + ".weight"] if len(names) == 1 else torch.cat([P[n + ".weight"] for n in names])
+            b = P[names[0] + ".bias"] if len(names) == 1 else torch.cat([P[n + ".bias"] for n in names])
+            if half is None:
+                y = packed_linear(x, w, b, gelu, rows)
+            else:
+                w16 = half(P[names[0] + ".weight"]) if len(names) == 1 else torch.cat([half(P[n + ".weight"]) for n in names])
+                y = packed_linear(x, w, b, gelu, rows, w16)
+            self._rec("linear", label, {"x": x}, {"y": y}, w=w, b=b, gelu=gelu, rows=rows, names=names)
+            return y
+
+        def ln(x, res, name, rows=None, label=""):
+            y16, y32 = packed_layer_norm(x, res, P[name + ".weight"], P[name + ".bias"], EPS, rows, True)
+            self._rec("ln", label, {"x": x, "res": res}, {"y16": y16, "y32": y32}, rows=rows, name_=name)
+            return y16, y32
+
+        def attn(qkv, cls_only, label):
+            ctx = packed_self_attention(qkv, cu, NH, L, cls_only)
+            self._rec("attn", label, {"qkv": qkv}, {"ctx": ctx}, mode=3 if cls_only else 0)
+            return ctx
+
+        def tail(p, ctx, res32, rows, lab):
+            a16, a32 = ln(linear(ctx, [p + "attention.output.dense"], False, rows, lab + ".ao"), res32, p + "attention.output.LayerNorm", rows, lab + ".ln1")
+            f2 = linear(linear(a16, [p + "intermediate.dense"], True, rows, lab + ".ff1"), [p + "output.dense"], False, rows, lab + ".ff2")
+            return ln(f2, a32, p + "output.LayerNorm", rows, lab + ".ln2")
+
+        h16, h32 = packed_embedding_layer_norm(tids, src, pid, total, P[E_ + "word_embeddings.weight"], P[E_ + "position_embeddings.weight"],
+                                               P[E_ + "token_type_embeddings.weight"][0], P[E_ + "LayerNorm.weight"], P[E_ + "LayerNorm.bias"], EPS,
+                                               self.cap, PAD, True)
+        self._rec("emb", "emb", {}, {"y16": h16, "y32": h32})
+        nl = GEOM["layers"]
+        for i in range(nl):
+            p, lab = f"encoder.encoder.layer.{i}.", f"L{i}"
+            qkv = linear(h16, [p + "attention.self." + n for n in ("query", "key", "value")], False, total, lab + ".qkv")
+            if i < nl - 1:
+                h16, h32 = tail(p, attn(qkv, False, lab + ".attn"), h32, total, lab)
+            else:  # the CLS rows alone; their fp16 copy (h16[starts]) has no consumer in this mode
+                cls32 = h32[self.starts]
+                self._rec("gather", lab + ".cls", {"src32": h32}, {"cls32": cls32})
+                h16, h32 = tail(p, attn(qkv, True, lab + ".attn"), cls32, None, lab)
+        y = linear(h16, ["project.0"], False, None, "project.0")
+        out16, out = packed_layer_norm(y, None, P["project.1.weight"], P["project.1.bias"], EPS, None, True)
+        self._rec("ln", "project.1", {"x": y, "res": None}, {"y16": out16, "y32": out}, rows=None, name_="project.1")
+        self.out = out
+
+    def _rec(self, kind, label, ins, outs, **extra):
+        rec = dict(kind=kind, label=label, ins=ins, outs=outs, g={}, **extra)
+        for k, t in outs.items():
+            if t is not None and t.requires_grad:
+                t.register_hook(functools.partial(self._store, rec, k))
+        self.tape.append(rec)
+
+    @staticmethod
+    def _store(rec, key, g):
+        if g is not None:  # (an unused output of a two-output function: autograd passes None, nothing is materialised)
+            rec["g"][key] = g.detach().clone()
+
+
+def grads_np(P, scale=1.0):
+    return {k: v.grad.detach().cpu().numpy().astype(np.float64) / scale for k, v in P.items()}
+
+
+def check_e(g_dev, g_reg, g64, batches, title):
+    rows, e_pool = ch.criterion_e(g_dev, g_reg, g64)
+    print(ch.table(rows, e_pool, "E " + title))
+    print(f"E {title}: worst share of the bar {max(r[4] for r in rows):.3f}, worst e_dev / e_reg "
+          f"{max(r[1] / r[2] for r in rows if r[2] > 0):.3f}")
+    zr = ch.zero_rows(batches)
+    w = E_ + "word_embeddings.weight"
+    assert zr.any() and not g_dev[w][zr].any() and not g64[w][zr].any(), "a word row that owns no token (or padding_idx's) has a gradient"
+    for k in ch.zero_grad_names():
+        print(f"E {title}: {k} max |g_dev| {np.abs(g_dev[k]).max():.3e} (mathematically zero; the query bias's {np.abs(g_dev[k.replace('key', 'query')]).max():.3e})")
+    assert not ch.failures(rows), [(r[0], round(r[4], 3)) for r in ch.failures(rows)]

@@ -96,30 +96,49 @@ def _h(t):
     return t.to(torch.float16).to(t.dtype)
 
 
+GRAD_PEAKS = None  # a dict while record_grad_peaks() is open: {label of a gradient-rounding point: the largest |g| it was handed, before rounding}
+
+
+class record_grad_peaks:
+    """with record_grad_peaks() as peaks: ... -- every gradient-rounding point of the regime notes the largest magnitude it is handed BEFORE it
+    rounds it to fp16 (tests/overflow_ref.py predicts from it which loss scales overflow). Nothing is recorded outside the block."""
+
+    def __enter__(self):
+        global GRAD_PEAKS
+        GRAD_PEAKS = {}
+        return GRAD_PEAKS
+
+    def __exit__(self, *exc):
+        global GRAD_PEAKS
+        GRAD_PEAKS = None
+
+
 class _Round(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, value, grad):
-        ctx.grad = grad
+    def forward(ctx, x, value, grad, label):
+        ctx.grad, ctx.label = grad, label
         return _h(x) if value else x.clone()
 
     @staticmethod
     def backward(ctx, g):
-        return (_h(g) if ctx.grad else g), None, None
+        if ctx.grad and GRAD_PEAKS is not None and g.numel():
+            GRAD_PEAKS[ctx.label] = max(GRAD_PEAKS.get(ctx.label, 0.0), float(g.detach().abs().max()))
+        return (_h(g) if ctx.grad else g), None, None, None
 
 
-def R(x):
+def R(x, label="?"):
     """a tensor the device holds in fp16: its value and its gradient are rounded"""
-    return _Round.apply(x, True, True)
+    return _Round.apply(x, True, True, label)
 
 
 def Rv(x):
     """an fp16 operand made from an fp32 tensor whose gradient stays fp32 (a weight, P)"""
-    return _Round.apply(x, True, False)
+    return _Round.apply(x, True, False, None)
 
 
-def Rg(x):
+def Rg(x, label="?"):
     """an fp32 value whose gradient the device rounds to fp16 (the scores, the GELU's pre-activation)"""
-    return _Round.apply(x, False, True)
+    return _Round.apply(x, False, True, label)
 
 
 def _gelu(z):
@@ -169,12 +188,12 @@ def regime_encode(W, geom, ids, mask, mutation=None):
     e = "encoder.embeddings."
     x = (W[e + "word_embeddings.weight"][ids] + W[e + "position_embeddings.weight"][pos]) + W[e + "token_type_embeddings.weight"][0]
     h32 = ln(x, W[e + "LayerNorm.weight"], W[e + "LayerNorm.bias"], eps)
-    h16 = R(h32)
+    h16 = R(h32, "emb.y16")
     add_mask = ((1.0 - mask.to(dtype)) * -10000.0)[:, None, None, :]
 
     def linear(t, name, gelu=False):
-        z = R(t) @ Rv(W[name + ".weight"]).T + W[name + ".bias"]
-        return R(_GeluAt.apply(Rg(z), mutation == "gelu_grad_at_output")) if gelu else R(z)
+        z = R(t, name + ":x") @ Rv(W[name + ".weight"]).T + W[name + ".bias"]
+        return R(_GeluAt.apply(Rg(z, name + ":dZ"), mutation == "gelu_grad_at_output"), name + ":y") if gelu else R(z, name + ":y")
 
     def heads(t):
         return t.reshape(B, -1, nh, hd).permute(0, 2, 1, 3)
@@ -182,10 +201,10 @@ def regime_encode(W, geom, ids, mask, mutation=None):
     def tail(p, ctx, h32, first):
         res = h32.detach() if (mutation == "res_dropped_ln1" and first) else h32
         a32 = ln(linear(ctx, p + "attention.output.dense") + res, W[p + "attention.output.LayerNorm.weight"], W[p + "attention.output.LayerNorm.bias"], eps)
-        f = linear(linear(R(a32), p + "intermediate.dense", True), p + "output.dense")
+        f = linear(linear(R(a32, p + "attention.output.LayerNorm:y16"), p + "intermediate.dense", True), p + "output.dense")
         res = a32.detach() if (mutation == "res_dropped_ln2" and first) or (mutation == "dy2_dropped" and not first) else a32
         o32 = ln(f + res, W[p + "output.LayerNorm.weight"], W[p + "output.LayerNorm.bias"], eps)
-        return R(o32), o32
+        return R(o32, p + "output.LayerNorm:y16"), o32
 
     for i in range(nl):
         p = f"encoder.encoder.layer.{i}."
@@ -193,8 +212,8 @@ def regime_encode(W, geom, ids, mask, mutation=None):
         q, k, v = (heads(linear(h16, p + "attention.self." + n)) for n in ("query", "key", "value"))
         if last:  # the query, the attention and the tail of the CLS rows alone
             q = q[:, :, :1]
-        s = Rg(q @ k.transpose(-1, -2) / math.sqrt(hd) + add_mask)
-        ctx = R(Rv(torch.softmax(s, -1)) @ v).permute(0, 2, 1, 3).reshape(B, -1, H)
+        s = Rg(q @ k.transpose(-1, -2) / math.sqrt(hd) + add_mask, p + "attention:dS")
+        ctx = R(Rv(torch.softmax(s, -1)) @ v, p + "attention:ctx").permute(0, 2, 1, 3).reshape(B, -1, H)
         if last:
             cls32 = h32[:, 0]
             h16, h32 = tail(p, ctx[:, 0], cls32.detach() if mutation == "cls_rows_not_added" else cls32, False)
@@ -227,7 +246,8 @@ def loss64(o):
 def loss_regime(o):
     """mode O1 of tests/mhop_loss_ref.py: fp16 operands, fp16 scores, g rounded to fp16, every contraction's backward result rounded to fp16 per
     call, the terms of one leaf added unrounded"""
-    return _loss(o, lambda x, c: R(R(x) @ R(c).T), lambda x, n: R(torch.einsum("bd,bnd->bn", R(x), R(n))))
+    return _loss(o, lambda x, c: R(R(x, "loss:operand") @ R(c, "loss:operand").T, "loss:g"),
+                 lambda x, n: R(torch.einsum("bd,bnd->bn", R(x, "loss:operand"), R(n, "loss:operand")), "loss:g"))
 
 
 # ---- gradients -----------------------------------------------------------------------------------------------------------------------------

@@ -39,9 +39,11 @@ def h16(x):
         return np.asarray(x, np.float64).astype(np.float16).astype(np.float64)
 
 
-def loss_and_grads(inp, queue=None, g0=1.0, o1=False, mutate=None):
+def loss_and_grads(inp, queue=None, g0=1.0, o1=False, mutate=None, record=None):
     """inp: the six [B, d] matrices by name; queue [K, d] or None. Returns {"loss", "grads": {name: [B, d]}, "loss_bound", "bounds": {name: [B, d]}}.
-    `mutate` (one of MUTATIONS) states a WRONG formula: what the bound must reject."""
+    `mutate` (one of MUTATIONS) states a WRONG formula: what the bound must reject.
+    `record` (a dict, mode O1; tests/overflow_ref.py): filled with what the gradient's fp16 rounding points are HANDED, value and error in front
+    of the rounding: "g" -> per hop (g [B, N], dg), and per leaf name the list of (t [B, d], e) of the contraction results added into it."""
     assert mutate is None or mutate in MUTATIONS, mutate
     r = h16 if o1 else (lambda x: np.asarray(x, np.float64))
     X = [r(inp["q"]), r(inp["q_sp1"])]
@@ -54,7 +56,10 @@ def loss_and_grads(inp, queue=None, g0=1.0, o1=False, mutate=None):
     scale = float(g0) * (1.0 if mutate == "no_inv_b" else 1.0 / B)
     rows = np.arange(B)
 
-    def rt(t, e):  # the rounding of one contraction's result, and what it does to the error
+    def rt(t, e, leaves=()):  # the rounding of one contraction's result, and what it does to the error
+        if record is not None:
+            for name, pick in leaves:
+                record.setdefault(name, []).append((t[pick], e[pick]))
         return (h16(t), np.maximum(h16(t + e) - h16(t - e), 0.0)) if o1 else (t, e + U32 * np.abs(t))
 
     loss, loss_bound = 0.0, 0.0
@@ -92,6 +97,8 @@ def loss_and_grads(inp, queue=None, g0=1.0, o1=False, mutate=None):
             g = np.where(mask, 0.0, (p - onehot) * scale)
             dg = abs(scale) * (1.01 * p * rp + 4 * U32 * np.abs(p - onehot))
             dg = np.where(mask, 0.0, dg)
+            if record is not None:
+                record.setdefault("g", []).append((g, dg))
             if o1:
                 g, dg = h16(g), np.maximum(h16(g + dg) - h16(g - dg), 0.0)
             tgt = s[rows, t]
@@ -101,17 +108,19 @@ def loss_and_grads(inp, queue=None, g0=1.0, o1=False, mutate=None):
             ag = np.abs(g)
             gc, gn, gq = g[:, :2 * B], g[:, 2 * B:2 * B + 2], g[:, 2 * B + 2:]
             ec, en, eq = dg[:, :2 * B], dg[:, 2 * B:2 * B + 2], dg[:, 2 * B + 2:]
-            terms = [rt(gc @ C, ec @ np.abs(C) + (2 * B + 2) * U32 * (ag[:, :2 * B] @ np.abs(C))),
-                     rt(np.einsum("bn,bnd->bd", gn, NG), np.einsum("bn,bnd->bd", en + 4 * U32 * np.abs(gn), np.abs(NG)))]
+            own = [(("q", "q_sp1")[h], slice(None))]
+            terms = [rt(gc @ C, ec @ np.abs(C) + (2 * B + 2) * U32 * (ag[:, :2 * B] @ np.abs(C)), own),
+                     rt(np.einsum("bn,bnd->bd", gn, NG), np.einsum("bn,bnd->bd", en + 4 * U32 * np.abs(gn), np.abs(NG)), own)]
             if K:
-                terms.append(rt(gq @ QU, eq @ np.abs(QU) + (K + 2) * U32 * (ag[:, 2 * B + 2:] @ np.abs(QU))))
+                terms.append(rt(gq @ QU, eq @ np.abs(QU) + (K + 2) * U32 * (ag[:, 2 * B + 2:] @ np.abs(QU)), own))
             dx.append(sum(t_ for t_, _ in terms))
             bx.append(sum(e_ for _, e_ in terms) + 4 * U32 * sum(np.abs(t_) for t_, _ in terms))
             if not (h == 1 and mutate == "dctx_no_hop2"):
-                t_, e_ = rt(gc.T @ x, ec.T @ np.abs(x) + (B + 2) * U32 * (ag[:, :2 * B].T @ np.abs(x)))
+                t_, e_ = rt(gc.T @ x, ec.T @ np.abs(x) + (B + 2) * U32 * (ag[:, :2 * B].T @ np.abs(x)), [("c1", slice(0, B)), ("c2", slice(B, 2 * B))])
                 dctx += t_
                 bctx += e_ + 4 * U32 * np.abs(t_)
-            t_, e_ = rt(gn[:, :, None] * x[:, None, :], (en + 4 * U32 * np.abs(gn))[:, :, None] * np.abs(x)[:, None, :])
+            t_, e_ = rt(gn[:, :, None] * x[:, None, :], (en + 4 * U32 * np.abs(gn))[:, :, None] * np.abs(x)[:, None, :],
+                        [("neg_1", (slice(None), 0)), ("neg_2", (slice(None), 1))])
             dneg += t_
             bneg += e_ + 4 * U32 * np.abs(t_)
     if mutate == "swap_dneg":

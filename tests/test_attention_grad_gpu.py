@@ -185,6 +185,49 @@ def test_non_finite_gradients_stay_in_their_sequence(mode):
         if b != victim:
             assert np.array_equal(bits(got[int(cu[b]):int(cu[b + 1])]), bits(clean[int(cu[b]):int(cu[b + 1])])), b
     assert not np.isfinite(got[int(cu[victim]):int(cu[victim + 1])].astype(np.float32)).all()
+    # delivered and contained, per sequence and per head. The whole block of one head's dO in one sequence is +Inf, -Inf or NaN
+    # (mode 3: the first query's row, the only one there is). Every query i of that head then has a non-finite dP_ij = dO_i . V_j and delta_i,
+    # so dS_ij is non-finite for every key j -- also where P_ij has underflowed, 0 * Inf being NaN -- and with it dQ_i = sum_j dS_ij K_j,
+    # dK_j = sum_i dS_ij Q_i and dV_j = sum_i P_ij dO_i: EVERY dQ, dK and dV element of that head in that sequence (mode 3: dQ of the first query;
+    # the other queries' dQ rows keep the clean run's bits). The other head of the sequence and every other sequence keep their bits.
+    heads, lens = 2, [1, 64, 65, 130]
+    L, hidden = max(lens), 64 * heads
+    qkv, cu = ao.realistic(lens, heads, 24, 1.0)
+    dctx = dctx_for(cu, heads, mode, 9)
+    clean = run(qkv, dctx, cu, heads, L, mode)
+    assert np.isfinite(clean.astype(np.float32)).all()
+    values = [np.inf, -np.inf, np.nan]
+    for victim in range(len(lens)):
+        lo, hi = int(cu[victim]), int(cu[victim + 1])
+        for h in range(heads):
+            v = values[(victim + h) % 3]
+            dirty = dctx.copy()
+            (dirty[victim:victim + 1] if mode == 3 else dirty[lo:hi])[:, 64 * h:64 * (h + 1)] = v
+            got = run(qkv, dirty, cu, heads, L, mode)
+            hit = np.zeros(got.shape, bool)
+            for part in range(3):
+                dq_rows = slice(lo, lo + 1) if (mode == 3 and part == 0) else slice(lo, hi)
+                hit[dq_rows, part * hidden + 64 * h:part * hidden + 64 * (h + 1)] = True
+            assert not np.isfinite(got[hit].astype(np.float32)).any(), (victim, h, v, "an element of the planted head stayed finite")
+            assert np.array_equal(bits(got)[~hit], bits(clean)[~hit]), (victim, h, v, "the other head or another sequence changed")
+    # ONE element dO[i, c] = v, head h = c // 64: dP_ij = dO_i . V_j and delta_i are non-finite for every key j, so row i of dS is -- and no other
+    # row. dQ_i = sum_j dS_ij K_j: every element of dQ row i in head h. dK_j = sum_i dS_ij Q_i has that term for every j: every dK element of head
+    # h in the sequence. dV_jc' = sum_i P_ij dO_ic' meets the element at c' = c alone: column c of every dV row of the sequence (P_ij = 0 gives
+    # 0 * Inf = NaN). Everything else keeps the clean run's bits: a reduction that drops one non-finite partial, or a select that swallows one
+    # NaN among finite terms, fails here and not above.
+    for k, (victim, i, c) in enumerate([(1, 0, 3), (2, 64, 64 + 63), (3, 129, 17), (3, 70, 64), (0, 0, 100)]):
+        lo, hi = int(cu[victim]), int(cu[victim + 1])
+        i, h, v = (0 if mode == 3 else i), c // 64, values[k % 3]
+        assert lo + i < hi
+        dirty = dctx.copy()
+        dirty[victim if mode == 3 else lo + i, c] = v
+        got = run(qkv, dirty, cu, heads, L, mode)
+        hit = np.zeros(got.shape, bool)
+        hit[lo + i, 64 * h:64 * (h + 1)] = True
+        hit[lo:hi, hidden + 64 * h:hidden + 64 * (h + 1)] = True
+        hit[lo:hi, 2 * hidden + c] = True
+        assert not np.isfinite(got[hit].astype(np.float32)).any(), (victim, i, c, v, "an element the planted one feeds stayed finite")
+        assert np.array_equal(bits(got)[~hit], bits(clean)[~hit]), (victim, i, c, v, "an element the planted one does not feed changed")
 
 
 def test_first_query_mode_against_every_query_mode():

@@ -3,7 +3,7 @@ fp64 statement of tests/mhop_loss_ref.py. Every element of the loss and of the s
 accumulation in any order; mode O1: the listed fp16 rounding points applied in the helper, a flipped rounding allowed only where a rounding
 boundary lies within the fp32 accumulation error). Inputs are LayerNorm-like rows scaled so that scores are O(1-10) (mhop_loss_ref.make_inputs).
 Mode O1 runs with a loss scale g0 = 2^12, as an amp run has one: without it g = p / B is below the smallest fp16 number for most columns of the
-queue (2^16, amp's starting value, overflows fp16 at B = 1, where amp would skip the step).
+queue (2^16, amp's starting value, overflows fp16 at B = 1, where amp would skip the step: tests/test_overflow_gpu.py asserts both halves of that).
 """
 import contextlib
 import os
