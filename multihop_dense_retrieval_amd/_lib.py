@@ -109,6 +109,23 @@ def lib():
     return _lib
 
 
+def binder(*tables):
+    """lib() of a module that owns further headers: the loaded library with the signatures of `tables` bound on first use (AttributeError
+    if the library lacks one: no fallback). Each header's table stays in its module; _SIGNATURES stays include/mdr_hip.h's."""
+    bound = []
+
+    def bound_lib():
+        L = lib()
+        if not bound:
+            for table in tables:
+                for name, (res, args) in table.items():
+                    fn = getattr(L, name)
+                    fn.restype, fn.argtypes = res, args
+            bound.append(True)
+        return L
+    return bound_lib
+
+
 def check(code):
     if code != 0:
         raise MdrError(code, lib().mdr_last_error().decode("utf-8", "replace"))
@@ -117,6 +134,44 @@ def check(code):
 def current_stream_ptr(device=None):
     """hipStream_t of torch's current stream as an integer for the `void* stream` arguments."""
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def dev_index(dev):
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def call(fn, *args, dev, device_arg=True):
+    """check(fn(*args, device index, stream)) on dev and torch's current stream there; device_arg=False for the entry points that take a
+    stream alone (include/mdr_inbatch.h)."""
+    with torch.cuda.device(dev):
+        check(fn(*args, *((dev_index(dev),) if device_arg else ()), current_stream_ptr(dev)))
+
+
+def workspace(nbytes, dev):
+    """The uint8 buffer of a *_workspace_bytes answer, None for 0."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+
+
+def is_like(t, dtypes, shape, dev):
+    return torch.is_tensor(t) and t.dtype in dtypes and t.is_contiguous() and t.device == dev and tuple(t.shape) == tuple(shape)
+
+
+def describe(t):
+    return f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}"
+
+
+def check_rows(rows, dev, name="rows", of="x"):
+    if not (torch.is_tensor(rows) and rows.device == dev and rows.dtype == torch.int32 and rows.numel() == 1):
+        raise ValueError(f"{name} must be an int32 tensor of one element on {of}'s device")
+
+
+def check_hidden(H):
+    if H < 64 or H > 1024 or H % 64:
+        raise ValueError(f"H = {H}: must be a multiple of 64, 64 .. 1024")
 
 
 def tensor_table(state_dict, names):

@@ -15,6 +15,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import ptr
 
 _c = ctypes
 # include/mdr_attention_grad.h -- bound here, apart from _lib._SIGNATURES (include/mdr_hip.h's table, pinned by its own test)
@@ -25,23 +26,7 @@ SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 MODE_ALL, MODE_CLS = 0, 3
-_bound = False
-
-
-def lib():
-    """libmdrhip.so with the signatures of include/mdr_attention_grad.h bound (AttributeError if the library lacks one: no fallback)."""
-    global _bound
-    L = _lib.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _bound = True
-    return L
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+lib = _lib.binder(SIGNATURES)  # libmdrhip.so with the signatures of include/mdr_attention_grad.h bound
 
 
 def attention_backward(qkv, dctx, cu, heads, max_len, mode=MODE_ALL, out=None):
@@ -51,11 +36,9 @@ def attention_backward(qkv, dctx, cu, heads, max_len, mode=MODE_ALL, out=None):
     B, hidden = cu.numel() - 1, qkv.shape[1] // 3
     dqkv = torch.empty_like(qkv) if out is None else out
     L = lib()
-    with torch.cuda.device(dev):
-        need = int(L.mdr_attention_backward_workspace_bytes(B, int(max_len), int(heads), int(mode)))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-        _lib.check(L.mdr_attention_backward(_ptr(qkv), _ptr(dctx), _ptr(cu), B, int(max_len), hidden, int(heads), int(mode), _ptr(dqkv), _ptr(ws), need,
-                                            dev.index if dev.index is not None else torch.cuda.current_device(), _lib.current_stream_ptr(dev)))
+    need = int(L.mdr_attention_backward_workspace_bytes(B, int(max_len), int(heads), int(mode)))
+    ws = _lib.workspace(need, dev)
+    _lib.call(L.mdr_attention_backward, ptr(qkv), ptr(dctx), ptr(cu), B, int(max_len), hidden, int(heads), int(mode), ptr(dqkv), ptr(ws), need, dev=dev)
     return dqkv
 
 
@@ -66,9 +49,7 @@ class _PackedSelfAttention(torch.autograd.Function):
         B, hidden = cu.numel() - 1, qkv.shape[1] // 3
         q = qkv.detach()
         out = torch.empty((B if cls_only else q.shape[0], hidden), dtype=torch.float16, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().mdr_test_attention(_ptr(q), _ptr(cu), None, B, int(max_len), hidden, int(heads), 3 if cls_only else 0, _ptr(out),
-                                                     dev.index if dev.index is not None else torch.cuda.current_device(), _lib.current_stream_ptr(dev)))
+        _lib.call(_lib.lib().mdr_test_attention, ptr(q), ptr(cu), None, B, int(max_len), hidden, int(heads), 3 if cls_only else 0, ptr(out), dev=dev)
         ctx.save_for_backward(q, cu)
         ctx.heads, ctx.max_len, ctx.mode = int(heads), int(max_len), MODE_CLS if cls_only else MODE_ALL
         return out

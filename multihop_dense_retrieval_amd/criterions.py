@@ -50,20 +50,8 @@ LOSS_SIGNATURES = {
     "mdr_inbatch_loss_backward": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int64, _c.c_int, _c.c_int, _c.c_int] + [_c.c_void_p] * 8 + [_c.c_size_t, _c.c_void_p]),
 }
 LOSS_EXPORTED_SYMBOLS = tuple(LOSS_SIGNATURES)
-_bound = False
-
-
-def lib():
-    """libmdrhip.so with the signatures of include/mdr_inbatch.h and include/mdr_inbatch_loss.h bound (AttributeError if the library lacks one: no
-    fallback)."""
-    global _bound
-    L = _lib.lib()
-    if not _bound:
-        for name, (res, args) in {**SIGNATURES, **LOSS_SIGNATURES}.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _bound = True
-    return L
+lib = _lib.binder(SIGNATURES, LOSS_SIGNATURES)  # libmdrhip.so with include/mdr_inbatch.h and include/mdr_inbatch_loss.h bound
+_ptr = _lib.ptr
 
 
 def inbatch_rank(q, q_sp, c1, c2, neg_1, neg_2, mode):
@@ -81,14 +69,11 @@ def inbatch_rank(q, q_sp, c1, c2, neg_1, neg_2, mode):
         raise ValueError(f"q {tuple(q.shape)}, q_sp {tuple(q_sp.shape)}, [c1; c2] {tuple(ctx.shape)} and the negatives {tuple(neg.shape)} do not fit one batch")
     out = {k: torch.empty(B, dtype=torch.int32, device=dev) for k in ("rank1", "rank2")}
     out.update({k: torch.empty(B, dtype=torch.float32, device=dev) for k in ("tscore1", "tscore2", "lse1", "lse2")})
-    L = lib()
-    with torch.cuda.device(dev):
-        need = int(L.mdr_inbatch_workspace_bytes(B, d, mode))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.check(L.mdr_inbatch_rank(p(q), p(q_sp), p(ctx), p(neg), B, d, int(mode), p(out["rank1"]), p(out["rank2"]), p(out["tscore1"]),
-                                      p(out["tscore2"]), p(out["lse1"]), p(out["lse2"]), p(ws) if ws is not None else None, need,
-                                      _lib.current_stream_ptr(dev)))
+    L, p = lib(), _ptr
+    need = int(L.mdr_inbatch_workspace_bytes(B, d, mode))
+    ws = _lib.workspace(need, dev)
+    _lib.call(L.mdr_inbatch_rank, p(q), p(q_sp), p(ctx), p(neg), B, d, int(mode), p(out["rank1"]), p(out["rank2"]), p(out["tscore1"]), p(out["tscore2"]),
+              p(out["lse1"]), p(out["lse2"]), p(ws), need, dev=dev, device_arg=False)
     return out
 
 
@@ -117,10 +102,6 @@ def mhop_loss_value(outputs, fp16=False):
     return float((ce(s1.float(), t) + ce(s2.float(), t + B)).item())
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class _InbatchLoss(torch.autograd.Function):
     """loss = mean(lse1 - t1) + mean(lse2 - t2) over 2B + 2 + K columns. forward: mdr_inbatch_loss_forward; backward:
     mdr_inbatch_loss_backward with the upstream gradient passed as a device scalar (no synchronisation in either)."""
@@ -142,11 +123,10 @@ class _InbatchLoss(torch.autograd.Function):
         K = int(queue.shape[0]) if queue is not None else 0
         L = lib()
         out = torch.empty(4, B, dtype=torch.float32, device=dev)  # tscore1, tscore2, lse1, lse2
-        with torch.cuda.device(dev):
-            need = int(L.mdr_inbatch_loss_workspace_bytes(B, d, K, int(mode)))
-            ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-            _lib.check(L.mdr_inbatch_loss_forward(_ptr(q), _ptr(q_sp), _ptr(cc), _ptr(neg), _ptr(queue), K, B, d, int(mode), _ptr(out[0]), _ptr(out[1]),
-                                                  _ptr(out[2]), _ptr(out[3]), _ptr(ws), need, _lib.current_stream_ptr(dev)))
+        need = int(L.mdr_inbatch_loss_workspace_bytes(B, d, K, int(mode)))
+        ws = _lib.workspace(need, dev)
+        _lib.call(L.mdr_inbatch_loss_forward, _ptr(q), _ptr(q_sp), _ptr(cc), _ptr(neg), _ptr(queue), K, B, d, int(mode), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                  _ptr(out[3]), _ptr(ws), need, dev=dev, device_arg=False)
         ctx.save_for_backward(q, q_sp, cc, neg, out)
         ctx.queue, ctx.mode, ctx.ws, ctx.need = queue, int(mode), ws, need
         return (out[2] - out[0]).mean() + (out[3] - out[1]).mean()
@@ -160,10 +140,8 @@ class _InbatchLoss(torch.autograd.Function):
         K = int(queue.shape[0]) if queue is not None else 0
         g0 = grad.detach().to(device=dev, dtype=torch.float32).reshape(1).contiguous()
         dq, dqsp, dctx, dneg = torch.empty_like(q), torch.empty_like(q_sp), torch.empty_like(cc), torch.empty_like(neg)
-        with torch.cuda.device(dev):
-            _lib.check(lib().mdr_inbatch_loss_backward(_ptr(q), _ptr(q_sp), _ptr(cc), _ptr(neg), _ptr(queue), K, B, d, ctx.mode, _ptr(out[2]), _ptr(out[3]),
-                                                       _ptr(g0), _ptr(dq), _ptr(dqsp), _ptr(dctx), _ptr(dneg), _ptr(ctx.ws), ctx.need,
-                                                       _lib.current_stream_ptr(dev)))
+        _lib.call(lib().mdr_inbatch_loss_backward, _ptr(q), _ptr(q_sp), _ptr(cc), _ptr(neg), _ptr(queue), K, B, d, ctx.mode, _ptr(out[2]), _ptr(out[3]), _ptr(g0),
+                  _ptr(dq), _ptr(dqsp), _ptr(dctx), _ptr(dneg), _ptr(ctx.ws), ctx.need, dev=dev, device_arg=False)
         return dq, dqsp, dctx[:B], dctx[B:], dneg[:, 0], dneg[:, 1], None, None
 
 

@@ -29,7 +29,7 @@
 //   5. p is rounded to fp16 ONLY as the MFMA operand of dV; dS is rounded to fp16 ONLY as the operand of dQ and dK.
 //   6. dQ, dK, dV accumulate in fp32 (MFMA; mode 3: dQ as fma chains, dK and dV single products); dQ and dK are multiplied by 1/8 (exact)
 //      and every output is rounded to fp16 once.
-#include "mdr_common.h"
+#include "mdr_grad_common.h"
 #include "../../include/mdr_attention_grad.h"
 
 namespace mdr {
@@ -249,12 +249,6 @@ attn_grad_kernel(const _Float16* __restrict__ qkv, const _Float16* __restrict__ 
     }
 }
 
-__device__ __forceinline__ float ag_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // Mode 3: dctx is [B, H], the gradient of each sequence's first query alone.
 __global__ void __launch_bounds__(kAgClsThreads)
 attn_grad_cls_kernel(const _Float16* __restrict__ qkv, const _Float16* __restrict__ dctx, const int* __restrict__ cu, int H, _Float16* __restrict__ dqkv) {
@@ -304,8 +298,8 @@ attn_grad_cls_kernel(const _Float16* __restrict__ qkv, const _Float16* __restric
         sum += e;
         dsum = fmaf(e, dp_s[key], dsum);
     }
-    sum = ag_wave_sum(sum);
-    dsum = ag_wave_sum(dsum);
+    sum = grad_wave_sum(sum);
+    dsum = grad_wave_sum(dsum);
     if (lane == 0) {
         red[1][wave] = sum;
         red[2][wave] = dsum;
@@ -371,14 +365,10 @@ int mdr_attention_backward(const void* qkv_dev, const void* dctx_dev, const int*
     MDR_REQUIRE(L >= 1 && L <= 512, "%s: L=%d out of range (1..512)", fn, L);
     MDR_REQUIRE(heads >= 1 && heads <= 65535 && hidden == 64 * heads, "%s: head dim must be 64 (hidden=%d heads=%d)", fn, hidden, heads);
     MDR_REQUIRE(mode == 0 || mode == 3, "%s: mode must be 0 (every query) or 3 (first query of each sequence), got %d", fn, mode);
-    MDR_REQUIRE((((uintptr_t)qkv_dev | (uintptr_t)dctx_dev | (uintptr_t)dqkv_dev | (uintptr_t)workspace_dev) & 15) == 0,
-                "%s: qkv, dctx, dqkv and the workspace must be 16-byte aligned", fn);
+    MDR_REQUIRE(aligned16({qkv_dev, dctx_dev, dqkv_dev, workspace_dev}), "%s: qkv, dctx, dqkv and the workspace must be 16-byte aligned", fn);
     const size_t need = ag_need(B, L, heads, mode);
-    if (need && !(workspace_dev && workspace_bytes >= need))
-        return set_error(MDR_E_WORKSPACE, "%s: workspace of %zu bytes, need %zu (mdr_attention_backward_workspace_bytes)", fn,
-                         workspace_dev ? workspace_bytes : (size_t)0, need);
-    DeviceGuard guard(device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    MDR_REQUIRE_WORKSPACE(fn, workspace_dev, workspace_bytes, need, "mdr_attention_backward_workspace_bytes");
+    MDR_ENTER_DEVICE(device);
     const _Float16* qkv = (const _Float16*)qkv_dev;
     const _Float16* dctx = (const _Float16*)dctx_dev;
     _Float16* dqkv = (_Float16*)dqkv_dev;

@@ -14,11 +14,12 @@
 // emb_scatter_kernel: a workgroup of eight waves owns a segment (a grid-stride loop over the segments of one table). A wave owns a piece
 //   of P tokens: lane l holds columns l + 64 i and adds the piece's d rows from 0 in token order. The pieces go through LDS eight at a
 //   time and thread e adds them from 0 in ascending piece order. The old value enters last. accumulate = 0: the table is zeroed on the stream first, then the same kernel writes the rows that own a segment.
-// emb_ln_grad_kernel: the rows are cut into S chunks (eg_chunks: a function of (cap, H) alone); one workgroup of four waves owns a chunk,
+// emb_ln_grad_kernel: the rows are cut into S chunks (grad_row_chunks: a function of (cap, H) alone); one workgroup of four waves owns a chunk,
 //   a wave a token, with the forward's columns l + 64 i at every H. Wave w walks tokens w, w + 4, ... of the chunk in order, writes d of
 //   each and keeps its lanes' dg, db and dtype0 columns in registers; the four waves' columns are added through LDS in wave order and go
 //   to the workspace [S][3][H]. emb_colsum_kernel does the same for dtype0 alone from a given d ([S][1][H]): mdr_embedding_scatter.
-// emb_reduce_kernel: strand j of sixteen adds chunks j, j + 16, ... in order, the min(S, 16) strands are added in order, then the old value.
+// grad_strand_reduce_kernel (csrc/mdr_layernorm_grad.hip, through launch_strand_reduce of csrc/mdr_grad_common.h): strand j of sixteen adds
+//   chunks j, j + 16, ... in order, the min(S, 16) strands are added in order, then the old value.
 // Every output element has one owner and one summation order: no floating-point atomics, two runs give the same bits.
 //
 // Rounding points (tests/embedding_grad_ref.py derives its bound from this list; every operation is fp32, and a multiply feeding an add
@@ -37,9 +38,8 @@
 // Non-finite values propagate by IEEE rules alone: nothing float is clamped, compared or used as an index.
 #include <algorithm>
 #include <climits>
-#include <initializer_list>
 
-#include "mdr_common.h"
+#include "mdr_grad_common.h"
 #include "../../include/mdr_embedding_grad.h"
 
 namespace mdr {
@@ -50,7 +50,7 @@ typedef int eg_int4 __attribute__((ext_vector_type(4)));
 constexpr int kEgMaxCap = 1 << 20;
 constexpr int kEgMaxVocab = 1 << 20;
 constexpr int kEgMaxPos = 1 << 16;
-constexpr int kEgMaxH = 1024;
+constexpr int kEgMaxH = kGradMaxH;
 constexpr int kEgPerLane = kEgMaxH / 64;
 constexpr int kEgWaves = 4;
 constexpr int kEgThreads = 64 * kEgWaves;
@@ -62,9 +62,7 @@ constexpr int kEgSegThreads = 1024;
 constexpr int kEgScatterWaves = 8;                      // pieces of a segment summed side by side
 constexpr int kEgScatterThreads = 64 * kEgScatterWaves;
 constexpr int kEgScatterGrid = 1 << 16;                 // most workgroups of emb_scatter_kernel per table
-constexpr int kEgStrands = 16;
-constexpr int kEgMaxChunks = 1024;                      // target number of workgroups ...
-constexpr size_t kEgMaxPartialBytes = (size_t)4 << 20;  // ... as far as the partial sums [S][3][H] stay within 4 MiB
+constexpr int kEgPlanes = 3;                            // dg, db, dtype0: the partial sums are [S][3][H] (the scatter's [S][1][H] uses the same split)
 
 enum { kHdrMagic = 0, kHdrTotal, kHdrSegWord, kHdrSegPos, kHdrCap, kHdrVocab, kHdrMaxPos, kHdrPadRow };
 
@@ -73,22 +71,7 @@ __host__ __device__ inline int eg_table_off(int cap, int tbl) { return kEgHeader
 __host__ __device__ inline int eg_keys_off(int cap, int tbl) { return kEgHeader + 2 * eg_table_stride(cap) + tbl * cap; }
 inline size_t eg_plan_words(int cap) { return (size_t)kEgHeader + 2 * (size_t)eg_table_stride(cap) + 2 * (size_t)cap; }
 
-bool eg_hidden_ok(int H) { return H >= 64 && H <= kEgMaxH && H % 64 == 0; }
 bool eg_cap_ok(int cap) { return cap >= 1 && cap <= kEgMaxCap; }
-
-// (S, rows per chunk) of a shape inside the limits (lg_chunks of csrc/mdr_layernorm_grad.hip with three planes of partial sums)
-int eg_chunks(int M, int H, int* rpc_out) {
-    const int most = (int)std::min<size_t>(kEgMaxChunks, kEgMaxPartialBytes / (3 * sizeof(float) * (size_t)H));
-    const int rpc = ((M + most - 1) / most + 3) / 4 * 4;
-    *rpc_out = rpc;
-    return (M + rpc - 1) / rpc;
-}
-
-__device__ __forceinline__ float eg_wave_sum(float v) {  // (wave_sum of csrc/mdr_encoder_pack_ln.inl)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __device__ __forceinline__ int eg_total(const int* __restrict__ total, int cap) { return min(max(*total, 0), cap); }
 
@@ -340,12 +323,12 @@ emb_ln_grad_kernel(const long long* __restrict__ ids, const int* __restrict__ to
                     dy[i] = dy2_f32 ? ((const float*)dy2)[off + e] : (float)((const _Float16*)dy2)[off + e];
                 }
             }
-        const float mu = eg_wave_sum(s) / H;
+        const float mu = grad_wave_sum(s) / H;
         float v = 0.f;
 #pragma unroll
         for (int i = 0; i < kEgPerLane; ++i)
             if (i < nl) { const float dlt = x[i] - mu; v += dlt * dlt; }
-        const float rstd = rsqrtf(eg_wave_sum(v) / H + eps);
+        const float rstd = rsqrtf(grad_wave_sum(v) / H + eps);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int i = 0; i < kEgPerLane; ++i)
@@ -359,7 +342,7 @@ emb_ln_grad_kernel(const long long* __restrict__ ids, const int* __restrict__ to
                 x[i] = xh;
                 dy[i] = a;
             }
-        const float c1 = eg_wave_sum(s1) / H, c2 = eg_wave_sum(s2) / H;
+        const float c1 = grad_wave_sum(s1) / H, c2 = grad_wave_sum(s2) / H;
 #pragma unroll
         for (int i = 0; i < kEgPerLane; ++i)
             if (i < nl) {
@@ -388,33 +371,6 @@ emb_colsum_kernel(const float* __restrict__ d32, const int* __restrict__ plan, i
             if (i < nl) sums[0][i] += r[64 * i];
     }
     eg_store_partials<1>(red, sums, nl, H, part);
-}
-
-// part [S][NP][H] -> the NP outputs. A workgroup owns 64 columns of one plane, a wave is a strand.
-__global__ void __launch_bounds__(64 * kEgStrands)
-emb_reduce_kernel(const float* __restrict__ part, int S, int NP, int H, float* o0, float* o1, float* o2, int accumulate) {
-    __shared__ float st[kEgStrands][64];
-    const int col = threadIdx.x & 63, strand = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + col;  // < NP H: the grid is NP H / 64 workgroups
-    const int pl = i / H, e = i - pl * H;  // (pl is uniform over the workgroup: H is a multiple of 64)
-    float* out = pl == 0 ? o0 : (pl == 1 ? o1 : o2);
-    if (!out) return;
-    const float* p = part + (size_t)pl * H + e;
-    float acc = 0.f;
-#pragma unroll 8
-    for (int c = strand; c < S; c += kEgStrands) acc += p[(size_t)c * NP * H];
-    st[strand][col] = acc;
-    __syncthreads();
-    if (strand != 0) return;
-    const int ns = min(S, kEgStrands);
-    for (int j = 1; j < ns; ++j) acc += st[j][col];
-    out[e] = accumulate ? acc + out[e] : acc;
-}
-
-bool eg_aligned16(std::initializer_list<const void*> ps) {
-    uintptr_t all = 0;
-    for (const void* p : ps) all |= (uintptr_t)p;
-    return (all & 15) == 0;
 }
 
 // the table half of both entry points: accumulate = 0 zeroes the given tables first
@@ -448,12 +404,11 @@ int mdr_embedding_plan(const int64_t* ids_dev, const int* tok_src_dev, const int
     MDR_REQUIRE(vocab >= 1 && vocab <= kEgMaxVocab, "%s: vocab=%d out of range (1 .. 2^20)", fn, vocab);
     MDR_REQUIRE(max_pos >= 1 && max_pos <= kEgMaxPos, "%s: max_pos=%d out of range (1 .. 2^16)", fn, max_pos);
     MDR_REQUIRE(pad_row >= -1 && pad_row < kEgMaxVocab, "%s: pad_row=%d out of range (-1 .. 2^20 - 1)", fn, pad_row);
-    MDR_REQUIRE(eg_aligned16({plan_dev}), "%s: the plan must be 16-byte aligned", fn);
+    MDR_REQUIRE(aligned16({plan_dev}), "%s: the plan must be 16-byte aligned", fn);
     const size_t need = eg_plan_words(cap) * sizeof(int);
     if (!(plan_dev && plan_bytes >= need))
         return set_error(MDR_E_WORKSPACE, "%s: plan buffer of %zu bytes, need %zu (mdr_embedding_plan_bytes)", fn, plan_dev ? plan_bytes : (size_t)0, need);
-    DeviceGuard guard(device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    MDR_ENTER_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     int* plan = (int*)plan_dev;
     hipLaunchKernelGGL(emb_keys_kernel, dim3((std::max(cap, kEgHeader) + 255) / 256), dim3(256), 0, st, (const long long*)ids_dev, tok_src_dev, tok_pid_dev, total_dev,
@@ -469,23 +424,23 @@ int mdr_embedding_plan(const int64_t* ids_dev, const int* tok_src_dev, const int
 int mdr_embedding_backward_chunks(int cap, int H, int* rows_per_chunk) {
     using namespace mdr;
     int rpc = 0, S = 0;
-    if (eg_cap_ok(cap) && eg_hidden_ok(H)) S = eg_chunks(cap, H, &rpc);
+    if (eg_cap_ok(cap) && grad_hidden_ok(H)) S = grad_row_chunks(cap, H, kEgPlanes, &rpc);
     if (rows_per_chunk) *rows_per_chunk = rpc;
     return S;
 }
 
 size_t mdr_embedding_scatter_workspace_bytes(int cap, int H) {
     using namespace mdr;
-    if (!(eg_cap_ok(cap) && eg_hidden_ok(H))) return 0;
+    if (!(eg_cap_ok(cap) && grad_hidden_ok(H))) return 0;
     int rpc;
-    return align_up((size_t)eg_chunks(cap, H, &rpc) * H * sizeof(float), 256);
+    return align_up((size_t)grad_row_chunks(cap, H, kEgPlanes, &rpc) * H * sizeof(float), 256);
 }
 
 size_t mdr_embedding_backward_workspace_bytes(int cap, int H) {
     using namespace mdr;
-    if (!(eg_cap_ok(cap) && eg_hidden_ok(H))) return 0;
+    if (!(eg_cap_ok(cap) && grad_hidden_ok(H))) return 0;
     int rpc;
-    return align_up((size_t)cap * H * sizeof(float), 256) + align_up((size_t)eg_chunks(cap, H, &rpc) * 3 * H * sizeof(float), 256);
+    return align_up((size_t)cap * H * sizeof(float), 256) + align_up((size_t)grad_row_chunks(cap, H, kEgPlanes, &rpc) * 3 * H * sizeof(float), 256);
 }
 
 int mdr_embedding_scatter(const float* d32_dev, const void* plan_dev, int cap, int H, int vocab, int max_pos, float* dword_dev, float* dpos_dev,
@@ -496,26 +451,22 @@ int mdr_embedding_scatter(const float* d32_dev, const void* plan_dev, int cap, i
     MDR_REQUIRE(dword_dev || dpos_dev || dtype0_dev, "%s: NULL pointer (every output: at least one is required)", fn);
     MDR_REQUIRE(accumulate == 0 || accumulate == 1, "%s: accumulate must be 0 or 1, got %d", fn, accumulate);
     MDR_REQUIRE(eg_cap_ok(cap), "%s: cap=%d out of range (1 .. 2^20)", fn, cap);
-    MDR_REQUIRE(eg_hidden_ok(H), "%s: H=%d unsupported (a multiple of 64, 64 .. 1024)", fn, H);
+    MDR_REQUIRE(grad_hidden_ok(H), "%s: H=%d unsupported (a multiple of 64, 64 .. 1024)", fn, H);
     MDR_REQUIRE(vocab >= 1 && vocab <= kEgMaxVocab, "%s: vocab=%d out of range (1 .. 2^20)", fn, vocab);
     MDR_REQUIRE(max_pos >= 1 && max_pos <= kEgMaxPos, "%s: max_pos=%d out of range (1 .. 2^16)", fn, max_pos);
-    MDR_REQUIRE(eg_aligned16({d32_dev, plan_dev, dword_dev, dpos_dev, dtype0_dev, workspace_dev}), "%s: every pointer must be 16-byte aligned", fn);
+    MDR_REQUIRE(aligned16({d32_dev, plan_dev, dword_dev, dpos_dev, dtype0_dev, workspace_dev}), "%s: every pointer must be 16-byte aligned", fn);
     int rpc;
-    const int S = eg_chunks(cap, H, &rpc);
+    const int S = grad_row_chunks(cap, H, kEgPlanes, &rpc);
     const size_t need = dtype0_dev ? (size_t)S * H * sizeof(float) : 0;
-    if (need && !(workspace_dev && workspace_bytes >= need))
-        return set_error(MDR_E_WORKSPACE, "%s: workspace of %zu bytes, need %zu (mdr_embedding_scatter_workspace_bytes)", fn,
-                         workspace_dev ? workspace_bytes : (size_t)0, need);
-    DeviceGuard guard(device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    MDR_REQUIRE_WORKSPACE(fn, workspace_dev, workspace_bytes, need, "mdr_embedding_scatter_workspace_bytes");
+    MDR_ENTER_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     const int* plan = (const int*)plan_dev;
     if (dtype0_dev) {
         float* part = (float*)workspace_dev;
         hipLaunchKernelGGL(emb_colsum_kernel, dim3(S), dim3(kEgThreads), 0, st, d32_dev, plan, cap, H, rpc, part);
         MDR_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(emb_reduce_kernel, dim3(H / 64), dim3(64 * kEgStrands), 0, st, part, S, 1, H, dtype0_dev, (float*)nullptr, (float*)nullptr, accumulate);
-        MDR_HIP_TRY(hipGetLastError());
+        if (int rc = launch_strand_reduce(part, S, 1, H, dtype0_dev, nullptr, nullptr, accumulate, st)) return rc;
     }
     return eg_launch_tables(d32_dev, plan, cap, H, vocab, max_pos, dword_dev, dpos_dev, accumulate, st);
 }
@@ -534,21 +485,18 @@ int mdr_embedding_backward(const int64_t* ids_dev, const int* tok_src_dev, const
     MDR_REQUIRE(dy2_f32 == 0 || dy2_f32 == 1, "%s: dy2_f32 must be 0 or 1, got %d", fn, dy2_f32);
     MDR_REQUIRE(accumulate == 0 || accumulate == 1, "%s: accumulate must be 0 or 1, got %d", fn, accumulate);
     MDR_REQUIRE(eg_cap_ok(cap), "%s: cap=%d out of range (1 .. 2^20)", fn, cap);
-    MDR_REQUIRE(eg_hidden_ok(H), "%s: H=%d unsupported (a multiple of 64, 64 .. 1024)", fn, H);
+    MDR_REQUIRE(grad_hidden_ok(H), "%s: H=%d unsupported (a multiple of 64, 64 .. 1024)", fn, H);
     MDR_REQUIRE(vocab >= 1 && vocab <= kEgMaxVocab, "%s: vocab=%d out of range (1 .. 2^20)", fn, vocab);
     MDR_REQUIRE(max_pos >= 1 && max_pos <= kEgMaxPos, "%s: max_pos=%d out of range (1 .. 2^16)", fn, max_pos);
-    MDR_REQUIRE(eg_aligned16({word_dev, pos_dev, type0_dev, g_dev, dy16_dev, dy2_dev, plan_dev, dword_dev, dpos_dev, dtype0_dev, dg_dev, db_dev, d32_dev,
+    MDR_REQUIRE(aligned16({word_dev, pos_dev, type0_dev, g_dev, dy16_dev, dy2_dev, plan_dev, dword_dev, dpos_dev, dtype0_dev, dg_dev, db_dev, d32_dev,
                               workspace_dev}),
                 "%s: every float, plan and workspace pointer must be 16-byte aligned", fn);
     int rpc;
-    const int S = eg_chunks(cap, H, &rpc);
+    const int S = grad_row_chunks(cap, H, kEgPlanes, &rpc);
     const size_t d_bytes = align_up((size_t)cap * H * sizeof(float), 256);
     const size_t need = d_bytes + (size_t)S * 3 * H * sizeof(float);
-    if (!(workspace_dev && workspace_bytes >= need))
-        return set_error(MDR_E_WORKSPACE, "%s: workspace of %zu bytes, need %zu (mdr_embedding_backward_workspace_bytes)", fn,
-                         workspace_dev ? workspace_bytes : (size_t)0, need);
-    DeviceGuard guard(device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    MDR_REQUIRE_WORKSPACE(fn, workspace_dev, workspace_bytes, need, "mdr_embedding_backward_workspace_bytes");
+    MDR_ENTER_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     float* d32 = d32_dev ? d32_dev : (float*)workspace_dev;  // d goes where the caller wants to see it
     const bool sums = dtype0_dev || dg_dev || db_dev;
@@ -556,10 +504,8 @@ int mdr_embedding_backward(const int64_t* ids_dev, const int* tok_src_dev, const
     hipLaunchKernelGGL(emb_ln_grad_kernel, dim3(S), dim3(kEgThreads), 0, st, (const long long*)ids_dev, tok_src_dev, tok_pid_dev, total_dev, cap, word_dev, pos_dev,
                        type0_dev, g_dev, H, vocab, max_pos, eps, (const _Float16*)dy16_dev, dy2_dev, dy2_f32, rpc, d32, part);
     MDR_HIP_TRY(hipGetLastError());
-    if (part) {
-        hipLaunchKernelGGL(emb_reduce_kernel, dim3(3 * H / 64), dim3(64 * kEgStrands), 0, st, part, S, 3, H, dg_dev, db_dev, dtype0_dev, accumulate);
-        MDR_HIP_TRY(hipGetLastError());
-    }
+    if (part)
+        if (int rc = launch_strand_reduce(part, S, kEgPlanes, H, dg_dev, db_dev, dtype0_dev, accumulate, st)) return rc;
     return eg_launch_tables(d32, (const int*)plan_dev, cap, H, vocab, max_pos, dword_dev, dpos_dev, accumulate, st);
 }
 

@@ -556,10 +556,9 @@ int loss_check(const char* fn, const void* q, const void* qsp, const void* ctx, 
     MDR_REQUIRE(gr_plan(B, d, K).nctx_chunks + gr_plan(B, d, K).nq_chunks <= kGrMaxChunks, "%s: B = %d, K = %lld: too many column chunks", fn, B, K);
     MDR_REQUIRE(q && qsp && ctx && neg, "%s: q, qsp, ctx and neg must not be NULL", fn);
     MDR_REQUIRE(K == 0 || queue, "%s: queue must not be NULL when K = %lld", fn, K);
-    MDR_REQUIRE((((uintptr_t)q | (uintptr_t)qsp | (uintptr_t)ctx | (uintptr_t)neg | (uintptr_t)queue) & 15) == 0,
-                "%s: q, qsp, ctx, neg and queue must be 16-byte aligned", fn);
+    MDR_REQUIRE(aligned16({q, qsp, ctx, neg, queue}), "%s: q, qsp, ctx, neg and queue must be 16-byte aligned", fn);
     MDR_REQUIRE(need == 0 || (ws && bytes >= need), "%s: workspace of %zu bytes, need %zu", fn, ws ? bytes : (size_t)0, need);
-    MDR_REQUIRE(((uintptr_t)ws & 15) == 0, "%s: the workspace must be 16-byte aligned", fn);
+    MDR_REQUIRE(aligned16({ws}), "%s: the workspace must be 16-byte aligned", fn);
     return MDR_OK;
 }
 
@@ -601,8 +600,7 @@ int mdr_inbatch_loss_backward(const float* q_dev, const float* qsp_dev, const fl
     if (rc != MDR_OK) return rc;
     MDR_REQUIRE(lse1_dev && lse2_dev && g0_dev, "%s: lse1, lse2 and g0 must not be NULL", fn);
     MDR_REQUIRE(dq_dev && dqsp_dev && dctx_dev && dneg_dev, "%s: dq, dqsp, dctx and dneg must not be NULL", fn);
-    MDR_REQUIRE((((uintptr_t)dq_dev | (uintptr_t)dqsp_dev | (uintptr_t)dctx_dev | (uintptr_t)dneg_dev) & 15) == 0,
-                "%s: dq, dqsp, dctx and dneg must be 16-byte aligned", fn);
+    MDR_REQUIRE(aligned16({dq_dev, dqsp_dev, dctx_dev, dneg_dev}), "%s: dq, dqsp, dctx and dneg must be 16-byte aligned", fn);
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace_dev;
     if (mode == MDR_INBATCH_O1)

@@ -5,15 +5,16 @@
 //     xhat = (x - mu) * rstd    a = dy * g    c1 = mean(a)    c2 = mean(a * xhat)    dx = rstd * (a - c1 - xhat * c2)
 //     dg = sum over rows of dy * xhat          db = sum over rows of dy
 //
-// ln_grad_kernel<IN_T, NV>: the rows are cut into S chunks of rows_per_chunk rows (lg_chunks: a function of (M, H) alone). One workgroup
+// ln_grad_kernel<IN_T, NV>: the rows are cut into S chunks of rows_per_chunk rows (grad_row_chunks: a function of (M, H) alone). One workgroup
 //   of four waves owns a chunk. A wave owns a row, as in the forward, with the forward's element order per lane: H % 256 == 0 (NV = H / 256,
 //   a compile-time count that keeps the registers of H = 768 at three groups) lane l holds the NV groups of four columns (l + 64 i) * 4 ..,
 //   one 16-byte load per fp32 group; otherwise (NV = 0) the H / 64 columns l + 64 i. Wave w
 //   walks rows w, w + 4, ... of the chunk in order, writes dx of each row and keeps its lanes' dg and db columns in registers. The four
 //   waves' columns are added through LDS in wave order. S = 1: the workgroup writes dg and db itself (+ the old value). Otherwise it
-//   writes its sums to the workspace [S][2][H], and ln_grad_reduce_kernel adds them in a fixed order: strand j of sixteen adds chunks j,
+//   writes its sums to the workspace [S][2][H], and grad_strand_reduce_kernel adds them in a fixed order: strand j of sixteen adds chunks j,
 //   j + 16, ... in order (sixteen times the loads in flight of one chain over up to 1024 chunks), the min(S, 16) strands are added in strand
 //   order, then the old value. A chunk at or behind the valid count writes zeros. Every output element has one owner and one summation order: no atomics, two runs give the same bits.
+// grad_strand_reduce_kernel is defined here once and serves the embedding backward too (launch_strand_reduce of csrc/mdr_grad_common.h).
 // gather_cls_grad_kernel: one thread per element of d16 [B, H]; row cu[b] of acc16 has one owner.
 //
 // Rounding points (tests/layernorm_grad_ref.py derives its bound from this list; every operation is fp32, and a multiply feeding an add may
@@ -33,7 +34,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "mdr_common.h"
+#include "mdr_grad_common.h"
 #include "../../include/mdr_layernorm_grad.h"
 
 namespace mdr {
@@ -44,27 +45,9 @@ typedef float lg_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kLgWaves = 4;
 constexpr int kLgThreads = 64 * kLgWaves;
-constexpr int kLgMaxH = 1024;
+constexpr int kLgMaxH = kGradMaxH;
 constexpr int kLgPerLane = kLgMaxH / 64;
-constexpr int kLgStrands = 16;                        // chains of ln_grad_reduce_kernel over the chunks
-constexpr int kLgMaxChunks = 1024;                    // target number of workgroups ...
-constexpr size_t kLgMaxPartialBytes = (size_t)4 << 20;  // ... as far as the partial sums [S][2][H] stay within 4 MiB
-
-__device__ __forceinline__ float lg_wave_sum(float v) {  // (wave_sum of csrc/mdr_encoder_pack_ln.inl)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-bool lg_hidden_ok(int H) { return H >= 64 && H <= kLgMaxH && H % 64 == 0; }
-
-// (S, rows per chunk) of a shape inside the limits
-int lg_chunks(int M, int H, int* rpc_out) {
-    const int cap = (int)std::min<size_t>(kLgMaxChunks, kLgMaxPartialBytes / (2 * sizeof(float) * (size_t)H));
-    const int rpc = ((M + cap - 1) / cap + 3) / 4 * 4;
-    *rpc_out = rpc;
-    return (M + rpc - 1) / rpc;
-}
+constexpr int kLgPlanes = 2;  // dg, db: the partial sums are [S][2][H]
 
 // the lane's element k = i * W + j  <->  column (VEC ? (lane + 64 i) * 4 + j : lane + 64 i), W = VEC ? 4 : 1
 template <typename T, bool VEC>
@@ -144,12 +127,12 @@ ln_grad_kernel(const IN_T* __restrict__ in, const _Float16* __restrict__ res16, 
                     else lg_load<_Float16, VEC>((const _Float16*)dy2 + off, lane, i, di);
                 }
             }
-        const float mu = lg_wave_sum(s) / H;
+        const float mu = grad_wave_sum(s) / H;
         float v = 0.f;
 #pragma unroll
         for (int k = 0; k < NE; ++k)
             if (k < n * W) { const float dlt = x[k] - mu; v += dlt * dlt; }
-        const float rstd = rsqrtf(lg_wave_sum(v) / H + eps);
+        const float rstd = rsqrtf(grad_wave_sum(v) / H + eps);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int k = 0; k < NE; ++k)
@@ -163,7 +146,7 @@ ln_grad_kernel(const IN_T* __restrict__ in, const _Float16* __restrict__ res16, 
                 x[k] = xh;
                 dy[k] = a;
             }
-        const float c1 = lg_wave_sum(s1) / H, c2 = lg_wave_sum(s2) / H;
+        const float c1 = grad_wave_sum(s1) / H, c2 = grad_wave_sum(s2) / H;
 #pragma unroll
         for (int i = 0; i < NG; ++i)
             if (i < n) {
@@ -209,23 +192,25 @@ ln_grad_kernel(const IN_T* __restrict__ in, const _Float16* __restrict__ res16, 
     }
 }
 
-// part [S][2][H] -> dg, db. A workgroup owns 64 columns of dg or of db, a wave is a strand: strand j adds chunks j, j + 16, ... in order,
-// then the first wave adds the min(S, 16) strands in order, then the old value.
-__global__ void __launch_bounds__(64 * kLgStrands) ln_grad_reduce_kernel(const float* __restrict__ part, int S, int H, float* dg, float* db, int accumulate) {
-    __shared__ float st[kLgStrands][64];
+// part [S][NP][H] -> the NP outputs. A workgroup owns 64 columns of one plane, a wave is a strand: strand j adds chunks j, j + 16, ... in
+// order, then the first wave adds the min(S, 16) strands in order, then the old value.
+__global__ void __launch_bounds__(64 * kGradStrands)
+grad_strand_reduce_kernel(const float* __restrict__ part, int S, int NP, int H, float* o0, float* o1, float* o2, int accumulate) {
+    __shared__ float st[kGradStrands][64];
     const int col = threadIdx.x & 63, strand = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + col;          // < 2 H: the grid is 2 H / 64 workgroups
-    const int which = i >= H ? 1 : 0, e = i - which * H;
-    float* out = which ? db : dg;                 // (uniform over the workgroup: H is a multiple of 64)
+    const int i = blockIdx.x * 64 + col;  // < NP H: the grid is NP H / 64 workgroups
+    const int pl = (i >= H) + (i >= 2 * H), e = i - pl * H;  // i / H for NP <= 3 without the division (uniform over the workgroup: H is a multiple of 64)
+    float* out = pl == 0 ? o0 : (pl == 1 ? o1 : o2);
     if (!out) return;
-    const float* p = part + (size_t)which * H + e;
+    const size_t chunk = (size_t)NP * H;  // floats of one chunk's partial sums
+    const float* p = part + strand * chunk + (size_t)pl * H + e;
     float acc = 0.f;
 #pragma unroll 8
-    for (int c = strand; c < S; c += kLgStrands) acc += p[(size_t)c * 2 * H];
+    for (int c = strand; c < S; c += kGradStrands, p += kGradStrands * chunk) acc += *p;
     st[strand][col] = acc;
     __syncthreads();
     if (strand != 0) return;
-    const int ns = min(S, kLgStrands);
+    const int ns = min(S, kGradStrands);
     for (int j = 1; j < ns; ++j) acc += st[j][col];
     out[e] = accumulate ? acc + out[e] : acc;
 }
@@ -258,6 +243,13 @@ void lg_launch(int H, dim3 grid, hipStream_t st, const IN_T* in, const _Float16*
 }
 
 }  // namespace
+
+int launch_strand_reduce(const float* part, int S, int planes, int H, float* o0, float* o1, float* o2, int accumulate, hipStream_t stream) {
+    hipLaunchKernelGGL(grad_strand_reduce_kernel, dim3(planes * H / 64), dim3(64 * kGradStrands), 0, stream, part, S, planes, H, o0, o1, o2, accumulate);
+    MDR_HIP_TRY(hipGetLastError());
+    return MDR_OK;
+}
+
 }  // namespace mdr
 
 extern "C" {
@@ -265,16 +257,16 @@ extern "C" {
 int mdr_layernorm_backward_chunks(int M, int H, int* rows_per_chunk) {
     using namespace mdr;
     int rpc = 0, S = 0;
-    if (M >= 1 && lg_hidden_ok(H)) S = lg_chunks(M, H, &rpc);
+    if (M >= 1 && grad_hidden_ok(H)) S = grad_row_chunks(M, H, kLgPlanes, &rpc);
     if (rows_per_chunk) *rows_per_chunk = rpc;
     return S;
 }
 
 size_t mdr_layernorm_backward_workspace_bytes(int M, int H, int want) {
     using namespace mdr;
-    if (!(M >= 1 && lg_hidden_ok(H))) return 0;
+    if (!(M >= 1 && grad_hidden_ok(H))) return 0;
     int rpc;
-    const int S = lg_chunks(M, H, &rpc);
+    const int S = grad_row_chunks(M, H, kLgPlanes, &rpc);
     if (S == 1 || !(want & (MDR_LAYERNORM_WANT_DG | MDR_LAYERNORM_WANT_DB))) return 0;
     return align_up((size_t)S * 2 * H * sizeof(float), 256);
 }
@@ -291,19 +283,15 @@ int mdr_layernorm_backward(const void* in_dev, int in_f16, const void* res16_dev
     MDR_REQUIRE(in_f16 == 0 || in_f16 == 1, "%s: in_f16 must be 0 or 1, got %d", fn, in_f16);
     MDR_REQUIRE(dy2_f32 == 0 || dy2_f32 == 1, "%s: dy2_f32 must be 0 or 1, got %d", fn, dy2_f32);
     MDR_REQUIRE(M >= 1, "%s: M=%d must be at least 1", fn, M);
-    MDR_REQUIRE(lg_hidden_ok(H), "%s: H=%d unsupported (a multiple of 64, 64 .. 1024)", fn, H);
-    MDR_REQUIRE((((uintptr_t)in_dev | (uintptr_t)res16_dev | (uintptr_t)res32_dev | (uintptr_t)dy16_dev | (uintptr_t)dy2_dev | (uintptr_t)g_dev |
-                  (uintptr_t)dx16_dev | (uintptr_t)dx32_dev | (uintptr_t)dg_dev | (uintptr_t)db_dev | (uintptr_t)workspace_dev) & 15) == 0,
+    MDR_REQUIRE(grad_hidden_ok(H), "%s: H=%d unsupported (a multiple of 64, 64 .. 1024)", fn, H);
+    MDR_REQUIRE(aligned16({in_dev, res16_dev, res32_dev, dy16_dev, dy2_dev, g_dev, dx16_dev, dx32_dev, dg_dev, db_dev, workspace_dev}),
                 "%s: every pointer must be 16-byte aligned", fn);
     int rpc;
-    const int S = lg_chunks(M, H, &rpc);
+    const int S = grad_row_chunks(M, H, kLgPlanes, &rpc);
     const bool sums = dg_dev || db_dev;
     const size_t need = S > 1 && sums ? (size_t)S * 2 * H * sizeof(float) : 0;
-    if (need && !(workspace_dev && workspace_bytes >= need))
-        return set_error(MDR_E_WORKSPACE, "%s: workspace of %zu bytes, need %zu (mdr_layernorm_backward_workspace_bytes)", fn,
-                         workspace_dev ? workspace_bytes : (size_t)0, need);
-    DeviceGuard guard(device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    MDR_REQUIRE_WORKSPACE(fn, workspace_dev, workspace_bytes, need, "mdr_layernorm_backward_workspace_bytes");
+    MDR_ENTER_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     float* part = need ? (float*)workspace_dev : nullptr;
     if (in_f16)
@@ -313,10 +301,7 @@ int mdr_layernorm_backward(const void* in_dev, int in_f16, const void* res16_dev
         lg_launch(H, dim3(S), st, (const float*)in_dev, (const _Float16*)res16_dev, res32_dev, (const _Float16*)dy16_dev, dy2_dev, dy2_f32, M, m_dev, rpc,
                   g_dev, eps, (_Float16*)dx16_dev, dx32_dev, dg_dev, db_dev, accumulate ? 1 : 0, part);
     MDR_HIP_TRY(hipGetLastError());
-    if (part) {
-        hipLaunchKernelGGL(ln_grad_reduce_kernel, dim3(2 * H / 64), dim3(64 * kLgStrands), 0, st, part, S, H, dg_dev, db_dev, accumulate ? 1 : 0);
-        MDR_HIP_TRY(hipGetLastError());
-    }
+    if (part) return launch_strand_reduce(part, S, kLgPlanes, H, dg_dev, db_dev, nullptr, accumulate ? 1 : 0, st);
     return MDR_OK;
 }
 
@@ -325,10 +310,9 @@ int mdr_gather_cls_backward(const void* d16_dev, const int* cu_dev, int B, int H
     const char* fn = "mdr_gather_cls_backward";
     MDR_REQUIRE(d16_dev && cu_dev && acc16_dev, "%s: NULL pointer (d16, cu and acc16 are required)", fn);
     MDR_REQUIRE(B >= 1 && B <= (1 << 20), "%s: B=%d out of range (1 .. 2^20)", fn, B);
-    MDR_REQUIRE(lg_hidden_ok(H), "%s: H=%d unsupported (a multiple of 64, 64 .. 1024)", fn, H);
-    MDR_REQUIRE((((uintptr_t)d16_dev | (uintptr_t)acc16_dev) & 15) == 0, "%s: d16 and acc16 must be 16-byte aligned", fn);
-    DeviceGuard guard(device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    MDR_REQUIRE(grad_hidden_ok(H), "%s: H=%d unsupported (a multiple of 64, 64 .. 1024)", fn, H);
+    MDR_REQUIRE(aligned16({d16_dev, acc16_dev}), "%s: d16 and acc16 must be 16-byte aligned", fn);
+    MDR_ENTER_DEVICE(device);
     hipLaunchKernelGGL(gather_cls_grad_kernel, dim3((B * H + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const _Float16*)d16_dev, cu_dev, B, H,
                        (_Float16*)acc16_dev);
     MDR_HIP_TRY(hipGetLastError());

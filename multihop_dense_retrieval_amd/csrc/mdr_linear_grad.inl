@@ -274,8 +274,6 @@ LgPlan lg_plan(int M, int N, int K, int want) {
     return p;
 }
 
-bool lg_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -300,16 +298,12 @@ int mdr_linear_backward(const void* x_dev, const void* w_dev, const void* dy_dev
     MDR_REQUIRE(dx_dev || dw_dev || db_dev, "nothing to compute: dx, dw and db are all NULL");
     MDR_REQUIRE(M >= 1, "M=%d must be at least 1", M);
     MDR_REQUIRE(N >= 64 && K >= 64 && N % 64 == 0 && K % 64 == 0, "bad Linear shape N=%d K=%d (positive multiples of 64)", N, K);
-    MDR_REQUIRE(lg_aligned16(x_dev) && lg_aligned16(w_dev) && lg_aligned16(dy_dev) && lg_aligned16(pre_dev) && lg_aligned16(dx_dev) &&
-                    lg_aligned16(dw_dev) && lg_aligned16(db_dev) && lg_aligned16(workspace_dev),
-                "pointers must be 16-byte aligned");
+    MDR_REQUIRE(aligned16({x_dev, w_dev, dy_dev, pre_dev, dx_dev, dw_dev, db_dev, workspace_dev}), "pointers must be 16-byte aligned");
     const int want = (dx_dev ? MDR_LINEAR_WANT_DX : 0) | (dw_dev ? MDR_LINEAR_WANT_DW : 0) | (db_dev ? MDR_LINEAR_WANT_DB : 0) |
                      (pre_dev ? MDR_LINEAR_WANT_PRE : 0);
     const LgPlan p = lg_plan(M, N, K, want);
-    if (p.bytes && (!workspace_dev || workspace_bytes < p.bytes))
-        return set_error(MDR_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", p.bytes, workspace_dev ? workspace_bytes : (size_t)0);
-    DeviceGuard guard(device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    MDR_REQUIRE_WORKSPACE("mdr_linear_backward", workspace_dev, workspace_bytes, p.bytes, "mdr_linear_backward_workspace_bytes");
+    MDR_ENTER_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace_dev;
     const _Float16* x = (const _Float16*)x_dev;

@@ -377,8 +377,6 @@ int64_t opt_chunks(const int64_t* n, int n_tensors, int64_t* first) {
 
 size_t opt_table_bytes(int n_tensors, int64_t chunks) { return align_up((size_t)n_tensors * sizeof(mdr_optim_tensor) + (size_t)chunks * sizeof(OptMap), 256); }
 
-bool opt_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 }  // namespace mdr
 
@@ -407,7 +405,7 @@ int mdr_optim_table_fill(const mdr_optim_tensor* tensors, int n_tensors, void* t
         MDR_REQUIRE(t.n >= 1, "%s: tensor %d has n=%lld, must be at least 1", fn, i, (long long)t.n);
         MDR_REQUIRE(t.p, "%s: tensor %d has a NULL p", fn, i);
         MDR_REQUIRE(!t.g || (t.m && t.v), "%s: tensor %d has a g but no m or v", fn, i);
-        MDR_REQUIRE(opt_aligned16(t.p) && opt_aligned16(t.g) && opt_aligned16(t.m) && opt_aligned16(t.v) && ((uintptr_t)t.p16 & 7) == 0,
+        MDR_REQUIRE(aligned16({t.p, t.g, t.m, t.v}) && ((uintptr_t)t.p16 & 7) == 0,
                     "%s: tensor %d: p, g, m, v must be 16-byte aligned and p16 8-byte aligned", fn, i);
         total += (t.n - 1) / kOptChunk + 1;
         MDR_REQUIRE(total <= 0x7fffffff, "%s: more than 2^31 - 1 chunks", fn);
@@ -431,10 +429,9 @@ int mdr_optim_state_init(mdr_optim_state* state_dev, float loss_scale, int devic
     using namespace mdr;
     const char* fn = "mdr_optim_state_init";
     MDR_REQUIRE(state_dev, "%s: NULL state", fn);
-    MDR_REQUIRE(opt_aligned16(state_dev), "%s: state must be 16-byte aligned", fn);
+    MDR_REQUIRE(aligned16({state_dev}), "%s: state must be 16-byte aligned", fn);
     MDR_REQUIRE(loss_scale > 0.f && std::isfinite(loss_scale), "%s: loss_scale=%g must be positive and finite", fn, (double)loss_scale);
-    DeviceGuard guard(device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    MDR_ENTER_DEVICE(device);
     hipLaunchKernelGGL(optim_state_init_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state_dev, loss_scale);
     MDR_HIP_TRY(hipGetLastError());
     return MDR_OK;
@@ -448,7 +445,7 @@ int mdr_optim_step(const void* table_dev, int n_tensors, int n_chunks, mdr_optim
     MDR_REQUIRE(table_dev && state_dev, "%s: NULL pointer (table and state are required)", fn);
     MDR_REQUIRE(n_tensors >= 1, "%s: n_tensors=%d must be at least 1", fn, n_tensors);
     MDR_REQUIRE(n_chunks >= n_tensors, "%s: n_chunks=%d is less than n_tensors=%d (mdr_optim_chunks)", fn, n_chunks, n_tensors);
-    MDR_REQUIRE(opt_aligned16(table_dev) && opt_aligned16(state_dev) && opt_aligned16(workspace_dev), "%s: every pointer must be 16-byte aligned", fn);
+    MDR_REQUIRE(aligned16({table_dev, state_dev, workspace_dev}), "%s: every pointer must be 16-byte aligned", fn);
     MDR_REQUIRE(std::isfinite(lr), "%s: lr=%g must be finite", fn, (double)lr);
     MDR_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "%s: betas (%g, %g) must lie in [0, 1)", fn, (double)beta1, (double)beta2);
     MDR_REQUIRE(eps > 0.f && std::isfinite(eps), "%s: eps=%g must be positive and finite", fn, (double)eps);
@@ -458,11 +455,8 @@ int mdr_optim_step(const void* table_dev, int n_tensors, int n_chunks, mdr_optim
     MDR_REQUIRE(scale_window >= 1, "%s: scale_window=%d must be at least 1", fn, scale_window);
     MDR_REQUIRE(max_scale > 0.f && std::isfinite(max_scale), "%s: max_scale=%g must be positive and finite", fn, (double)max_scale);
     const size_t need = (size_t)n_chunks * sizeof(OptSlot);
-    if (!(workspace_dev && workspace_bytes >= need))
-        return set_error(MDR_E_WORKSPACE, "%s: workspace of %zu bytes, need %zu (mdr_optim_workspace_bytes)", fn, workspace_dev ? workspace_bytes : (size_t)0,
-                         need);
-    DeviceGuard guard(device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    MDR_REQUIRE_WORKSPACE(fn, workspace_dev, workspace_bytes, need, "mdr_optim_workspace_bytes");
+    MDR_ENTER_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     const mdr_optim_tensor* tab = (const mdr_optim_tensor*)table_dev;
     const OptMap* map = (const OptMap*)(tab + n_tensors);
@@ -484,10 +478,9 @@ int mdr_optim_ema(const void* table_k_dev, const void* table_q_dev, int n_tensor
     MDR_REQUIRE(table_k_dev && table_q_dev, "%s: NULL pointer (both tables are required)", fn);
     MDR_REQUIRE(n_tensors >= 1, "%s: n_tensors=%d must be at least 1", fn, n_tensors);
     MDR_REQUIRE(n_chunks >= n_tensors, "%s: n_chunks=%d is less than n_tensors=%d (mdr_optim_chunks)", fn, n_chunks, n_tensors);
-    MDR_REQUIRE(opt_aligned16(table_k_dev) && opt_aligned16(table_q_dev), "%s: every pointer must be 16-byte aligned", fn);
+    MDR_REQUIRE(aligned16({table_k_dev, table_q_dev}), "%s: every pointer must be 16-byte aligned", fn);
     MDR_REQUIRE(m >= 0.0 && m <= 1.0, "%s: m=%g must lie in [0, 1]", fn, m);
-    DeviceGuard guard(device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    MDR_ENTER_DEVICE(device);
     const mdr_optim_tensor* tk = (const mdr_optim_tensor*)table_k_dev;
     hipLaunchKernelGGL(optim_ema_kernel, dim3(std::min(n_chunks, kOptMaxGrid)), dim3(kOptThreads), 0, (hipStream_t)stream, tk,
                        (const mdr_optim_tensor*)table_q_dev, (const OptMap*)(tk + n_tensors), n_chunks, (float)m, (float)(1.0 - m));

@@ -17,6 +17,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import check_hidden, check_rows, describe, is_like, ptr
 
 _c = ctypes
 # include/mdr_embedding_grad.h -- bound here, apart from _lib._SIGNATURES (include/mdr_hip.h's table, pinned by its own test)
@@ -38,35 +39,7 @@ PIECE = 16                 # MDR_EMBEDDING_PIECE
 PLAN_HEADER = 16           # MDR_EMBEDDING_PLAN_HEADER
 PLAN_MAGIC = 0x4D455031    # MDR_EMBEDDING_PLAN_MAGIC
 MAX_CAP, MAX_VOCAB, MAX_POS = 1 << 20, 1 << 20, 1 << 16
-_bound = False
-
-
-def lib():
-    """libmdrhip.so with the signatures of include/mdr_embedding_grad.h bound (AttributeError if the library lacks one: no fallback)."""
-    global _bound
-    L = _lib.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _bound = True
-    return L
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _dev_index(dev):
-    return dev.index if dev.index is not None else torch.cuda.current_device()
-
-
-def _is(t, dtypes, shape, dev):
-    return torch.is_tensor(t) and t.dtype in dtypes and t.is_contiguous() and t.device == dev and tuple(t.shape) == tuple(shape)
-
-
-def _describe(t):
-    return f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}"
+lib = _lib.binder(SIGNATURES)  # libmdrhip.so with the signatures of include/mdr_embedding_grad.h bound
 
 
 def plan_layout(cap):
@@ -92,14 +65,13 @@ def _check_pack(ids, tok_src, tok_pid, total, cap):
         raise RuntimeError("the embedding backward runs on a HIP device only (there is no CPU fallback)")
     dev = ids.device
     if ids.dtype != torch.int64 or not ids.is_contiguous() or ids.numel() < 1:
-        raise ValueError(f"ids must be a contiguous int64 tensor, got {_describe(ids)}")
+        raise ValueError(f"ids must be a contiguous int64 tensor, got {describe(ids)}")
     if not (isinstance(cap, int) and 1 <= cap <= MAX_CAP):
         raise ValueError(f"cap = {cap!r}: must be an int, 1 .. 2^20")
     for name, t in (("tok_src", tok_src), ("tok_pid", tok_pid)):
         if not (torch.is_tensor(t) and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.device == dev and t.shape[0] >= cap):
-            raise ValueError(f"{name} must be a contiguous int32 [>= {cap}] tensor on ids' device, got {_describe(t)}")
-    if not (torch.is_tensor(total) and total.device == dev and total.dtype == torch.int32 and total.numel() == 1):
-        raise ValueError("total must be an int32 tensor of one element on ids' device")
+            raise ValueError(f"{name} must be a contiguous int32 [>= {cap}] tensor on ids' device, got {describe(t)}")
+    check_rows(total, dev, "total", "ids")
     return dev
 
 
@@ -112,22 +84,17 @@ def _check_sizes(vocab, max_pos, pad_row):
         raise ValueError(f"pad_row = {pad_row!r}: must be an int, -1 .. 2^20 - 1")
 
 
-def _check_hidden(H):
-    if H < 64 or H > 1024 or H % 64:
-        raise ValueError(f"H = {H}: must be a multiple of 64, 64 .. 1024")
-
-
 def _check_plan(plan, cap, dev):
     if not (torch.is_tensor(plan) and plan.dtype == torch.int32 and plan.dim() == 1 and plan.is_contiguous() and plan.device == dev
             and plan.shape[0] >= plan_layout(cap)["words"]):
-        raise ValueError(f"plan must be the int32 tensor embedding_plan returned for cap = {cap} on the same device, got {_describe(plan)}")
+        raise ValueError(f"plan must be the int32 tensor embedding_plan returned for cap = {cap} on the same device, got {describe(plan)}")
 
 
 def _check_outputs(outs, H, dev):
     for name, t, rows in outs:
         shape = (H,) if rows is None else (rows, H)
-        if t is not None and not _is(t, (torch.float32,), shape, dev):
-            raise ValueError(f"{name} must be None or a contiguous fp32 {list(shape)} tensor on the inputs' device, got {_describe(t)}")
+        if t is not None and not is_like(t, (torch.float32,), shape, dev):
+            raise ValueError(f"{name} must be None or a contiguous fp32 {list(shape)} tensor on the inputs' device, got {describe(t)}")
 
 
 def embedding_plan(ids, tok_src, tok_pid, total, cap, vocab, max_pos, pad_row=-1):
@@ -137,9 +104,7 @@ def embedding_plan(ids, tok_src, tok_pid, total, cap, vocab, max_pos, pad_row=-1
     L = lib()
     nbytes = int(L.mdr_embedding_plan_bytes(cap))
     plan = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.mdr_embedding_plan(_ptr(ids), _ptr(tok_src), _ptr(tok_pid), _ptr(total), cap, vocab, max_pos, pad_row, _ptr(plan), nbytes,
-                                        _dev_index(dev), _lib.current_stream_ptr(dev)))
+    _lib.call(L.mdr_embedding_plan, ptr(ids), ptr(tok_src), ptr(tok_pid), ptr(total), cap, vocab, max_pos, pad_row, ptr(plan), nbytes, dev=dev)
     return plan
 
 
@@ -150,35 +115,34 @@ def embedding_scatter(d32, plan, vocab, max_pos, dword=None, dpos=None, dtype0=N
     if not (torch.is_tensor(d32) and d32.is_cuda):
         raise RuntimeError("the embedding scatter runs on a HIP device only (there is no CPU fallback)")
     if d32.dtype != torch.float32 or d32.dim() != 2 or not d32.is_contiguous() or not 1 <= d32.shape[0] <= MAX_CAP:
-        raise ValueError(f"d32 must be a contiguous fp32 [1 <= cap <= 2^20, H] tensor, got {_describe(d32)}")
+        raise ValueError(f"d32 must be a contiguous fp32 [1 <= cap <= 2^20, H] tensor, got {describe(d32)}")
     cap, H = int(d32.shape[0]), int(d32.shape[1])
     dev = d32.device
-    _check_hidden(H)
+    check_hidden(H)
     _check_sizes(vocab, max_pos, -1)
     _check_plan(plan, cap, dev)
     _check_outputs((("dword", dword, vocab), ("dpos", dpos, max_pos), ("dtype0", dtype0, None)), H, dev)
     if dword is None and dpos is None and dtype0 is None:
         raise ValueError("nothing to compute: dword, dpos and dtype0 are all None")
     L = lib()
-    with torch.cuda.device(dev):
-        need = int(L.mdr_embedding_scatter_workspace_bytes(cap, H))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        _lib.check(L.mdr_embedding_scatter(_ptr(d32), _ptr(plan), cap, H, vocab, max_pos, _ptr(dword), _ptr(dpos), _ptr(dtype0), 1 if accumulate else 0,
-                                           _ptr(ws), need, _dev_index(dev), _lib.current_stream_ptr(dev)))
+    need = int(L.mdr_embedding_scatter_workspace_bytes(cap, H))
+    ws = _lib.workspace(need, dev)
+    _lib.call(L.mdr_embedding_scatter, ptr(d32), ptr(plan), cap, H, vocab, max_pos, ptr(dword), ptr(dpos), ptr(dtype0), 1 if accumulate else 0, ptr(ws), need,
+              dev=dev)
     return dword, dpos, dtype0
 
 
 def _check_params(word, pos, type0, weight, dev):
     if not (torch.is_tensor(word) and word.dtype == torch.float32 and word.dim() == 2 and word.is_contiguous() and word.device == dev and word.shape[0] >= 1):
-        raise ValueError(f"word must be a contiguous fp32 [vocab, H] tensor on ids' device, got {_describe(word)}")
+        raise ValueError(f"word must be a contiguous fp32 [vocab, H] tensor on ids' device, got {describe(word)}")
     vocab, H = int(word.shape[0]), int(word.shape[1])
-    _check_hidden(H)
+    check_hidden(H)
     if not (torch.is_tensor(pos) and pos.dtype == torch.float32 and pos.dim() == 2 and pos.is_contiguous() and pos.device == dev and pos.shape[0] >= 1
             and pos.shape[1] == H):
-        raise ValueError(f"pos must be a contiguous fp32 [max_pos, {H}] tensor on ids' device, got {_describe(pos)}")
+        raise ValueError(f"pos must be a contiguous fp32 [max_pos, {H}] tensor on ids' device, got {describe(pos)}")
     for name, t in (("type0", type0), ("weight", weight)):
-        if not _is(t, (torch.float32,), (H,), dev):
-            raise ValueError(f"{name} must be a contiguous fp32 [{H}] tensor on ids' device, got {_describe(t)}")
+        if not is_like(t, (torch.float32,), (H,), dev):
+            raise ValueError(f"{name} must be a contiguous fp32 [{H}] tensor on ids' device, got {describe(t)}")
     return vocab, int(pos.shape[0]), H
 
 
@@ -190,10 +154,10 @@ def embedding_backward(ids, tok_src, tok_pid, total, cap, word, pos, type0, weig
     dev = _check_pack(ids, tok_src, tok_pid, total, cap)
     vocab, max_pos, H = _check_params(word, pos, type0, weight, dev)
     _check_sizes(vocab, max_pos, -1)
-    if dy16 is not None and not _is(dy16, (torch.float16,), (cap, H), dev):
-        raise ValueError(f"dy16 must be None or a contiguous fp16 [{cap}, {H}] tensor on ids' device, got {_describe(dy16)}")
-    if dy2 is not None and not _is(dy2, (torch.float16, torch.float32), (cap, H), dev):
-        raise ValueError(f"dy2 must be None or a contiguous fp16 or fp32 [{cap}, {H}] tensor on ids' device, got {_describe(dy2)}")
+    if dy16 is not None and not is_like(dy16, (torch.float16,), (cap, H), dev):
+        raise ValueError(f"dy16 must be None or a contiguous fp16 [{cap}, {H}] tensor on ids' device, got {describe(dy16)}")
+    if dy2 is not None and not is_like(dy2, (torch.float16, torch.float32), (cap, H), dev):
+        raise ValueError(f"dy2 must be None or a contiguous fp16 or fp32 [{cap}, {H}] tensor on ids' device, got {describe(dy2)}")
     if dy16 is None and dy2 is None:
         raise ValueError("dy16 and dy2 are both None: one output gradient is required")
     _check_outputs((("dword", dword, vocab), ("dpos", dpos, max_pos), ("dtype0", dtype0, None), ("dg", dg, None), ("db", db, None), ("d32", d32, cap)), H, dev)
@@ -202,13 +166,11 @@ def embedding_backward(ids, tok_src, tok_pid, total, cap, word, pos, type0, weig
     if dword is not None or dpos is not None:
         _check_plan(plan, cap, dev)
     L = lib()
-    with torch.cuda.device(dev):
-        need = int(L.mdr_embedding_backward_workspace_bytes(cap, H))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        _lib.check(L.mdr_embedding_backward(_ptr(ids), _ptr(tok_src), _ptr(tok_pid), _ptr(total), cap, _ptr(word), _ptr(pos), _ptr(type0), _ptr(weight), H,
-                                            vocab, max_pos, float(eps), _ptr(dy16), _ptr(dy2), 1 if dy2 is not None and dy2.dtype == torch.float32 else 0,
-                                            _ptr(plan), _ptr(dword), _ptr(dpos), _ptr(dtype0), _ptr(dg), _ptr(db), _ptr(d32), 1 if accumulate else 0, _ptr(ws),
-                                            need, _dev_index(dev), _lib.current_stream_ptr(dev)))
+    need = int(L.mdr_embedding_backward_workspace_bytes(cap, H))
+    ws = _lib.workspace(need, dev)
+    _lib.call(L.mdr_embedding_backward, ptr(ids), ptr(tok_src), ptr(tok_pid), ptr(total), cap, ptr(word), ptr(pos), ptr(type0), ptr(weight), H, vocab, max_pos,
+              float(eps), ptr(dy16), ptr(dy2), 1 if dy2 is not None and dy2.dtype == torch.float32 else 0, ptr(plan), ptr(dword), ptr(dpos), ptr(dtype0), ptr(dg),
+              ptr(db), ptr(d32), 1 if accumulate else 0, ptr(ws), need, dev=dev)
     return dword, dpos, dtype0, dg, db, d32
 
 
@@ -217,10 +179,8 @@ def _forward(ids, tok_src, tok_pid, total, cap, word, pos, type0, weight, bias, 
     dev, (vocab, H), max_pos = ids.device, word.shape, pos.shape[0]
     y16 = torch.zeros((cap, H), dtype=torch.float16, device=dev)
     y32 = torch.zeros((cap, H), dtype=torch.float32, device=dev) if keep32 else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mdr_test_embed_ln(0, _ptr(ids), None, _ptr(tok_src), _ptr(tok_pid), _ptr(total), cap, 0, _ptr(word), _ptr(pos), _ptr(type0), 1,
-                                                _ptr(weight), _ptr(bias), H, vocab, max_pos, float(eps), _ptr(y16), _ptr(y32), _dev_index(dev),
-                                                _lib.current_stream_ptr(dev)))
+    _lib.call(_lib.lib().mdr_test_embed_ln, 0, ptr(ids), None, ptr(tok_src), ptr(tok_pid), ptr(total), cap, 0, ptr(word), ptr(pos), ptr(type0), 1, ptr(weight),
+              ptr(bias), H, vocab, max_pos, float(eps), ptr(y16), ptr(y32), dev=dev)
     return y16, y32
 
 
@@ -255,6 +215,6 @@ def packed_embedding_layer_norm(ids, tok_src, tok_pid, total, word, pos, type0, 
     dev = _check_pack(ids, tok_src, tok_pid, total, cap)
     vocab, max_pos, H = _check_params(word, pos, type0, weight, dev)
     _check_sizes(vocab, max_pos, pad_row)
-    if not _is(bias, (torch.float32,), (H,), dev):
-        raise ValueError(f"bias must be a contiguous fp32 [{H}] tensor on ids' device, got {_describe(bias)}")
+    if not is_like(bias, (torch.float32,), (H,), dev):
+        raise ValueError(f"bias must be a contiguous fp32 [{H}] tensor on ids' device, got {describe(bias)}")
     return _PackedEmbeddingLayerNorm.apply(ids, tok_src, tok_pid, total, word, pos, type0, weight, bias, float(eps), cap, pad_row, bool(keep32))

@@ -16,6 +16,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import check_hidden, check_rows, describe, is_like, ptr
 
 _c = ctypes
 # include/mdr_layernorm_grad.h -- bound here, apart from _lib._SIGNATURES (include/mdr_hip.h's table, pinned by its own test)
@@ -29,27 +30,7 @@ SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 WANT_DG, WANT_DB = 1, 2
-_bound = False
-
-
-def lib():
-    """libmdrhip.so with the signatures of include/mdr_layernorm_grad.h bound (AttributeError if the library lacks one: no fallback)."""
-    global _bound
-    L = _lib.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _bound = True
-    return L
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _dev_index(dev):
-    return dev.index if dev.index is not None else torch.cuda.current_device()
+lib = _lib.binder(SIGNATURES)  # libmdrhip.so with the signatures of include/mdr_layernorm_grad.h bound
 
 
 def backward_chunks(M, H):
@@ -59,28 +40,19 @@ def backward_chunks(M, H):
     return S, int(rpc.value)
 
 
-def _is(t, dtypes, shape, dev):
-    return torch.is_tensor(t) and t.dtype in dtypes and t.is_contiguous() and t.device == dev and tuple(t.shape) == tuple(shape)
-
-
-def _describe(t):
-    return f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}"
-
-
 def _check_operands(x, residual, weight, rows):
     if not (torch.is_tensor(x) and x.is_cuda):
         raise RuntimeError("the packed LayerNorm runs on a HIP device only (there is no CPU fallback)")
     if x.dtype not in (torch.float32, torch.float16) or x.dim() != 2 or not x.is_contiguous() or x.shape[0] < 1:
-        raise ValueError(f"x must be a contiguous fp32 or fp16 [M >= 1, H] tensor, got {_describe(x)}")
+        raise ValueError(f"x must be a contiguous fp32 or fp16 [M >= 1, H] tensor, got {describe(x)}")
     M, H = int(x.shape[0]), int(x.shape[1])
-    if H < 64 or H > 1024 or H % 64:
-        raise ValueError(f"H = {H}: must be a multiple of 64, 64 .. 1024")
-    if residual is not None and not _is(residual, (torch.float16, torch.float32), (M, H), x.device):
-        raise ValueError(f"residual must be None or a contiguous fp16 or fp32 [{M}, {H}] tensor on x's device, got {_describe(residual)}")
-    if not _is(weight, (torch.float32,), (H,), x.device):
-        raise ValueError(f"weight must be a contiguous fp32 [{H}] tensor on x's device, got {_describe(weight)}")
-    if rows is not None and not (torch.is_tensor(rows) and rows.device == x.device and rows.dtype == torch.int32 and rows.numel() == 1):
-        raise ValueError("rows must be an int32 tensor of one element on x's device")
+    check_hidden(H)
+    if residual is not None and not is_like(residual, (torch.float16, torch.float32), (M, H), x.device):
+        raise ValueError(f"residual must be None or a contiguous fp16 or fp32 [{M}, {H}] tensor on x's device, got {describe(residual)}")
+    if not is_like(weight, (torch.float32,), (H,), x.device):
+        raise ValueError(f"weight must be a contiguous fp32 [{H}] tensor on x's device, got {describe(weight)}")
+    if rows is not None:
+        check_rows(rows, x.device)
     return M, H
 
 
@@ -98,15 +70,15 @@ def layer_norm_backward(x, residual, dy16, dy2, weight, eps=1e-5, rows=None, nee
     was given). Enqueued on the current stream."""
     M, H = _check_operands(x, residual, weight, rows)
     dev = x.device
-    if dy16 is not None and not _is(dy16, (torch.float16,), (M, H), dev):
-        raise ValueError(f"dy16 must be None or a contiguous fp16 [{M}, {H}] tensor on x's device, got {_describe(dy16)}")
-    if dy2 is not None and not _is(dy2, (torch.float16, torch.float32), (M, H), dev):
-        raise ValueError(f"dy2 must be None or a contiguous fp16 or fp32 [{M}, {H}] tensor on x's device, got {_describe(dy2)}")
+    if dy16 is not None and not is_like(dy16, (torch.float16,), (M, H), dev):
+        raise ValueError(f"dy16 must be None or a contiguous fp16 [{M}, {H}] tensor on x's device, got {describe(dy16)}")
+    if dy2 is not None and not is_like(dy2, (torch.float16, torch.float32), (M, H), dev):
+        raise ValueError(f"dy2 must be None or a contiguous fp16 or fp32 [{M}, {H}] tensor on x's device, got {describe(dy2)}")
     if dy16 is None and dy2 is None:
         raise ValueError("dy16 and dy2 are both None: one output gradient is required")
     for name, t in (("dg", dg), ("db", db)):
-        if t is not None and not _is(t, (torch.float32,), (H,), dev):
-            raise ValueError(f"{name} must be None or a contiguous fp32 [{H}] tensor on x's device, got {_describe(t)}")
+        if t is not None and not is_like(t, (torch.float32,), (H,), dev):
+            raise ValueError(f"{name} must be None or a contiguous fp32 [{H}] tensor on x's device, got {describe(t)}")
     if not (need_dx16 or need_dx32 or dg is not None or db is not None):
         raise ValueError("nothing to compute: neither dx16 nor dx32 is needed and dg and db are None")
     dx16 = torch.zeros((M, H), dtype=torch.float16, device=dev) if need_dx16 else None
@@ -114,13 +86,11 @@ def layer_norm_backward(x, residual, dy16, dy2, weight, eps=1e-5, rows=None, nee
     res16, res32 = _residuals(residual)
     want = (WANT_DG if dg is not None else 0) | (WANT_DB if db is not None else 0)
     L = lib()
-    with torch.cuda.device(dev):
-        need = int(L.mdr_layernorm_backward_workspace_bytes(M, H, want))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-        _lib.check(L.mdr_layernorm_backward(_ptr(x), 1 if x.dtype == torch.float16 else 0, _ptr(res16), _ptr(res32), _ptr(dy16), _ptr(dy2),
-                                            1 if dy2 is not None and dy2.dtype == torch.float32 else 0, M, _ptr(rows), H, _ptr(weight), float(eps),
-                                            _ptr(dx16), _ptr(dx32), _ptr(dg), _ptr(db), 1 if accumulate else 0, _ptr(ws), need, _dev_index(dev),
-                                            _lib.current_stream_ptr(dev)))
+    need = int(L.mdr_layernorm_backward_workspace_bytes(M, H, want))
+    ws = _lib.workspace(need, dev)
+    _lib.call(L.mdr_layernorm_backward, ptr(x), 1 if x.dtype == torch.float16 else 0, ptr(res16), ptr(res32), ptr(dy16), ptr(dy2),
+              1 if dy2 is not None and dy2.dtype == torch.float32 else 0, M, ptr(rows), H, ptr(weight), float(eps), ptr(dx16), ptr(dx32), ptr(dg), ptr(db),
+              1 if accumulate else 0, ptr(ws), need, dev=dev)
     return dx16, dx32, dg, db
 
 
@@ -130,17 +100,15 @@ def gather_cls_backward(d, cu, acc):
     if not (torch.is_tensor(d) and d.is_cuda):
         raise RuntimeError("the CLS gather's backward runs on a HIP device only (there is no CPU fallback)")
     if d.dtype != torch.float16 or d.dim() != 2 or not d.is_contiguous() or d.shape[0] < 1:
-        raise ValueError(f"d must be a contiguous fp16 [B >= 1, H] tensor, got {_describe(d)}")
+        raise ValueError(f"d must be a contiguous fp16 [B >= 1, H] tensor, got {describe(d)}")
     B, H = int(d.shape[0]), int(d.shape[1])
-    if H < 64 or H > 1024 or H % 64:
-        raise ValueError(f"H = {H}: must be a multiple of 64, 64 .. 1024")
-    if not _is(cu, (torch.int32,), (B + 1,), d.device):
-        raise ValueError(f"cu must be a contiguous int32 [{B + 1}] tensor on d's device, got {_describe(cu)}")
+    check_hidden(H)
+    if not is_like(cu, (torch.int32,), (B + 1,), d.device):
+        raise ValueError(f"cu must be a contiguous int32 [{B + 1}] tensor on d's device, got {describe(cu)}")
     if not (torch.is_tensor(acc) and acc.dtype == torch.float16 and acc.dim() == 2 and acc.is_contiguous() and acc.device == d.device
             and acc.shape[1] == H):
-        raise ValueError(f"acc must be a contiguous fp16 [T, {H}] tensor on d's device, got {_describe(acc)}")
-    with torch.cuda.device(d.device):
-        _lib.check(lib().mdr_gather_cls_backward(_ptr(d), _ptr(cu), B, H, _ptr(acc), _dev_index(d.device), _lib.current_stream_ptr(d.device)))
+        raise ValueError(f"acc must be a contiguous fp16 [T, {H}] tensor on d's device, got {describe(acc)}")
+    _lib.call(lib().mdr_gather_cls_backward, ptr(d), ptr(cu), B, H, ptr(acc), dev=d.device)
     return acc
 
 
@@ -150,9 +118,8 @@ def _forward(x, residual, weight, bias, eps, rows, keep32):
     y16 = torch.zeros((M, H), dtype=torch.float16, device=dev)
     y32 = torch.zeros((M, H), dtype=torch.float32, device=dev) if keep32 else None
     res16, res32 = _residuals(residual)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mdr_test_layernorm(_ptr(x), 1 if x.dtype == torch.float16 else 0, _ptr(res16), _ptr(res32), M, _ptr(rows), H, _ptr(weight),
-                                                 _ptr(bias), float(eps), _ptr(y16), _ptr(y32), _dev_index(dev), _lib.current_stream_ptr(dev)))
+    _lib.call(_lib.lib().mdr_test_layernorm, ptr(x), 1 if x.dtype == torch.float16 else 0, ptr(res16), ptr(res32), M, ptr(rows), H, ptr(weight), ptr(bias),
+              float(eps), ptr(y16), ptr(y32), dev=dev)
     return y16, y32
 
 
@@ -188,6 +155,6 @@ def packed_layer_norm(x, residual, weight, bias, eps=1e-5, rows=None, keep32=Fal
     """LayerNorm(x + residual) * weight + bias on packed rows through the encoder's kernel, differentiable with respect to x, residual, weight
     and bias (module docstring)."""
     M, H = _check_operands(x, residual, weight, rows)
-    if not _is(bias, (torch.float32,), (H,), x.device):
-        raise ValueError(f"bias must be a contiguous fp32 [{H}] tensor on x's device, got {_describe(bias)}")
+    if not is_like(bias, (torch.float32,), (H,), x.device):
+        raise ValueError(f"bias must be a contiguous fp32 [{H}] tensor on x's device, got {describe(bias)}")
     return _PackedLayerNorm.apply(x, residual, weight, bias, float(eps), rows, bool(keep32))

@@ -17,6 +17,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import check_rows, describe, is_like, ptr
 
 _c = ctypes
 # include/mdr_linear_grad.h -- bound here, apart from _lib._SIGNATURES (include/mdr_hip.h's table, pinned by its own test)
@@ -28,27 +29,7 @@ SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 WANT_DX, WANT_DW, WANT_DB, WANT_PRE = 1, 2, 4, 8
-_bound = False
-
-
-def lib():
-    """libmdrhip.so with the signatures of include/mdr_linear_grad.h bound (AttributeError if the library lacks one: no fallback)."""
-    global _bound
-    L = _lib.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _bound = True
-    return L
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _dev_index(dev):
-    return dev.index if dev.index is not None else torch.cuda.current_device()
+lib = _lib.binder(SIGNATURES)  # libmdrhip.so with the signatures of include/mdr_linear_grad.h bound
 
 
 def backward_chunks(M, N, K):
@@ -62,16 +43,11 @@ def _check_operands(x, w16, N, K):
     if not (torch.is_tensor(x) and x.is_cuda):
         raise RuntimeError("the packed Linear runs on a HIP device only (there is no CPU fallback)")
     if x.dtype != torch.float16 or x.dim() != 2 or not x.is_contiguous() or x.shape[0] < 1 or x.shape[1] != K:
-        raise ValueError(f"x must be a contiguous fp16 [M >= 1, {K}] tensor, got {x.dtype} {tuple(x.shape)}")
+        raise ValueError(f"x must be a contiguous fp16 [M >= 1, {K}] tensor, got {describe(x)}")
     if N < 64 or K < 64 or N % 64 or K % 64:
         raise ValueError(f"weight [N, K] = [{N}, {K}]: N and K must be positive multiples of 64")
-    if w16 is not None and not (w16.dtype == torch.float16 and w16.is_contiguous() and w16.device == x.device and tuple(w16.shape) == (N, K)):
-        raise ValueError(f"w must be a contiguous fp16 [{N}, {K}] tensor on x's device, got {w16.dtype} {tuple(w16.shape)}")
-
-
-def _check_rows(rows, x):
-    if rows is not None and not (torch.is_tensor(rows) and rows.device == x.device and rows.dtype == torch.int32 and rows.numel() == 1):
-        raise ValueError("rows must be an int32 tensor of one element on x's device")
+    if w16 is not None and not is_like(w16, (torch.float16,), (N, K), x.device):
+        raise ValueError(f"w must be a contiguous fp16 [{N}, {K}] tensor on x's device, got {describe(w16)}")
 
 
 def linear_backward(x, w, dy, pre=None, rows=None, need_dx=True, dw=None, db=None, accumulate=False):
@@ -85,25 +61,24 @@ def linear_backward(x, w, dy, pre=None, rows=None, need_dx=True, dw=None, db=Non
     _check_operands(x, w, N, K)
     M, dev = int(x.shape[0]), x.device
     for name, t in (("dy", dy), ("pre", pre)):
-        if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float16 and t.is_contiguous() and t.device == dev and tuple(t.shape) == (M, N)):
-            raise ValueError(f"{name} must be a contiguous fp16 [{M}, {N}] tensor on x's device, got {getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))}")
+        if t is not None and not is_like(t, (torch.float16,), (M, N), dev):
+            raise ValueError(f"{name} must be a contiguous fp16 [{M}, {N}] tensor on x's device, got {describe(t)}")
     if dy is None:
         raise ValueError("dy is required")
-    _check_rows(rows, x)
-    if dw is not None and not (dw.dtype == torch.float32 and dw.is_contiguous() and dw.device == dev and tuple(dw.shape) == (N, K)):
-        raise ValueError(f"dw must be a contiguous fp32 [{N}, {K}] tensor on x's device, got {dw.dtype} {tuple(dw.shape)}")
-    if db is not None and not (db.dtype == torch.float32 and db.is_contiguous() and db.device == dev and tuple(db.shape) == (N,)):
-        raise ValueError(f"db must be a contiguous fp32 [{N}] tensor on x's device, got {db.dtype} {tuple(db.shape)}")
+    if rows is not None:
+        check_rows(rows, x.device)
+    for name, t, shape in (("dw", dw, (N, K)), ("db", db, (N,))):
+        if t is not None and not is_like(t, (torch.float32,), shape, dev):
+            raise ValueError(f"{name} must be a contiguous fp32 {list(shape)} tensor on x's device, got {describe(t)}")
     if not need_dx and dw is None and db is None:
         raise ValueError("nothing to compute: need_dx is False and dw and db are None")
     dx = torch.zeros((M, K), dtype=torch.float16, device=dev) if need_dx else None
     want = (WANT_DX if need_dx else 0) | (WANT_DW if dw is not None else 0) | (WANT_DB if db is not None else 0) | (WANT_PRE if pre is not None else 0)
     L = lib()
-    with torch.cuda.device(dev):
-        need = int(L.mdr_linear_backward_workspace_bytes(M, N, K, want))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-        _lib.check(L.mdr_linear_backward(_ptr(x), _ptr(w), _ptr(dy), _ptr(pre), M, _ptr(rows), N, K, _ptr(dx), _ptr(dw), _ptr(db),
-                                         1 if accumulate else 0, _ptr(ws), need, _dev_index(dev), _lib.current_stream_ptr(dev)))
+    need = int(L.mdr_linear_backward_workspace_bytes(M, N, K, want))
+    ws = _lib.workspace(need, dev)
+    _lib.call(L.mdr_linear_backward, ptr(x), ptr(w), ptr(dy), ptr(pre), M, ptr(rows), N, K, ptr(dx), ptr(dw), ptr(db), 1 if accumulate else 0, ptr(ws), need,
+              dev=dev)
     return dx, dw, db
 
 
@@ -111,9 +86,7 @@ def _forward_gemm(x, w16, bias, rows, epilogue):
     """mdr_test_gemm_f16 with kernel = 0: the kernel the encoder picks for this shape. Rows at or behind the valid count stay zero."""
     M, (N, K), dev = x.shape[0], w16.shape, x.device
     out = torch.zeros((M, N), dtype=torch.float16, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mdr_test_gemm_f16(_ptr(x), _ptr(w16), _ptr(bias), M, _ptr(rows), N, K, _ptr(out), epilogue, 0, _dev_index(dev),
-                                                _lib.current_stream_ptr(dev)))
+    _lib.call(_lib.lib().mdr_test_gemm_f16, ptr(x), ptr(w16), ptr(bias), M, ptr(rows), N, K, ptr(out), epilogue, 0, dev=dev)
     return out
 
 
@@ -151,5 +124,6 @@ def packed_linear(x, weight, bias, gelu=False, rows=None, weight16=None):
         raise ValueError(f"weight must be the fp32 master [{N}, {K}] on x's device, got {weight.dtype} {tuple(weight.shape)} on {weight.device}")
     if not (torch.is_tensor(bias) and bias.dtype == torch.float32 and bias.device == x.device and tuple(bias.shape) == (N,)):
         raise ValueError(f"bias must be an fp32 [{N}] tensor on x's device, got {getattr(bias, 'dtype', None)} {tuple(getattr(bias, 'shape', ()))}")
-    _check_rows(rows, x)
+    if rows is not None:
+        check_rows(rows, x.device)
     return _PackedLinear.apply(x, weight, bias, bool(gelu), rows, weight16)

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr
 
 _c = ctypes
 CHUNK = 4096  # MDR_OPTIM_CHUNK
@@ -49,27 +50,7 @@ STATE_DTYPE = np.dtype([("loss_scale", "<f4"), ("unskipped", "<i4"), ("adam_step
                         ("skipped_last", "<i4"), ("grad_norm", "<f4"), ("clip_coef", "<f4"), ("mult", "<f4"), ("skipped_total", "<i4"),
                         ("bias1", "<f4"), ("bias2", "<f4")])
 _STATE_WORDS = 16  # the device buffer: 64 bytes, the struct is the first 48
-_bound = False
-
-
-def lib():
-    """libmdrhip.so with the signatures of include/mdr_optim.h bound (AttributeError if the library lacks one: no fallback)."""
-    global _bound
-    L = _lib.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _bound = True
-    return L
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _dev_index(dev):
-    return dev.index if dev.index is not None else torch.cuda.current_device()
+lib = _lib.binder(SIGNATURES)  # libmdrhip.so with the signatures of include/mdr_optim.h bound
 
 
 def _sizes(sizes):
@@ -169,10 +150,9 @@ class FusedAdam(torch.optim.Optimizer):
                 self._half[id(p)] = p.detach().to(dtype=torch.float16).contiguous()
         self._key, self._table, self._n_chunks, self._workspace = None, None, 0, None
         self.last_lr = None  # the lr of the last mdr_optim_step
-        with torch.cuda.device(self._device):
-            self._state = torch.zeros(_STATE_WORDS, dtype=torch.int32, device=self._device)
-            self._state_f32 = self._state.view(torch.float32)
-            _lib.check(lib().mdr_optim_state_init(_ptr(self._state), scale0, _dev_index(self._device), _lib.current_stream_ptr(self._device)))
+        self._state = torch.zeros(_STATE_WORDS, dtype=torch.int32, device=self._device)
+        self._state_f32 = self._state.view(torch.float32)
+        _lib.call(lib().mdr_optim_state_init, ptr(self._state), scale0, dev=self._device)
 
     def half(self, p):
         """The fp16 copy of parameter p that every step keeps current (fp16_copies)."""
@@ -224,10 +204,9 @@ class FusedAdam(torch.optim.Optimizer):
                 if self._workspace is None:
                     self._workspace = torch.empty(workspace_bytes([r[5] for r in rows]), dtype=torch.uint8, device=dev)
                 self._key = rows
-            _lib.check(L.mdr_optim_step(_ptr(self._table), len(rows), self._n_chunks, _ptr(self._state), lr, self.betas[0], self.betas[1], self.eps,
-                                        self.max_grad_norm, 1 if self._dynamic else 0, self.scale_window, self.max_loss_scale,
-                                        1 if self.zero_grads else 0, _ptr(self._workspace), self._workspace.numel(), _dev_index(dev),
-                                        _lib.current_stream_ptr(dev)))
+            _lib.call(L.mdr_optim_step, ptr(self._table), len(rows), self._n_chunks, ptr(self._state), lr, self.betas[0], self.betas[1], self.eps,
+                      self.max_grad_norm, 1 if self._dynamic else 0, self.scale_window, self.max_loss_scale, 1 if self.zero_grads else 0,
+                      ptr(self._workspace), self._workspace.numel(), dev=dev)
         self.last_lr = lr
         return loss
 
@@ -261,4 +240,4 @@ def momentum_update(params_k, params_q, m, fp16_copies=None):
             host_q, _ = build_table([(qp, 0, 0, 0, 0, n, 0.0) for _, qp, _, n in key])
             _ema_tables[key] = (torch.from_numpy(host_k).to(dev), torch.from_numpy(host_q).to(dev), len(key), n_chunks)
         tk, tq, n_tensors, n_chunks = _ema_tables[key]
-        _lib.check(lib().mdr_optim_ema(_ptr(tk), _ptr(tq), n_tensors, n_chunks, float(m), _dev_index(dev), _lib.current_stream_ptr(dev)))
+        _lib.call(lib().mdr_optim_ema, ptr(tk), ptr(tq), n_tensors, n_chunks, float(m), dev=dev)

@@ -63,23 +63,8 @@ SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 MAX_SEQ_LEN = 512  # the span kernel keeps one row of start / end logits in LDS
 
-_bound = None
-
-
-def lib():
-    """libmdrhip.so with the reader's entry points bound (raises if the library is missing or lacks one)."""
-    global _bound
-    if _bound is None:
-        L = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        _bound = L
-    return _bound
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+lib = _lib.binder(SIGNATURES)  # libmdrhip.so with the signatures of include/mdr_reader.h bound
+_ptr = _lib.ptr
 
 
 def model_family(model_name, config):
@@ -180,10 +165,8 @@ class QAModel(_HipModule):
         need = int(L_.mdr_reader_workspace_bytes(self._h, B, L, NS))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L_.mdr_reader_forward(self._h, _ptr(ids), _ptr(mask), _ptr(tt), _ptr(pm), _ptr(so), B, L, NS,
-                                             -1 if max_ans_len is None else int(max_ans_len), ctypes.byref(o), _ptr(self._ws), self._ws.numel(),
-                                             _lib.current_stream_ptr(dev)))
+        _lib.call(L_.mdr_reader_forward, self._h, _ptr(ids), _ptr(mask), _ptr(tt), _ptr(pm), _ptr(so), B, L, NS, -1 if max_ans_len is None else int(max_ans_len),
+                  ctypes.byref(o), _ptr(self._ws), self._ws.numel(), dev=dev, device_arg=False)
         return out, spans
 
     def __call__(self, batch):
@@ -233,9 +216,7 @@ def span_search(start_logits, end_logits, max_ans_len):
     B, L = s16.shape
     dev = s16.device
     out = (torch.empty(B, dtype=torch.int64, device=dev), torch.empty(B, dtype=torch.int64, device=dev), torch.empty(B, dtype=torch.float16, device=dev))
-    with torch.cuda.device(dev):
-        _lib.check(lib().mdr_reader_span_search(_ptr(s16), _ptr(e16), B, L, int(max_ans_len), *[_ptr(t) for t in out], dev.index,
-                                                _lib.current_stream_ptr(dev)))
+    _lib.call(lib().mdr_reader_span_search, _ptr(s16), _ptr(e16), B, L, int(max_ans_len), *[_ptr(t) for t in out], dev=dev)
     return out
 
 

@@ -30,7 +30,7 @@ SEED = 20240
 CHILD_LIMIT_S = 200
 STREAM_TBS = 6.3
 KERNELS = {"keys_ms": "emb_keys_kernel", "rank_ms": "emb_rank_kernel", "segments_ms": "emb_segments_kernel", "ln_grad_ms": "emb_ln_grad_kernel",
-           "reduce_ms": "emb_reduce_kernel", "scatter_kernel_ms": "emb_scatter_kernel", "colsum_ms": "emb_colsum_kernel"}
+           "reduce_ms": "grad_strand_reduce_kernel", "scatter_kernel_ms": "emb_scatter_kernel", "colsum_ms": "emb_colsum_kernel"}
 
 
 def lengths(tokens, rng):
@@ -209,7 +209,7 @@ def main():
                      f"{r['scatter_bytes'] / 1e6:.1f} | {r['scatter_bytes'] / (r['scatter_ms'] * 1e-3) / 1e12:.2f} | {f4(r, 'call_ms')} | {f4(r, 'call_overwrite_ms')} | "
                      f"{f4(r, 'torch_ms')} | {r['torch_ms'] / r['call_ms']:.2f} | {r['torch_ms'] / r['call_overwrite_ms']:.2f} | {r['max_abs_diff_vs_torch']:.2e} |")
     lines += ["", "Kernel times of one plan and one call (accumulate = 1), from the profiler, ms:", "",
-              "| tokens | emb_keys | emb_rank | emb_segments | emb_ln_grad | emb_reduce | emb_scatter |", "|---|---|---|---|---|---|---|"]
+              "| tokens | emb_keys | emb_rank | emb_segments | emb_ln_grad | grad_strand_reduce | emb_scatter |", "|---|---|---|---|---|---|---|"]
     for r in rows:
         lines.append(f"| {r['tokens']} | " + " | ".join(f4(r, k) for k in ("keys_ms", "rank_ms", "segments_ms", "ln_grad_ms", "reduce_ms", "scatter_kernel_ms")) + " |")
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

@@ -12,7 +12,7 @@ A call is a few tens of microseconds, so one timed step is `--reps` calls betwee
 median of `--iters` steps after 3 warm-up steps. The calls go through the C ABI on preallocated buffers (what a trunk pass would do), torch's
 through preallocated inputs. torch: x = in.float() + res.float() and dy = dy16.float() + dy2.float() (the adds it needs: it fuses neither),
 native_layer_norm_backward in fp32 with the mean and rstd its forward would have saved, and dx.half() where the trunk needs dx16. The kernels
-apart (ln_grad_kernel, ln_grad_reduce_kernel) from the profiler's kernel times. Bytes: what the call must move, every input row read once and
+apart (ln_grad_kernel, grad_strand_reduce_kernel) from the profiler's kernel times. Bytes: what the call must move, every input row read once and
 every output row written once (the [H] vectors and the partial sums left out); TB/s = bytes / call time, beside the ~6.3 TB/s a streaming
 kernel reaches on this device. Every M runs in a child process of its own under a time limit; the first failure stops the run.
 """
@@ -30,7 +30,7 @@ MODES = {0: ("f32", "f16", "f16", ("dx16",)), 1: ("f32", "f32", "f32", ("dx16", 
 SIZE = {"f16": 2, "f32": 4, "dx16": 2, "dx32": 4}
 CHILD_LIMIT_S = 150
 STREAM_TBS = 6.3
-KERNELS = {"main_kernel_ms": "ln_grad_kernel", "reduce_kernel_ms": "ln_grad_reduce_kernel"}
+KERNELS = {"main_kernel_ms": "ln_grad_kernel", "reduce_kernel_ms": "grad_strand_reduce_kernel"}
 
 
 def bytes_moved(M, mode):

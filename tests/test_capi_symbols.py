@@ -21,6 +21,52 @@ def test_header_and_binding_agree():
     assert sorted(_lib.EXPORTED_SYMBOLS) == declared_symbols()
 
 
+# (header, module, table attribute, the header's entry points): every header besides include/mdr_hip.h, bound by the module that owns it
+HEADER_TABLES = [
+    ("mdr_attention_grad.h", "attention", "SIGNATURES", ["mdr_attention_backward", "mdr_attention_backward_workspace_bytes"]),
+    ("mdr_linear_grad.h", "linear", "SIGNATURES", ["mdr_linear_backward", "mdr_linear_backward_chunks", "mdr_linear_backward_workspace_bytes"]),
+    ("mdr_layernorm_grad.h", "layernorm", "SIGNATURES",
+     ["mdr_gather_cls_backward", "mdr_layernorm_backward", "mdr_layernorm_backward_chunks", "mdr_layernorm_backward_workspace_bytes"]),
+    ("mdr_embedding_grad.h", "embedding", "SIGNATURES",
+     ["mdr_embedding_backward", "mdr_embedding_backward_chunks", "mdr_embedding_backward_workspace_bytes", "mdr_embedding_plan",
+      "mdr_embedding_plan_bytes", "mdr_embedding_scatter", "mdr_embedding_scatter_workspace_bytes"]),
+    ("mdr_optim.h", "optim", "SIGNATURES",
+     ["mdr_optim_chunks", "mdr_optim_ema", "mdr_optim_state_init", "mdr_optim_step", "mdr_optim_table_bytes", "mdr_optim_table_fill",
+      "mdr_optim_workspace_bytes"]),
+    ("mdr_inbatch.h", "criterions", "SIGNATURES", ["mdr_inbatch_rank", "mdr_inbatch_workspace_bytes"]),
+    ("mdr_inbatch_loss.h", "criterions", "LOSS_SIGNATURES", ["mdr_inbatch_loss_backward", "mdr_inbatch_loss_forward", "mdr_inbatch_loss_workspace_bytes"]),
+    ("mdr_reader.h", "reader", "SIGNATURES",
+     ["mdr_reader_assemble", "mdr_reader_create", "mdr_reader_forward", "mdr_reader_free", "mdr_reader_span_search", "mdr_reader_workspace_bytes"]),
+]
+
+
+@pytest.mark.parametrize("header,module,attr,expected", HEADER_TABLES, ids=[h[0] for h in HEADER_TABLES])
+def test_header_binding_and_library_agree(header, module, attr, expected):
+    """The header declares exactly what its module's table binds and the library exports, apart from include/mdr_hip.h's table and from
+    every other header's; each signature has the prototype's number of arguments; module.lib() binds."""
+    import importlib
+    from multihop_dense_retrieval_amd import _lib, build
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+    declared = sorted(set(re.findall(r"\b(mdr_[a-z0-9_]+)\s*\(", text)))
+    mod = importlib.import_module("multihop_dense_retrieval_amd." + module)
+    table = getattr(mod, attr)
+    assert sorted(table) == declared == expected
+    assert sorted(getattr(mod, attr.replace("SIGNATURES", "EXPORTED_SYMBOLS"))) == declared
+    assert not set(table) & set(_lib.EXPORTED_SYMBOLS)  # the retrieval table stays what include/mdr_hip.h declares
+    for h, m, a, _ in HEADER_TABLES:
+        if (h, a) != (header, attr):
+            assert not set(table) & set(getattr(importlib.import_module("multihop_dense_retrieval_amd." + m), a)), h
+    for name, (_, args) in table.items():
+        proto = re.search(r"\b" + name + r"\s*\(([^)]*)\)", text).group(1)
+        assert len(args) == proto.count(",") + 1, name
+    lib = ctypes.CDLL(build.build_lib())
+    for name in declared:
+        assert hasattr(lib, name), f"{name} declared in include/{header} but not exported"
+    mod.lib()  # every signature binds
+    if header == "mdr_inbatch_loss.h":  # include/mdr_inbatch.h pulls it in
+        assert '#include "mdr_inbatch_loss.h"' in open(os.path.join(ROOT, "include", "mdr_inbatch.h")).read()
+
+
 def test_library_builds_loads_and_exports_everything():
     from multihop_dense_retrieval_amd import build
     path = build.build_lib()

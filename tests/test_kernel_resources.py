@@ -109,6 +109,7 @@ def test_every_kernel_is_reported(resources):
     assert labels["mips_screen8w_kernel<12,1,3,true>"]["VGPRs"] > 128  # the report really is the wide kernel's (one workgroup per CU)
     assert sum(label.startswith("gemm_quad_kernel<") for label, _ in resources) == 3, sorted(labels)
     assert "attention_ring_kernel" in labels, sorted(labels)
+    assert "grad_strand_reduce_kernel" in labels, sorted(labels)  # one definition serves the LayerNorm and the embedding backward
 
 
 def test_no_kernel_uses_scratch_or_spills(resources):

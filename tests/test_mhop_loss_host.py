@@ -1,9 +1,7 @@
 """CPU: the fp64 statement of the in-batch loss and its gradients (tests/mhop_loss_ref.py) against what the REFERENCE's own mhop_loss and
 dequeue_and_enqueue computed in fp32 (tests/golden/mhop_loss_grad_ref.npz, written by scripts/gen_mhop_loss_grad_golden.py), the derived error
 bound against wrong formulas, and MemoryBank against the reference's queue. No device."""
-import ctypes
 import os
-import re
 import types
 
 import numpy as np
@@ -129,18 +127,3 @@ def test_the_loss_refuses_cpu_tensors():
     o = {k: torch.zeros(2, 32) for k in ref.KEYS}
     with pytest.raises(RuntimeError, match="HIP device only"):
         criterions.mhop_loss_outputs(o, types.SimpleNamespace(fp16=False))
-
-
-def test_loss_header_binding_and_library_agree():
-    """include/mdr_inbatch_loss.h declares exactly what criterions.LOSS_SIGNATURES binds and the library exports; include/mdr_inbatch.h pulls it in."""
-    from multihop_dense_retrieval_amd import _lib, build, criterions
-    inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "mdr_inbatch_loss.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(mdr_[a-z0-9_]+)\s*\(", text)))
-    assert sorted(criterions.LOSS_EXPORTED_SYMBOLS) == declared == ["mdr_inbatch_loss_backward", "mdr_inbatch_loss_forward", "mdr_inbatch_loss_workspace_bytes"]
-    assert not set(criterions.LOSS_EXPORTED_SYMBOLS) & (set(criterions.EXPORTED_SYMBOLS) | set(_lib.EXPORTED_SYMBOLS))
-    assert '#include "mdr_inbatch_loss.h"' in open(os.path.join(inc, "mdr_inbatch.h")).read()
-    lib = ctypes.CDLL(build.build_lib())
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/mdr_inbatch_loss.h but not exported"
-    criterions.lib()

@@ -2,7 +2,6 @@
 the checkpoint schema against the reference QAModel's, the refusal of model families the kernels do not compute, and the span
 search's torch restatement (the formula of scripts/train_qa.py predict(), used by the GPU tests as the bit-exact yardstick) against
 an independent walk over the band."""
-import ctypes
 import os
 import re
 import types
@@ -12,21 +11,6 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(mdr_[a-z0-9_]+)\s*\(", text)))
-
-
-def test_reader_header_binding_and_library_agree():
-    from multihop_dense_retrieval_amd import _lib, build, reader
-    assert sorted(reader.EXPORTED_SYMBOLS) == _declared("mdr_reader.h")
-    assert not set(reader.EXPORTED_SYMBOLS) & set(_lib.EXPORTED_SYMBOLS)  # the retrieval table stays what include/mdr_hip.h declares
-    lib = ctypes.CDLL(build.build_lib())
-    for name in reader.EXPORTED_SYMBOLS:
-        assert hasattr(lib, name), f"{name} declared in include/mdr_reader.h but not exported"
-    reader.lib()  # every signature binds
 
 
 def test_config_struct_matches_header():
