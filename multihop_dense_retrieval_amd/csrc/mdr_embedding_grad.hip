@@ -30,7 +30,8 @@
 //   3. dy = fp32(dy16) + fp32(dy2): one rounded add, none when only one is given.
 //   4. xhat = (x - mu) * rstd, a = dy * g: one rounding each.
 //   5. c1 = wave_sum(sum of a) / H and c2 = wave_sum(sum of a * xhat) / H: every term passes through at most H / 64 + 6 additions.
-//   6. d = rstd * ((a - c1) - xhat * c2): not rounded again; the workspace holds it in fp32.
+//   6. d = rstd * ((a - c1) - xhat * c2): not rounded again; the workspace holds it in fp32. dtype0 adds THAT value (the add is never fused with
+//      the product), so that it has the bits of emb_colsum_kernel over the stored d.
 //   7. A table row: the pieces' sums (at most P - 1 roundings: the first add is to 0), the pieces in order (at most ceil(n / P) - 1
 //      roundings), the old value (one): at most P - 1 + ceil(n / P) + 1 additions per term.
 //   8. dg += dy * xhat, db += dy and dtype0 += d per token in the wave's order; ((w0 + w1) + w2) + w3 over the waves; the chunks strand
@@ -347,7 +348,12 @@ emb_ln_grad_kernel(const long long* __restrict__ ids, const int* __restrict__ to
         for (int i = 0; i < kEgPerLane; ++i)
             if (i < nl) {
                 const float d = rstd * ((dy[i] - c1) - x[i] * c2);
-                sums[2][i] += d;
+                {
+                    // dtype0 adds the d that is STORED: fused into the product, the add took rstd * (..) unrounded, and from the second token
+                    // of a wave on (rows_per_chunk > 4) dtype0 no longer had the bits of emb_colsum_kernel over the same d
+#pragma clang fp contract(off)
+                    sums[2][i] += d;
+                }
                 d32[off + lane + 64 * i] = d;
             }
     }

@@ -54,6 +54,15 @@ DY_FORMS = ("dy16", "dy2_f32", "both")
 HS = [64, 192, 768, 1024]
 # (B, L): token counts 1, 3, 4, 5 and a few hundred; cap = B L > total in every one (make_pack masks at least one position out)
 BL_SWEEP = [(1, 2), (2, 2), (1, 5), (2, 3), (7, 50)]
+# A batch of 150 sequences, the README's training batch, at 25 positions: cap = 3750 and about 1900 tokens, so that at H = 768 and 1024 a wave
+# of emb_ln_grad_kernel walks three tokens with dg, db and dtype0 in registers (rows_per_chunk = 12), hundreds of chunks lie behind `total`,
+# and the longest table rows own more than 8 P tokens: emb_scatter_kernel sums 8 pieces per round and goes round again. (kind, pad_row): with
+# "random" the longest rows of both tables are the pad id's and the pad position's, which only pad_row = -1 sums; with "equal" one word row
+# owns every token. assert_large() states the properties. The host emulation runs over all of it (under a second a case).
+BL_LARGE = (150, 25)
+HS_LARGE = [768, 1024]
+KINDS_LARGE = [("random", -1), ("equal", 1)]
+ROUND = 8 * P                 # tokens of one round of emb_scatter_kernel: kEgScatterWaves pieces
 
 
 def chunks(cap, H):
@@ -63,6 +72,27 @@ def chunks(cap, H):
     most = min(MAX_CHUNKS, MAX_PARTIAL_BYTES // (12 * H))
     rpc = ((cap + most - 1) // most + 3) // 4 * 4
     return (cap + rpc - 1) // rpc, rpc
+
+
+def longest_summed_segments(case):
+    """(word, pos): the most tokens a table row owns that the scatter sums (pad_row is skipped)"""
+    out = []
+    for keys in rows(case):
+        n = np.bincount(keys)
+        if 0 <= case["pad_row"] < len(n):
+            n[case["pad_row"]] = 0
+        out.append(int(n.max(initial=0)))
+    return tuple(out)
+
+
+def assert_large(case, chunks_of=None):
+    """A case at BL_LARGE: rows_per_chunk >= 12, whole chunks behind `total`, and a longest summed segment of more than one round in the
+    word table (pad_row = -1: in both tables). Returns (S, rows_per_chunk, longest word segment, longest position segment)."""
+    cap, H = len(case["tok_src"]), case["word"].shape[1]
+    S, rpc = (chunks_of or chunks)(cap, H)
+    lw, lp = longest_summed_segments(case)
+    assert rpc >= 3 * WAVES and case["total"] + rpc < (S - 1) * rpc and lw > ROUND and (lp > ROUND or case["pad_row"] >= 0), (cap, H, S, rpc, case["total"], lw, lp)
+    return S, rpc, lw, lp
 
 
 def plan_layout(cap):

@@ -61,6 +61,11 @@ MUTATIONS = ("no_c1", "no_c2", "no_rstd", "no_g", "stats_without_residual", "no_
 # The shapes of the GPU tests (the host test runs the emulation over the same ones).
 HS = [64, 192, 256, 768, 1024]
 M_SWEEP = [1, 2, 3, 4, 5, 7, 8, 9, 300]
+# (H, M) at training row counts: the smallest M at the shipping widths at which a wave of ln_grad_kernel walks three rows or more with dg and db
+# carried in registers (rows_per_chunk >= 12), the last chunk is ragged, and a strand of grad_strand_reduce_kernel adds more than sixteen
+# chunks (S > 16 * 16). assert_large() states the properties; the host test holds it against the library's split. The host emulation runs
+# over every one of them (under a second each).
+LARGE_HM = [(768, 5461), (1024, 4101), (192, 8200), (256, 8200)]
 # (in, residual, dy16, dy2). The first three are the trunk's: post_ln of csrc/mdr_encoder_trunk.inl with residual_fp32 = 0 (fp32 sums + the fp16
 # stream; both gradients come back in fp16), 1 (fp32 sums + the fp32 stream; the stream's gradient in fp32) and 2 (fp16 Linear output + the fp32
 # stream). The others complete the operand combinations.
@@ -79,6 +84,26 @@ def chunks(M, H):
     cap = min(MAX_CHUNKS, MAX_PARTIAL_BYTES // (8 * H))
     rpc = ((M + cap - 1) // cap + 3) // 4 * 4
     return (M + rpc - 1) // rpc, rpc
+
+
+def assert_large(shapes=None, chunks_of=None):
+    """Every shape of LARGE_HM: rows_per_chunk >= 12, M no multiple of it, S > 256. Returns [(H, M, S, rows_per_chunk)]."""
+    out = []
+    for H, M in (LARGE_HM if shapes is None else shapes):
+        S, rpc = (chunks_of or chunks)(M, H)
+        assert rpc >= 3 * WAVES and M % rpc != 0 and S > STRANDS * STRANDS, (H, M, S, rpc)
+        out.append((H, M, S, rpc))
+    return out
+
+
+def large_ms(M, H):
+    """valid-row counts for a shape of LARGE_HM: none; one inside a chunk in the middle, with hundreds of whole chunks behind it (a call on
+    those rows alone is cut otherwise: its sums are compared through the bound); M - 2, for which a call on those rows alone is cut alike
+    (compared bit for bit); all"""
+    S, rpc = chunks(M, H)
+    ms = (0, (S // 2) * rpc + rpc - 1, M - 2, M)
+    assert ms[1] % rpc and ms[1] + 100 * rpc < M and chunks(ms[2], H)[1] == rpc != chunks(ms[1], H)[1], (M, H, ms)
+    return ms
 
 
 def split_ms(H=64):

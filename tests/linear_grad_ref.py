@@ -57,6 +57,29 @@ MUTATIONS = ("extra_row", "missing_row", "drop_last_chunk", "dw_transposed", "dx
 SMALL_NK = [(64, 64), (192, 64), (64, 192), (128, 128), (256, 384)]
 MODEL_NK = [(768, 768), (2304, 768), (3072, 768), (768, 3072)]
 M_SWEEP = [1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 300]   # 63 .. 65 and 127 .. 129: -1, 0, +1 around one and two chunks of 64 rows
+# (M, N, K) at training row counts: the smallest M at which a chunk of lg_wgrad_kernel holds three slabs or more, so that its register double
+# buffer reaches the steady state (put slab i, issue i + 1, compute i, put i + 1, ...), with S >= 3 partials to reduce and a ragged last
+# chunk. The three wide model Linears (3, 7 and 9 slabs per chunk), a small-tile shape, the 64-wide remainder quarter on either side of a
+# 128 tile, and FFN2 at the M from which its dX leaves the one-tile GEMMs (17 slabs per chunk). assert_large() states the properties; the
+# host test holds it against the library's split, so a change of the split constants fails there instead of shrinking the coverage.
+# The host emulation runs over every one of them (a few seconds each).
+LARGE_MNK = [(2051, 768, 768), (2051, 2304, 768), (2051, 3072, 768), (11011, 256, 384), (33000, 64, 192), (33000, 192, 64), (4099, 768, 3072)]
+
+
+def assert_large(shapes=None, chunks_of=None):
+    """Every shape of LARGE_MNK: rows_per_chunk >= 192 (three slabs: the prefetch branch of the slab loop is taken twice in a row), S >= 3,
+    M no multiple of the slab and the last chunk shorter than the others. Over the list: some last chunk ends on FEWER slabs than the others
+    (the loop ends early) and some on as many with a partial last slab (the zero-fill inside the steady state). Returns
+    [(M, N, K, S, rows_per_chunk, rows of the last chunk)]."""
+    out = []
+    for M, N, K in (LARGE_MNK if shapes is None else shapes):
+        S, rpc = (chunks_of or chunks)(M, N, K)
+        last = M - (S - 1) * rpc
+        assert rpc >= 3 * SLAB and S >= 3 and M % SLAB != 0 and 0 < last < rpc, (M, N, K, S, rpc, last)
+        out.append((M, N, K, S, rpc, last))
+    fewer = [(last + SLAB - 1) // SLAB < rpc // SLAB for *_, rpc, last in out]
+    assert any(fewer) and not all(fewer), out
+    return out
 
 
 def chunks(M, N, K):

@@ -3,13 +3,15 @@ numpy's stable argsort, the segmented sum against integer sums, the whole call a
 packed_embedding_layer_norm (multihop_dense_retrieval_amd/embedding.py) on top of it. EVERY element is compared; nothing is averaged.
 
 Two bars. The plan is integers: EQUAL. Where the arithmetic is exact the result must be EQUAL too: the tables and dtype0 of a d on the
-grid of multiples of 1/8 (any fp32 sum of a few hundred such values of magnitude at most 4 is exact in any order). Everywhere else the bar
+grid of multiples of 1/8 (any fp32 sum of a few thousand such values of magnitude at most 4 is exact in any order). Everywhere else the bar
 is embedding_grad_ref's bound, derived from the formats and the rounding points listed in csrc/mdr_embedding_grad.hip and shown on the host
 (tests/test_embedding_grad_host.py) to hold a second implementation of the dataflow and to throw out each defect. No tolerance here was read
 off a device. Each bound check prints `SHARE ...`, the largest part of the bound the device used.
 
 The tables are small (vocab 97, max_pos 40), so that collisions are the rule. Every float output starts as a finite sentinel (or the old
 values) with guard rows behind it, the plan as ISENTINEL; tok_src / tok_pid hold ISENTINEL from `total` on, which no kernel may dereference.
+Token counts: 1, 3, 4, 5 and a few hundred; and embedding_grad_ref.BL_LARGE, a batch of 150 sequences, where a wave walks three tokens of a
+chunk, chunks lie behind `total` and table rows own more than the 8 pieces that the scatter sums per round (segments of up to 232 pieces).
 """
 import ctypes
 
@@ -213,6 +215,24 @@ def test_scatter_on_the_grid_equals_the_integer_sums(H):
             check_exact(case, d32, plan, f"{name} H={H} pad_row={pad_row}")
 
 
+@pytest.mark.parametrize("H", [64, 768])
+def test_scatter_rounds_on_the_grid_equal_the_integer_sums(H):
+    """segments of 8 P, 8 P + 1, 16 P - 1, 16 P + 1 and 40 P + 5 tokens -- whole rounds of eight pieces, a round of one piece, a ragged last
+    round, six rounds -- and one segment of 3700 tokens (232 pieces, 29 rounds), both accumulate modes, pad_row 1 and -1"""
+    tables = ref.make_tables("unit", H, 2)
+    counts = {3: 8 * P, 5: 8 * P + 1, 7: 16 * P - 1, 9: 16 * P + 1, 11: 40 * P + 5, 1: 4, 0: 2}
+    assert ref.ROUND == 8 * P
+    for name, pk in (("rounds", ref.make_flat(counts, 15)), ("one-long-segment", ref.make_flat({7: 3700}, 16))):
+        for pad_row in (1, -1):
+            case = dict(pk, **tables, pad_row=pad_row)
+            assert ref.longest_summed_segments(case)[0] == max(counts.values() if name == "rounds" else [3700])
+            d32 = ref.grid((len(pk["tok_src"]), H), 14)
+            d32[pk["total"]:] = np.nan  # rows at or behind total are never read as values
+            plan, words = build_plan(case)
+            ref.assert_plan(words, case, name)
+            check_exact(case, d32, plan, f"{name} H={H} pad_row={pad_row}")
+
+
 def test_scatter_total_zero_and_real_table_height():
     """total = 0: zeros, or the old bits with accumulate. vocab = 50265, H = 64, accumulate 1 into a table of SENTINEL: the rows that own
     tokens hold sum + SENTINEL, every other row and pad_row keep their bits."""
@@ -246,10 +266,19 @@ def test_scatter_total_zero_and_real_table_height():
 def test_a_row_depends_on_its_own_tokens_in_order_only():
     """the same ids and d rows interleaved with tokens of other ids: the rows of the original ids keep their bits (d is NOT on the grid
     here: the sums round, so the order and the pieces matter)"""
+    row_depends_on_its_own_tokens(90, 2 * P)
+
+
+def test_a_row_depends_on_its_own_tokens_in_order_only_over_several_rounds():
+    """the same with hot ids and positions that own more than 8 P tokens: the pieces of the later rounds are the same tokens in the same order"""
+    row_depends_on_its_own_tokens(600, ref.ROUND)
+
+
+def row_depends_on_its_own_tokens(size, least):
     H = 192
     tables = ref.make_tables("unit", H, 2)
     rng = np.random.default_rng(12)
-    base_ids = rng.choice(np.asarray([3, 5, 7, 9]), size=90, p=[0.05, 0.15, 0.3, 0.5])
+    base_ids = rng.choice(np.asarray([3, 5, 7, 9]), size=size, p=[0.05, 0.15, 0.3, 0.5])
     n = len(base_ids)
     d_base = rng.standard_normal((n, H)).astype(np.float32)
 
@@ -269,7 +298,7 @@ def test_a_row_depends_on_its_own_tokens_in_order_only():
     db_[where] = d_base
     b = flat(ids_b, pid_b)
     gb = run_scatter(b, db_, build_plan(b)[0])
-    assert max(np.bincount(base_ids)) > 2 * P
+    assert max(np.bincount(base_ids)) > least and (least <= 2 * P or min(np.bincount(np.arange(n) % 4)) > least)
     assert np.array_equal(bits(ga["dword"][[3, 5, 7, 9]]), bits(gb["dword"][[3, 5, 7, 9]]))
     assert np.array_equal(bits(ga["dpos"][:4]), bits(gb["dpos"][:4]))
     assert not np.array_equal(bits(ga["dtype0"]), bits(gb["dtype0"]))
@@ -319,11 +348,37 @@ def test_families_within_the_derived_bound(H, family):
     print(f"SHARE kernel=embedding_backward family={family} H={H} " + " ".join(f"{k}={v:.4f}" for k, v in worst.items()))
 
 
-@pytest.mark.parametrize("H", [192, 768])
-def test_two_halves_agree_and_two_runs_give_the_same_bits(H):
+LARGE = [pytest.param(H, kind, pad_row, id=f"H{H}-{kind}") for H in ref.HS_LARGE for kind, pad_row in ref.KINDS_LARGE]
+
+
+def large_case(family, H, kind, pad_row, seed):
+    """a case at BL_LARGE with its properties asserted against the LIBRARY's split"""
+    case = ref.make_case(family, H, *ref.BL_LARGE, seed, kind=kind, pad_row=pad_row)
+    assert ref.assert_large(case, emb().backward_chunks) == ref.assert_large(case)
+    return case
+
+
+@pytest.mark.parametrize("family", ref.FAMILIES)
+@pytest.mark.parametrize("H,kind,pad_row", LARGE)
+def test_families_within_the_derived_bound_at_training_token_counts(H, kind, pad_row, family):
+    """test_families_within_the_derived_bound at BL_LARGE: every element of the six outputs on every family, with a wave walking three tokens
+    of a chunk, chunks behind total and segments of more than one round; NaN and Inf in the dy rows at or behind total change nothing"""
+    case = large_case(family, H, kind, pad_row, 11)
+    label = f"family={family} H={H} B={ref.BL_LARGE[0]} L={ref.BL_LARGE[1]} both {kind} pad_row={pad_row}"
+    print(f"SEGMENTS {label} (S, rows_per_chunk, longest word, longest pos) = {ref.assert_large(case)} total = {case['total']}")
+    got = run_backward(case)
+    check_bound(got, ref.reference_and_bound(case), label)
+    bad = run_backward(poison(case))
+    for k in got:
+        assert np.array_equal(bits(got[k]), bits(bad[k])), (label, k, "NaN / Inf behind total changed the result")
+
+
+@pytest.mark.parametrize("H,B,L,kind,pad_row", [pytest.param(192, 7, 50, "range", 1, id="192"), pytest.param(768, 7, 50, "range", 1, id="768")] +
+                         [pytest.param(H, *ref.BL_LARGE, kind, pad_row, id=f"H{H}-{kind}") for H in ref.HS_LARGE for kind, pad_row in ref.KINDS_LARGE])
+def test_two_halves_agree_and_two_runs_give_the_same_bits(H, B, L, kind, pad_row):
     """the scatter alone on the d the backward wrote gives the backward's tables and dtype0; two runs, a larger workspace and each output
     alone give the same bits"""
-    case = ref.make_case("unit", H, 7, 50, 29, kind="range")
+    case = large_case("unit", H, kind, pad_row, 29) if (B, L) == ref.BL_LARGE else ref.make_case("unit", H, B, L, 29, kind=kind, pad_row=pad_row)
     pk = pack_dev(case)
     plan = build_plan(case, pk)[0]
     a, b, c = run_backward(case, plan, pk=pk), run_backward(case, plan, pk=pk), run_backward(case, plan, pk=pk, ws_extra=4096 + 16)
@@ -358,6 +413,31 @@ def test_total_says_how_many_tokens_exist(H):
         assert np.array_equal(bits(got["d"]), bits(full["d"][:m]))
     over = run_backward(dict(case, total=cap + 7, tok_src=np.where(case["tok_src"] < 0, 0, case["tok_src"]), tok_pid=np.where(case["tok_pid"] < 0, 0, case["tok_pid"])))
     assert over["d"].shape[0] == cap and np.isfinite(over["dword"]).all()  # (total is clamped to cap)
+
+
+@pytest.mark.parametrize("H,kind,pad_row", LARGE)
+def test_total_says_how_many_tokens_exist_at_training_token_counts(H, kind, pad_row):
+    """The same at BL_LARGE with *total = 0, inside the first chunk, inside a chunk with whole chunks of valid tokens on either side, and one
+    short: d and the tables have the bits of the call on the first m tokens alone; that call's cap = m + 1 cuts its rows otherwise
+    (rows_per_chunk 4, not 12), so dtype0, dg and db are held to the derived bound of the first m tokens instead."""
+    case = large_case("unit", H, kind, pad_row, 31)
+    full = run_backward(case)
+    S, rpc = ref.chunks(len(case["tok_src"]), H)
+    for m in (0, 5, 50 * rpc + 7, case["total"] - 1):
+        cut = dict(case, total=m)
+        got = run_backward(poison(cut))
+        if m == 0:
+            assert all(not got[k].any() for k in ("dword", "dpos", "dtype0", "dg", "db"))
+            continue
+        short = dict(cut, tok_src=case["tok_src"][:m + 1].copy(), tok_pid=case["tok_pid"][:m + 1].copy(),
+                     dy16=case["dy16"][:m + 1], dy2=case["dy2"][:m + 1])  # cap = m + 1: the token at m exists in the buffers only
+        alone = run_backward(short)
+        assert ref.chunks(m + 1, H)[1] != rpc and 0 < m < case["total"]
+        for k in ("d", "dword", "dpos"):
+            assert np.array_equal(bits(got[k]), bits(alone[k])), (m, k)
+        assert np.array_equal(bits(got["d"]), bits(full["d"][:m]))
+        check_bound({k: got[k] for k in ("dtype0", "dg", "db")}, {k: v for k, v in ref.reference_and_bound(cut).items() if k in ("dtype0", "dg", "db")},
+                    f"total={m} H={H} {kind}")
 
 
 def test_nan_in_a_valid_row_reaches_only_what_it_touches():

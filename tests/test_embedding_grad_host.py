@@ -88,6 +88,24 @@ def test_emulation_stays_inside_the_bound(H, family):
     print(f"RATIO emulation H={H} {family}: worst |err| / bound " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
 
 
+@pytest.mark.parametrize("family", ref.FAMILIES)
+@pytest.mark.parametrize("kind,pad_row", ref.KINDS_LARGE)
+@pytest.mark.parametrize("H", ref.HS_LARGE)
+def test_emulation_stays_inside_the_bound_at_training_token_counts(H, kind, pad_row, family):
+    """The same at BL_LARGE (the GPU test's cases): three tokens per wave and chunk, chunks behind total, segments of more than one round of
+    eight pieces; with and without old values. The split of the case is the LIBRARY's."""
+    from multihop_dense_retrieval_amd import embedding
+    case = ref.make_case(family, H, *ref.BL_LARGE, 11, kind=kind, pad_row=pad_row)
+    assert ref.assert_large(case, embedding.backward_chunks) == ref.assert_large(case)
+    rb = ref.reference_and_bound(case)
+    for old in (None, old_values(case, 12)):
+        if old is not None:
+            rb = ref.reference_and_bound(case, old=old)
+        shares = ref.worst_shares(ref.emulate(case, old=old, accumulate=old is not None), rb)
+        assert max(shares.values()) <= 1.0, (H, kind, family, old is not None, shares)
+    print(f"RATIO emulation H={H} {kind} {family}: worst |err| / bound " + ", ".join(f"{k} {v:.3g}" for k, v in shares.items()))
+
+
 def test_emulated_scatter_on_the_grid_is_exact():
     """segments of 1, P - 1, P, P + 1, 2 P + 1 tokens: the emulated pieces give the integer sums"""
     P = ref.P
@@ -99,6 +117,14 @@ def test_emulated_scatter_on_the_grid_is_exact():
     assert np.array_equal(ref.emulate_scatter(d32, wid, ref.VOCAB, 1), exact["dword"])
     assert np.array_equal(ref.emulate_scatter(d32, prow, ref.MAX_POS, 1), exact["dpos"])
     assert not exact["dword"][1].any() and exact["dword"][11].any()
+    # and over several rounds of eight pieces (the GPU test's "rounds" case)
+    pk = ref.make_flat({3: 8 * P, 5: 8 * P + 1, 7: 16 * P - 1, 9: 16 * P + 1, 11: 40 * P + 5, 1: 4, 0: 2}, 15)
+    case = dict(pk, **ref.make_tables("unit", 64, 7), pad_row=-1)
+    d32 = ref.grid((len(pk["tok_src"]), 64), 14)
+    wid, prow = ref.rows(case)
+    exact = ref.exact_tables(case, d32)
+    assert np.array_equal(ref.emulate_scatter(d32, wid, ref.VOCAB, -1), exact["dword"]) and np.array_equal(ref.emulate_scatter(d32, prow, ref.MAX_POS, -1), exact["dpos"])
+    assert ref.longest_summed_segments(case)[0] == 40 * P + 5 > 5 * ref.ROUND
 
 
 @pytest.mark.parametrize("mutation", ref.MUTATIONS)

@@ -13,7 +13,8 @@ Every output starts as a finite sentinel: dx16 and dx32 with 64 guard rows on bo
 which must keep their bits in every call of this file, as must the rows at or behind the valid count. Shapes: H = 64 and 192 (the generic
 path with 1 and 3 elements per lane), 256 and 768 (the 16-byte path with 1 and 3 groups), 1024 (the limit); M = 1 .. 9 around the four waves
 of a workgroup and one and two chunks, 300, and for H = 64 two M found by calling chunks() whose chunks hold >= 8 rows, do not divide M
-and number >= 3.
+and number >= 3; and layernorm_grad_ref.LARGE_HM, the shipping widths at the smallest training row counts at which a wave walks three rows
+with dg and db in registers, the last chunk is ragged and a strand of the reduction adds more than sixteen chunks.
 """
 import ctypes
 
@@ -129,6 +130,29 @@ def test_some_tested_shape_is_split():
     assert any(S == 1 for *_, S, _ in split)  # and the workgroup that writes dg and db itself
 
 
+LARGE_HM = [pytest.param(H, M, id=f"H{H}-M{M}") for H, M in ref.LARGE_HM]
+
+
+def test_large_shapes_walk_rows_and_fill_the_strands():
+    """LARGE_HM against the LIBRARY's split: rows_per_chunk >= 12, a ragged last chunk, S > 16 * 16 (layernorm_grad_ref.assert_large)"""
+    from multihop_dense_retrieval_amd import layernorm
+    assert ref.assert_large(chunks_of=layernorm.backward_chunks) == ref.assert_large()
+    S, rpc = ref.chunks(5461, 768)
+    m = ref.large_ms(5461, 768)[2]
+    assert (S - 2) * rpc < m < (S - 1) * rpc  # test_rows_behind_m_dev_do_not_exist: m cuts the last chunk but one, the last one lies whole behind it
+
+
+@pytest.mark.parametrize("combo", ref.TRUNK_COMBOS, ids=lambda c: "-".join(map(str, c)))
+@pytest.mark.parametrize("family", list(ref.FAMILIES))
+@pytest.mark.parametrize("H,M", LARGE_HM)
+def test_families_within_the_derived_bound_at_training_row_counts(H, M, family, combo):
+    """test_families_within_the_derived_bound at LARGE_HM: every family on the three trunk combinations, the unit family also under 2^8;
+    one combination per case, so that a case holds one fp64 reference (two for the unit family)"""
+    for scale in ((1.0, 256.0) if family == "unit" else (1.0,)):
+        case = ref.make_case(family, combo, M, H, 11, scale)
+        check_bound(run(**case), ref.reference_and_bound(**case), M, f"family={family} H={H} M={M} combo={'-'.join(map(str, combo))} scale={scale:g}")
+
+
 @pytest.mark.parametrize("family", list(ref.FAMILIES))
 @pytest.mark.parametrize("H", ref.HS)
 def test_families_within_the_derived_bound(H, family):
@@ -184,6 +208,21 @@ def test_db_on_the_grid_equals_the_integer_column_sums(H):
                 assert np.array_equal(got, exact_db(case, mm)), (M, H, combo, m, "overwrite")
 
 
+@pytest.mark.parametrize("H,M", LARGE_HM)
+def test_db_on_the_grid_equals_the_integer_column_sums_at_training_row_counts(H, M):
+    """test_db_on_the_grid_equals_the_integer_column_sums at LARGE_HM: the row walk of a wave, 342 to 684 chunks through the sixteen strands and
+    the ragged last chunk without a tolerance; valid-row counts inside a chunk with hundreds of whole chunks, and with one, behind them"""
+    old = ref.grid((H,), 5, 4.0)
+    for combo in ref.TRUNK_COMBOS[:2]:
+        case = grid_case(M, H, 3, combo)
+        for m in (None,) + ref.large_ms(M, H)[:3]:
+            mm = M if m is None else m
+            got = run(**case, m=m, outs="gb")["db"]
+            assert np.array_equal(bits(got), bits(exact_db(case, mm))), (M, H, combo, m, ref.chunks(M, H))
+            got = run(**case, m=m, outs="gb", old_db=old, old_dg=old, accumulate=True)["db"]
+            assert np.array_equal(got, exact_db(case, mm, old)), (M, H, combo, m, "accumulate")
+
+
 @pytest.mark.parametrize("H", ref.HS)
 def test_zero_dy_and_zero_gamma_give_exact_zeros(H):
     old_dg, old_db = ref.grid((H,), 6, 4.0) + 0.125, ref.grid((H,), 7, 4.0) + 0.125  # (no zero among them: an old -0 would not keep its sign)
@@ -215,10 +254,10 @@ def poison(case, m):
 
 
 @pytest.mark.parametrize("combo", ref.TRUNK_COMBOS, ids=lambda c: "-".join(map(str, c)))
-@pytest.mark.parametrize("H,M", [(192, 9), (768, 300), (64, ref.split_ms(64)[0] + 2)])
+@pytest.mark.parametrize("H,M", [(192, 9), (768, 300), (64, ref.split_ms(64)[0] + 2), (768, 5461)])
 def test_rows_behind_m_dev_do_not_exist(H, M, combo):
-    """m in {0, 1, M - 1, M, M + 7}, rows at or behind m NaN and Inf in every input: the results are those of the call on the first m rows alone,
-    bit for bit (the two calls cut the rows alike wherever rows_per_chunk agrees, and the chunks behind m add +0); m = 0 gives zeros, or the old
+    """m in {0, 1, M - 1, M, M + 7} (768 x 5461: layernorm_grad_ref.large_ms -- inside a chunk, with hundreds of whole chunks and with one behind
+    it), rows at or behind m NaN and Inf in every input: the results are those of the call on the first m rows alone, bit for bit (the two calls cut the rows alike wherever rows_per_chunk agrees, and the chunks behind m add +0); m = 0 gives zeros, or the old
     bits with accumulate; m = M + 7 is clamped to M. dx rows at or behind m keep the sentinel (run() asserts it)."""
     case = ref.make_case("unit", combo, M, H, 17)
     old_dg, old_db = ref.grid((H,), 18, 4.0) + 0.125, ref.grid((H,), 19, 4.0) + 0.125
@@ -226,7 +265,7 @@ def test_rows_behind_m_dev_do_not_exist(H, M, combo):
     over = run(**case, m=M + 7)
     for k in full:
         assert np.array_equal(bits(over[k]), bits(full[k])), (k, "m = M + 7")
-    for m in (0, 1, M - 1, M):
+    for m in (ref.large_ms(M, H) if (H, M) in ref.LARGE_HM else (0, 1, M - 1, M)):
         got = run(**poison(case, m), m=m)
         if m == 0:
             assert not got["dg"].any() and not got["db"].any()
@@ -261,7 +300,7 @@ def test_nan_in_a_valid_row_reaches_only_what_it_touches(H, M):
         assert np.array_equal(bits(got[k][cols]), bits(clean[k][cols])), k
 
 
-@pytest.mark.parametrize("H,M", [(192, 300), (768, 300), (64, ref.split_ms(64)[1])])
+@pytest.mark.parametrize("H,M", [(192, 300), (768, 300), (64, ref.split_ms(64)[1]), (192, 8200)])
 def test_two_runs_and_a_larger_workspace_give_the_same_bits(H, M):
     for combo in ref.TRUNK_COMBOS:
         case = ref.make_case("unit", combo, M, H, 29)
@@ -270,7 +309,7 @@ def test_two_runs_and_a_larger_workspace_give_the_same_bits(H, M):
             assert np.array_equal(bits(a[k]), bits(b[k])) and np.array_equal(bits(a[k]), bits(c[k])), (combo, k)
 
 
-@pytest.mark.parametrize("H,M", [(192, 300), (1024, 300), (64, ref.split_ms(64)[0])])
+@pytest.mark.parametrize("H,M", [(192, 300), (1024, 300), (64, ref.split_ms(64)[0]), (1024, 4101)])
 def test_permuting_the_rows_permutes_dx_and_leaves_db_on_the_grid(H, M):
     """a row's dx bits depend on that row's inputs and g only: not on where the row stands, nor on M"""
     case = grid_case(M, H, 31)

@@ -97,6 +97,23 @@ def test_emulation_stays_inside_the_bound(H, family):
     print(f"RATIO emulation H={H} {family}: worst |err| / bound " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
 
 
+@pytest.mark.parametrize("family", list(ref.FAMILIES))
+@pytest.mark.parametrize("H,M", ref.LARGE_HM, ids=lambda v: str(v))
+def test_emulation_stays_inside_the_bound_at_training_row_counts(H, M, family):
+    """The same at LARGE_HM, where a wave walks three rows and the strands add hundreds of chunks: the three trunk combinations, one of them
+    with a valid-row count in the middle and old values; the unit family under the loss scale, as in training. One fp64 reference per
+    combination keeps a case at a few seconds."""
+    worst = dict.fromkeys(OUTPUTS, 0.0)
+    old_dg, old_db = ref.grid((H,), 12, 4.0), ref.grid((H,), 13, 4.0)
+    for combo, (m, odg, odb) in zip(ref.TRUNK_COMBOS, ((None, None, None), (None, None, None), (ref.large_ms(M, H)[1], old_dg, old_db))):
+        case = ref.make_case(family, combo, M, H, 11, 256.0 if family == "unit" else 1.0)
+        rb = ref.reference_and_bound(**case, m=m, old_dg=odg, old_db=odb)
+        for k, (w, at) in _ratios(ref.emulate(**case, m=m, old_dg=odg, old_db=odb), rb).items():
+            assert w <= 1.0, (M, H, family, combo, m, k, w, at)
+            worst[k] = max(worst[k], w)
+    print(f"RATIO emulation H={H} M={M} {family}: worst |err| / bound " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+
+
 @pytest.mark.parametrize("mutation", ref.MUTATIONS)
 def test_each_mutation_leaves_the_bound(mutation):
     """The bound is worth something: every formula, operand, row-count, chunk and accumulate defect is thrown out."""
@@ -134,6 +151,7 @@ def test_split_is_a_function_of_the_shape_and_workspace_covers_it():
     for M in ref.split_ms(64):
         S, rpc = ref.chunks(M, 64)
         assert S >= 3 and rpc >= 8 and M % rpc
+    assert ref.assert_large(chunks_of=layernorm.backward_chunks) == ref.assert_large()  # the large shapes keep their properties under the LIBRARY's split
     for M, H in ((0, 64), (-1, 64), (5, 0), (5, 32), (5, 96), (5, 1088), (5, -64)):
         assert lib.mdr_layernorm_backward_workspace_bytes(M, H, 3) == 0
         assert layernorm.backward_chunks(M, H) == (0, 0) == ref.chunks(M, H)

@@ -12,7 +12,9 @@ off a device.
 Every output starts as a finite sentinel: dx with 64 guard rows on both sides, dw and db with 64 guard elements on both sides, which must
 keep their bits in every call of this file. Shapes: a whole 64 x 64 quarter tile, a 64-wide remainder on either side of a 128 x 128 tile,
 one whole tile, several tiles with a remainder, each at M = 1 .. 300 around the MFMA k-step, the slab and one and two chunks of 64 rows;
-the four Linears of roberta-base at M = 300.
+the four Linears of roberta-base at M = 300; and linear_grad_ref.LARGE_MNK, the smallest training row counts at which a chunk of the
+weight-gradient kernel holds three slabs or more (its register double buffer in the steady state, S >= 3 partials, a ragged last chunk) and
+at which dX of FFN2 leaves the one-tile GEMMs for a persistent kernel with its device-side row count.
 """
 import ctypes
 
@@ -27,10 +29,15 @@ pytestmark = pytest.mark.gpu
 SENTINEL = 777.0  # finite, fp16-exact, far from every expected output
 GUARD = 64        # rows of dx / elements of dw and db in front of and behind the call's own, which must keep their bits
 OK, E_INVALID, E_WORKSPACE = 0, -1, -4
-ALL_NK = [pytest.param(N, K, id=f"N{N}-K{K}") for N, K in ref.SMALL_NK + ref.MODEL_NK]
+# (M, N, K): M None is the shape's sweep of small row counts (ms_for); LARGE_MNK gives its own M
+ALL_NK = [pytest.param(None, N, K, id=f"N{N}-K{K}") for N, K in ref.SMALL_NK + ref.MODEL_NK] + \
+         [pytest.param(M, N, K, id=f"M{M}-N{N}-K{K}") for M, N, K in ref.LARGE_MNK]
+FFN2_LARGE = (4099, 768, 3072)  # the shape of LARGE_MNK whose dX takes a persistent GEMM
 
 
-def ms_for(N, K):
+def ms_for(N, K, M=None):
+    if M is not None:
+        return [M]
     return ref.M_SWEEP if (N, K) in ref.SMALL_NK else [300]
 
 
@@ -132,6 +139,8 @@ def _quantum(a):
     e = 0
     while not (nz * 2.0 ** -e == np.round(nz * 2.0 ** -e)).all():
         e -= 1
+    while e < 64 and (nz * 2.0 ** -(e + 1) == np.round(nz * 2.0 ** -(e + 1))).all():  # (upwards too: dy under a loss scale is a multiple of 32)
+        e += 1
     return 2.0 ** e
 
 
@@ -163,17 +172,33 @@ def test_some_tested_shape_is_split():
             assert rpc == 64, (M, N, K, S, rpc)
 
 
+def test_large_shapes_reach_the_steady_state_and_the_persistent_gemm():
+    """LARGE_MNK against the LIBRARY's split: three slabs or more per chunk, S >= 3, a ragged last chunk (linear_grad_ref.assert_large). dX of
+    the FFN2 shape leaves the one-tile kernels on this device: launch_gemm (csrc/mdr_encoder.hip) is called with the GEMM's N = the Linear's
+    K, its K = the Linear's N and M_est = M, and gemm_ref.flavour restates its choice (p_tiles = (N / 128) * ceil(M_est / 256) >= 3/2 of the
+    compute units); at M = 300 the same Linear stays on a one-tile kernel."""
+    import gemm_ref
+    from multihop_dense_retrieval_amd import linear
+    props = ref.assert_large(chunks_of=linear.backward_chunks)
+    assert props == ref.assert_large()
+    assert FFN2_LARGE in ref.LARGE_MNK
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    M, N, K = FFN2_LARGE
+    assert gemm_ref.flavour(0, M, M, K, N, 0, ncu) in ("persist", "big", "quad"), (ncu, gemm_ref.flavour(0, M, M, K, N, 0, ncu))
+    assert gemm_ref.flavour(0, 300, 300, K, N, 0, ncu) in ("small", "mid")
+
+
 @pytest.mark.parametrize("loss_scale", [False, True], ids=["unit", "x256"])
-@pytest.mark.parametrize("N,K", ALL_NK)
-def test_exact_grid_equality(N, K, loss_scale):
-    for M in ms_for(N, K):
+@pytest.mark.parametrize("M,N,K", ALL_NK)
+def test_exact_grid_equality(M, N, K, loss_scale):
+    for M in ms_for(N, K, M):
         x, w, dy = grid_inputs(M, N, K, 3, loss_scale)
         assert_equal(run(x, w, dy), exact_grid(x, w, dy), M, f"M={M} N={N} K={K}")
 
 
-@pytest.mark.parametrize("N,K", ALL_NK)
-def test_accumulate_on_the_grid(N, K):
-    for M in ms_for(N, K):
+@pytest.mark.parametrize("M,N,K", ALL_NK)
+def test_accumulate_on_the_grid(M, N, K):
+    for M in ms_for(N, K, M):
         x, w, dy = grid_inputs(M, N, K, 5)
         old_dw, old_db = ref.grid((N, K), 8).astype(np.float32) * 4, ref.grid((N,), 9).astype(np.float32) * 4
         got = run(x, w, dy, old_dw=old_dw, old_db=old_db, accumulate=True)
@@ -197,41 +222,54 @@ def check_bound(got, rb, m, label):
 
 
 @pytest.mark.parametrize("scale", [1.0, 256.0], ids=["unit", "x256"])
-@pytest.mark.parametrize("N,K", ALL_NK)
-def test_realistic_rows_within_the_derived_bound(N, K, scale):
+@pytest.mark.parametrize("M,N,K", ALL_NK)
+def test_realistic_rows_within_the_derived_bound(M, N, K, scale):
     """Identity and GELU path (u from the forward hook with epilogue 0), and the GELU path with one invalid row of NaN behind m = M - 1."""
-    for M in ms_for(N, K):
+    for M in ms_for(N, K, M):
         x, w, dy = ref.realistic(M, N, K, 11, scale)
         check_bound(run(x, w, dy), ref.reference_and_bound(x, w, dy), M, f"identity M={M} N={N} K={K} scale={scale}")
         u = forward_hook(x, w, ref.bias(N, 11), 0)
         check_bound(run(x, w, dy, u), ref.reference_and_bound(x, w, dy, u), M, f"gelu M={M} N={N} K={K} scale={scale}")
-    if M > 1:
+    if 1 < M <= 300:  # (the large shapes have their rows behind m in test_rows_behind_m_dev_do_not_exist)
         xb, dyb, ub = x.copy(), dy.copy(), u.copy()
         xb[M - 1], dyb[M - 1], ub[M - 1] = np.nan, np.inf, np.nan
         got = run(xb, w, dyb, ub, m=M - 1)
         check_bound(got, ref.reference_and_bound(x, w, dy, u, M - 1), M - 1, f"gelu m=M-1 M={M} N={N} K={K} scale={scale}")
 
 
-@pytest.mark.parametrize("N,K", ALL_NK)
-def test_gelu_at_zero_is_exactly_one_half(N, K):
+@pytest.mark.parametrize("M,N,K", ALL_NK)
+def test_gelu_at_zero_is_exactly_one_half(M, N, K):
     """u = 0 everywhere: gelu'(0) = 1/2 exactly (the polynomial gives 2^-1 at 0), dZ = dY / 2, and all three outputs are bit-exact on the grid."""
-    for M in ms_for(N, K):
+    for M in ms_for(N, K, M):
         x, w, dy = grid_inputs(M, N, K, 13)
         dz = (dy.astype(np.float32) / 2).astype(np.float16)
         assert_equal(run(x, w, dy, np.zeros((M, N), np.float16)), exact_grid(x, w, dz), M, f"gelu0 M={M} N={N} K={K}")
 
 
-@pytest.mark.parametrize("N,K", [pytest.param(128, 128, id="N128-K128"), pytest.param(256, 384, id="N256-K384"), pytest.param(768, 768, id="N768-K768")])
-@pytest.mark.parametrize("gelu0", [False, True], ids=["identity", "gelu0"])
-def test_rows_behind_m_dev_do_not_exist(N, K, gelu0):
-    """m in {0, 1, M - 1, M}, rows at or behind m of x, dy and pre NaN and Inf: outputs finite and equal, bit for bit, to the call on the
-    first m rows alone (on the grid every sum is exact, so the different split of the shorter call does not matter); dx rows at or behind m
-    keep the sentinel (run() asserts it); m = 0 gives zeros, or the old value with accumulate."""
-    M = 200
+def large_ms(M, N, K):
+    """valid-row counts for a split shape: none, one row into the second slab of chunk 1, one row short of the seam behind chunk 1, a count
+    that cuts the last chunk but one and leaves the whole last chunk behind it, all"""
+    S, rpc = ref.chunks(M, N, K)
+    ms = (0, rpc + ref.SLAB + 1, 2 * rpc - 1, (S - 2) * rpc + ref.SLAB + 6, M)
+    assert S >= 3 and rpc >= 2 * ref.SLAB and list(ms) == sorted(set(ms)) and ms[3] <= (S - 1) * rpc < M
+    return ms
+
+
+# the small shapes at M = 200 on both paths; (2051, 768, 768) and FFN2 at 4099 rows (dX through a persistent GEMM whose device-side row count
+# lies well below the cap) once each, one on either path
+ROWS_BEHIND = [pytest.param(200, N, K, g, id=f"{'gelu0' if g else 'identity'}-N{N}-K{K}") for g in (False, True) for N, K in ((128, 128), (256, 384), (768, 768))] + \
+              [pytest.param(2051, 768, 768, False, id="identity-M2051-N768-K768"), pytest.param(*FFN2_LARGE, True, id="gelu0-M4099-N768-K3072")]
+
+
+@pytest.mark.parametrize("M,N,K,gelu0", ROWS_BEHIND)
+def test_rows_behind_m_dev_do_not_exist(M, N, K, gelu0):
+    """m in {0, 1, M - 1, M} (the large shapes: large_ms), rows at or behind m of x, dy and pre NaN and Inf: outputs finite and equal, bit for
+    bit, to the call on the first m rows alone (on the grid every sum is exact, so the different split of the shorter call does not matter);
+    dx rows at or behind m keep the sentinel (run() asserts it); m = 0 gives zeros, or the old value with accumulate."""
     x, w, dy = grid_inputs(M, N, K, 17)
     pre = np.zeros((M, N), np.float16) if gelu0 else None
     old_dw, old_db = ref.grid((N, K), 18).astype(np.float32), ref.grid((N,), 19).astype(np.float32)
-    for m in (0, 1, M - 1, M):
+    for m in ((0, 1, M - 1, M) if M == 200 else large_ms(M, N, K)):
         xb, dyb = x.copy(), dy.copy()
         xb[m:], dyb[m:] = np.nan, np.inf
         xb[m + 1::2], dyb[m + 1::2] = -np.inf, np.nan
@@ -275,9 +313,9 @@ def test_nan_in_a_valid_row_reaches_only_what_it_touches():
     assert np.array_equal(got["db"][cols], clean["db"][cols])
 
 
-@pytest.mark.parametrize("N,K", [pytest.param(256, 384, id="N256-K384"), pytest.param(768, 768, id="N768-K768")])
-def test_two_runs_and_a_larger_workspace_give_the_same_bits(N, K):
-    M = 300
+@pytest.mark.parametrize("M,N,K", [pytest.param(300, 256, 384, id="N256-K384"), pytest.param(300, 768, 768, id="N768-K768"),
+                                   pytest.param(*FFN2_LARGE, id="M4099-N768-K3072")])
+def test_two_runs_and_a_larger_workspace_give_the_same_bits(M, N, K):
     x, w, dy = ref.realistic(M, N, K, 29)
     u = forward_hook(x, w, ref.bias(N, 29), 0)
     for pre in (None, u):

@@ -72,11 +72,13 @@ def test_gelu_grad_formula_over_every_finite_fp16():
     assert (wrong > bnd).any()
 
 
-@pytest.mark.parametrize("N,K", ref.SMALL_NK + ref.MODEL_NK)
-def test_emulation_stays_inside_the_bound(N, K):
-    """A second implementation of the listed dataflow, on every shape the GPU tests use, identity and GELU, unit and loss scale."""
-    for M in (ref.M_SWEEP if (N, K) in ref.SMALL_NK else [300]):
-        for scale in (1.0, 256.0):
+@pytest.mark.parametrize("M,N,K", [pytest.param(None, N, K, id=f"{N}-{K}") for N, K in ref.SMALL_NK + ref.MODEL_NK] +
+                         [pytest.param(M, N, K, id=f"M{M}-{N}-{K}") for M, N, K in ref.LARGE_MNK])
+def test_emulation_stays_inside_the_bound(M, N, K):
+    """A second implementation of the listed dataflow, on every shape the GPU tests use, identity and GELU, unit and loss scale (the shapes
+    of LARGE_MNK, where the slab loop and the chunk reduction add thousands of terms: under the loss scale, as in training)."""
+    for M in ([M] if M is not None else ref.M_SWEEP if (N, K) in ref.SMALL_NK else [300]):
+        for scale in ((1.0, 256.0) if M <= 300 else (256.0,)):
             x, w, dy = ref.realistic(M, N, K, 11, scale)
             pre = _pre(x, w, ref.bias(N, 11))
             old_dw, old_db = ref.realistic(N, 64, K, 12)[0].astype(np.float32), ref.bias(N, 12)
@@ -117,6 +119,9 @@ def test_split_is_a_function_of_the_shape_and_workspace_covers_it():
             assert full >= M * N * 2 + N * K * 2 + K * 4 + (S * N * K * 4 + S * N * 4 if S > 1 else 0)
             assert lib.mdr_linear_backward_workspace_bytes(M, N, K, 4) == (0 if S == 1 else (S * N * 4 + 255) // 256 * 256)
     assert some_split
+    for M, N, K, S, rpc, _ in ref.assert_large(chunks_of=linear.backward_chunks):  # the large shapes keep their properties under the LIBRARY's split
+        assert (S, rpc) == ref.chunks(M, N, K)
+        assert lib.mdr_linear_backward_workspace_bytes(M, N, K, 15) >= M * N * 2 + N * K * 2 + K * 4 + S * N * K * 4 + S * N * 4
     for M, N, K in ((0, 64, 64), (-1, 64, 64), (5, 0, 64), (5, 64, 0), (5, 96, 64), (5, 64, 100), (5, -64, 64)):
         assert lib.mdr_linear_backward_workspace_bytes(M, N, K, 15) == 0
         assert linear.backward_chunks(M, N, K) == (0, 0)
