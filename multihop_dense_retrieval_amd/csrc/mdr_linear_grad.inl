@@ -21,7 +21,10 @@
 // Every output element has one owner and one summation order: no atomics, and two runs give the same bits.
 //
 // Rounding points (tests/linear_grad_ref.py derives its bound from this list):
-//   1. x, w, dy and u are fp16: exact operands. A product of two fp16 is exact in fp32.
+//   1. x, w, dy and u are fp16: exact operands. A product of two fp16 is exact in fp32, but an MFMA adds the products of one instruction
+//      aligned to their largest exponent FIELD with 24 bits kept below it, and a subnormal or zero operand carries the field 2^-14 whatever
+//      its value: a sum of subnormal x normal products alone (FFN2's dW over a few CLS rows, a GELU-output column deep in the negative tail)
+//      loses up to ten bits. Nothing to do about it here; the bound has a term for it.
 //   2. gelu'(u) = Phi(u) + u phi(u) in fp32. Phi from the forward's tail polynomial (gelu_erf2 of mdr_encoder_gemm.inl, max |Phi error|
 //      2.1e-7) evaluated at min(|u|, 16) -- the polynomial is fitted on [0, 6] and turns around near 23.5, and Phi(-16) is 0 in fp32 --
 //      phi(u) = exp2(-u^2 log2(e) / 2) / sqrt(2 pi) from one v_exp_f32. dZ = fp16(fp32(dy) * gelu'(u)): one fp16 rounding.

@@ -65,6 +65,10 @@ TINY = dict(vocab=512, hidden=128, layers=2, heads=2, ffn=256, max_pos=514, ln_e
 # a little more at every rounding (at depth 12 their distance is ~0.7 of the regime's own error against fp32), so the
 # sharp operand-rounded parity bar is only meaningful on a SHALLOW stack -- this one.
 WIDE2 = dict(vocab=50265, hidden=768, layers=2, heads=12, ffn=3072, max_pos=514, ln_eps=1e-5, pad_id=1)
+# four layers: the smallest depth with a generic MIDDLE layer (layer 1: fed by a full layer, feeding a full layer). TINY's two layers are the
+# first one and the CLS-only last one, so a full layer never hands its fp32 stream and its fp16 copy to another full layer there. The widths
+# differ from TINY's and ffn = 3 x 128 is no power of two.
+DEEP = dict(vocab=512, hidden=256, layers=4, heads=4, ffn=384, max_pos=514, ln_eps=1e-5, pad_id=1)
 
 
 def state_dict_shapes(geom, with_pooler=True):

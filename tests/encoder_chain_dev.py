@@ -1,6 +1,7 @@
 """The device side that tests/test_encoder_chain_gpu.py and tests/test_overflow_chain_gpu.py share: the retriever encoder as ONE chain of the
 package's differentiable functions (Chain, with a tape of every call and a hook on every output), its leaves (params), the NaN seeding of the
-caching allocator (poison), the bit comparisons, and criterion E's assertion (check_e). The host side is tests/encoder_chain_ref.py."""
+caching allocator (poison), the bit comparisons, and criterion E's assertion (check_e). The host side is tests/encoder_chain_ref.py.
+Chain, params, poison and check_e take the geometry (oracle.seeded.TINY or DEEP); the default is TINY."""
 import ctypes
 import functools
 
@@ -10,7 +11,6 @@ import torch
 import encoder_chain_ref as ch
 
 GEOM = ch.GEOM
-H, NH, F, EPS, PAD = GEOM["hidden"], GEOM["heads"], GEOM["ffn"], GEOM["ln_eps"], GEOM["pad_id"]
 E_ = "encoder.embeddings."
 
 
@@ -31,40 +31,52 @@ def same_bits(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and bool(torch.equal(_ibits(a), _ibits(b)))
 
 
-def params():
-    sd = ch.state_dict()
+def params(geom=GEOM):
+    sd = ch.state_dict(geom)
     return {k: torch.from_numpy(v).cuda().requires_grad_(True) for k, v in sd.items()}
 
 
-def poison(mib=64):
+def poison(mib=64, geom=GEOM):
     """allocate, fill with NaN bit patterns and free blocks of the sizes the chain's torch.empty calls ask for (and many more): the caching
-    allocator hands them out again, so a read of an unwritten row shows as a NaN. Nothing here can fault."""
+    allocator hands them out again, so a read of an unwritten row shows as a NaN. Then every block the allocator still holds free -- what
+    earlier tests freed, the splinters between live tensors, the rest of the segments opened here -- is asked for by its exact size and
+    filled too, so that no unseeded block is left for the allocator to prefer, however much ran before. Nothing here can fault."""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()  # whole free segments go back to the driver: what remains free lies inside segments with live tensors
     held, total = [], 0
+    H, F = geom["hidden"], geom["ffn"]
     rows = (1280, 640, 288, 192, 8, 6, 4)
-    shapes = [(r, c) for r in rows for c in (H, 3 * H, F)] + [(H, H), (3 * H, H), (F, H), (H, F), (GEOM["vocab"], H), (GEOM["max_pos"], H), (H,), (3 * H,), (F,)]
+    shapes = [(r, c) for r in rows for c in (H, 3 * H, F)] + [(H, H), (3 * H, H), (F, H), (H, F), (geom["vocab"], H), (geom["max_pos"], H), (H,), (3 * H,), (F,)]
     while total < mib << 20:
-        for s in shapes:
-            held.append(torch.full(s, float("nan"), dtype=torch.float16, device="cuda"))
-            held.append(torch.full(s, float("nan"), dtype=torch.float32, device="cuda"))
+        for s in shapes:  # the bytes of an fp16 and of an fp32 tensor of this shape, all ones: a NaN whichever of the two types reads them
+            for width in (2, 4):  # (an fp32 NaN written as such reads as one NaN and one zero in fp16, and sizes do coincide: [1280, H] fp16, [640, H] fp32)
+                held.append(torch.full((width * int(np.prod(s)),), 0xFF, dtype=torch.uint8, device="cuda"))
             total += 6 * int(np.prod(s))
         for n in (512, 4096, 65536, 1 << 20, 4 << 20):
             held.append(torch.full((n,), 0xFF, dtype=torch.uint8, device="cuda"))
             total += n
+    for _ in range(8):  # a block of a small segment above 1 MiB takes two requests, a new segment's rest another pass
+        free = sorted((b["size"], seg["segment_type"]) for seg in torch.cuda.memory_snapshot() for b in seg["blocks"] if b["state"] == "inactive")
+        if not free:
+            break
+        for size, pool in reversed(free):  # (requests of up to 1 MiB are served from the small segments, larger ones from the large)
+            held.append(torch.full((min(size, 1 << 20) if pool == "small" else size,), 0xFF, dtype=torch.uint8, device="cuda"))
     torch.cuda.synchronize()
     del held
 
 
 class Chain:
     """one encode through the public functions, with a tape of every call and hooks on every output. half: None, or a function from a weight
-    leaf to the fp16 copy that every Linear is handed as weight16 (optim.FusedAdam.half)"""
+    leaf to the fp16 copy that every Linear is handed as weight16 (optim.FusedAdam.half). geom: the geometry P was made for"""
 
-    def __init__(self, P, ids, mask, half=None):
+    def __init__(self, P, ids, mask, half=None, geom=GEOM):
         from multihop_dense_retrieval_amd import _lib
         from multihop_dense_retrieval_amd.attention import packed_self_attention
         from multihop_dense_retrieval_amd.embedding import packed_embedding_layer_norm
         from multihop_dense_retrieval_amd.layernorm import packed_layer_norm
         from multihop_dense_retrieval_amd.linear import packed_linear
-        self.tape, self.P = [], P
+        self.tape, self.P, self.geom = [], P, geom
+        NH, EPS, PAD = geom["heads"], geom["ln_eps"], geom["pad_id"]
         self.ids_np, self.mask_np = ids, mask
         B, L = ids.shape
         self.B, self.L, self.cap = B, L, B * L
@@ -106,7 +118,7 @@ class Chain:
                                                P[E_ + "token_type_embeddings.weight"][0], P[E_ + "LayerNorm.weight"], P[E_ + "LayerNorm.bias"], EPS,
                                                self.cap, PAD, True)
         self._rec("emb", "emb", {}, {"y16": h16, "y32": h32})
-        nl = GEOM["layers"]
+        nl = geom["layers"]
         for i in range(nl):
             p, lab = f"encoder.encoder.layer.{i}.", f"L{i}"
             qkv = linear(h16, [p + "attention.self." + n for n in ("query", "key", "value")], False, total, lab + ".qkv")
@@ -138,14 +150,15 @@ def grads_np(P, scale=1.0):
     return {k: v.grad.detach().cpu().numpy().astype(np.float64) / scale for k, v in P.items()}
 
 
-def check_e(g_dev, g_reg, g64, batches, title):
-    rows, e_pool = ch.criterion_e(g_dev, g_reg, g64)
+def check_e(g_dev, g_reg, g64, batches, title, geom=GEOM):
+    rows, e_pool = ch.criterion_e(g_dev, g_reg, g64, geom)
     print(ch.table(rows, e_pool, "E " + title))
     print(f"E {title}: worst share of the bar {max(r[4] for r in rows):.3f}, worst e_dev / e_reg "
           f"{max(r[1] / r[2] for r in rows if r[2] > 0):.3f}")
-    zr = ch.zero_rows(batches)
+    zr = ch.zero_rows(batches, geom)
     w = E_ + "word_embeddings.weight"
     assert zr.any() and not g_dev[w][zr].any() and not g64[w][zr].any(), "a word row that owns no token (or padding_idx's) has a gradient"
-    for k in ch.zero_grad_names():
+    assert len(ch.zero_grad_names(geom)) == geom["layers"]
+    for k in ch.zero_grad_names(geom):
         print(f"E {title}: {k} max |g_dev| {np.abs(g_dev[k]).max():.3e} (mathematically zero; the query bias's {np.abs(g_dev[k.replace('key', 'query')]).max():.3e})")
     assert not ch.failures(rows), [(r[0], round(r[4], 3)) for r in ch.failures(rows)]

@@ -13,7 +13,10 @@ regime     an independent restatement of the device chain's numerics in plain to
            The dataflow is the default mode of the product's trunk (residual_fp32 = 2): a Linear's fp16 output meets the fp32 stream in the
            LayerNorm; the last layer runs its query, its attention and its tail on the CLS rows alone.
 regime_b   a second correct implementation: the same in fp32 arithmetic with the batch reversed.
-MUTATIONS  wiring defects of `regime`, one at a time (what a wrong composition of correct functions looks like).
+MUTATIONS  wiring defects of `regime`, one at a time (what a wrong composition of correct functions looks like). MID_MUTATIONS are the ones
+           that touch only a full layer that has a full layer behind it (0 < i < layers - 1): they change nothing on a two-layer geometry.
+
+Every function takes the geometry (oracle.seeded.TINY or DEEP); the default is TINY.
 
 Criterion E (criterion_e). For every parameter tensor p, e(p) = |g(p) - g64(p)|_2 / |g64(p)|_2, and e_pool the same ratio over all compared
 tensors at once. A candidate passes when e_cand(p) <= 2 max(e_reg(p), e_pool) for every p: the yardstick is the reference regime's own error.
@@ -40,7 +43,9 @@ BATCHES = {"L160": (160, (1, 2, 17, 63, 64, 65, 129, 160)), "L48": (48, (1, 5, 1
 # the six encodes of the in-batch loss: 4 sequences each, two padded lengths
 LOSS_L = {"q": 48, "q_sp1": 48, "c1": 160, "c2": 160, "neg_1": 48, "neg_2": 160}
 MUTATIONS = ("res_dropped_ln1", "res_dropped_ln2", "cls_rows_not_added", "dy2_dropped", "dw_qk_swapped", "last_call_only", "gelu_grad_at_output",
-             "pos_from_padded_index")
+             "pos_from_padded_index", "mid_stream_cls_only", "mid_dy16_dropped", "res_dropped_ln1_mid", "res_dropped_ln2_mid")
+# the defects that only a full layer BEHIND a full layer can show (0 < i < layers - 1): invisible on a two-layer geometry
+MID_MUTATIONS = MUTATIONS[-4:]
 
 
 def param_names(geom=GEOM):
@@ -55,11 +60,11 @@ def state_dict(geom=GEOM, seed=WEIGHT_SEED):
     return seeded.make_state_dict(seed, geom, with_pooler=False)
 
 
-def make_batch(L, lens, seed, vocab=GEOM["vocab"]):
+def make_batch(L, lens, seed, geom=GEOM):
     """ids, mask int64 [B, L]: <s> tokens </s> then pad (a sequence of one token is <s> alone)"""
     B = len(lens)
-    body = seeded.integers(seed, f"chain.tok.{L}", (B, L), 3, vocab)
-    ids, mask = np.full((B, L), GEOM["pad_id"], np.int64), np.zeros((B, L), np.int64)
+    body = seeded.integers(seed, f"chain.tok.{L}", (B, L), 3, geom["vocab"])
+    ids, mask = np.full((B, L), geom["pad_id"], np.int64), np.zeros((B, L), np.int64)
     for b, n in enumerate(lens):
         ids[b, :n] = body[b, :n]
         ids[b, 0] = 0
@@ -69,25 +74,26 @@ def make_batch(L, lens, seed, vocab=GEOM["vocab"]):
     return ids, mask
 
 
-def batch(name):
+def batch(name, geom=GEOM):
     L, lens = BATCHES[name]
-    return make_batch(L, lens, 31)
+    return make_batch(L, lens, 31, geom)
 
 
-def loss_batches():
-    return {k: seeded.make_token_batch(37 + i, "chain." + k, 4, LOSS_L[k], GEOM["vocab"]) for i, k in enumerate(KEYS)}
+def loss_batches(geom=GEOM):
+    return {k: seeded.make_token_batch(37 + i, "chain." + k, 4, LOSS_L[k], geom["vocab"], pad_fill=geom["pad_id"])
+            for i, k in enumerate(KEYS)}
 
 
-def cotangent(B, H=GEOM["hidden"]):
-    return seeded.normal(41, f"chain.G.{B}", (B, H)).astype(np.float32)
+def cotangent(B, geom=GEOM):
+    return seeded.normal(41, f"chain.G.{B}", (B, geom["hidden"])).astype(np.float32)
 
 
-def zero_rows(batches, vocab=GEOM["vocab"], pad=GEOM["pad_id"]):
+def zero_rows(batches, geom=GEOM):
     """bool [vocab]: the rows of word_embeddings whose gradient is exactly zero -- no masked-in token of any batch reads them, or padding_idx"""
-    used = np.zeros(vocab, bool)
+    used = np.zeros(geom["vocab"], bool)
     for ids, mask in batches:
         used[np.asarray(ids)[np.asarray(mask) != 0]] = True
-    used[pad] = False
+    used[geom["pad_id"]] = False
     return ~used
 
 
@@ -198,27 +204,33 @@ def regime_encode(W, geom, ids, mask, mutation=None):
     def heads(t):
         return t.reshape(B, -1, nh, hd).permute(0, 2, 1, 3)
 
-    def tail(p, ctx, h32, first):
-        res = h32.detach() if (mutation == "res_dropped_ln1" and first) else h32
+    def tail(p, ctx, h32, i):
+        """i: the index of a full layer, None for the last layer's CLS rows"""
+        first, mid = i == 0, i == 1
+        res = h32.detach() if (mutation == "res_dropped_ln1" and first) or (mutation == "res_dropped_ln1_mid" and mid) else h32
+        if mutation == "mid_stream_cls_only" and i is not None and i > 0:  # every layer taken for the one under the last
+            res = torch.cat([res[:, :1], res[:, 1:].detach()], 1)
         a32 = ln(linear(ctx, p + "attention.output.dense") + res, W[p + "attention.output.LayerNorm.weight"], W[p + "attention.output.LayerNorm.bias"], eps)
         f = linear(linear(R(a32, p + "attention.output.LayerNorm:y16"), p + "intermediate.dense", True), p + "output.dense")
-        res = a32.detach() if (mutation == "res_dropped_ln2" and first) or (mutation == "dy2_dropped" and not first) else a32
+        drop2 = (mutation == "res_dropped_ln2" and first) or (mutation == "res_dropped_ln2_mid" and mid) or (mutation == "dy2_dropped" and not first)
+        res = a32.detach() if drop2 else a32
         o32 = ln(f + res, W[p + "output.LayerNorm.weight"], W[p + "output.LayerNorm.bias"], eps)
         return R(o32, p + "output.LayerNorm:y16"), o32
 
     for i in range(nl):
         p = f"encoder.encoder.layer.{i}."
         last = i == nl - 1
-        q, k, v = (heads(linear(h16, p + "attention.self." + n)) for n in ("query", "key", "value"))
+        x16 = h16.detach() if (mutation == "mid_dy16_dropped" and 0 < i < nl - 1) else h16
+        q, k, v = (heads(linear(x16, p + "attention.self." + n)) for n in ("query", "key", "value"))
         if last:  # the query, the attention and the tail of the CLS rows alone
             q = q[:, :, :1]
         s = Rg(q @ k.transpose(-1, -2) / math.sqrt(hd) + add_mask, p + "attention:dS")
         ctx = R(Rv(torch.softmax(s, -1)) @ v, p + "attention:ctx").permute(0, 2, 1, 3).reshape(B, -1, H)
         if last:
             cls32 = h32[:, 0]
-            h16, h32 = tail(p, ctx[:, 0], cls32.detach() if mutation == "cls_rows_not_added" else cls32, False)
+            h16, h32 = tail(p, ctx[:, 0], cls32.detach() if mutation == "cls_rows_not_added" else cls32, None)
         else:
-            h16, h32 = tail(p, ctx, h32, i == 0)
+            h16, h32 = tail(p, ctx, h32, i)
     y = linear(h16, "project.0")
     return ln(y, W["project.1.weight"], W["project.1.bias"], eps)
 

@@ -1,6 +1,11 @@
 """GPU (-m gpu): the retriever encoder's backward as ONE chain of the package's differentiable functions -- packed_embedding_layer_norm,
 packed_linear, packed_self_attention, packed_layer_norm, mhop_loss_outputs -- composed as the product's forward in its default mode
-(residual_fp32 = 2; csrc/mdr_encoder_trunk.inl), on oracle.seeded.TINY. The host side is tests/encoder_chain_ref.py.
+(residual_fp32 = 2; csrc/mdr_encoder_trunk.inl), on oracle.seeded.TINY and on oracle.seeded.DEEP. The host side is tests/encoder_chain_ref.py.
+
+TINY has two layers: the first one and the last one, which runs on the CLS rows alone. DEEP has four, the smallest depth in which a full layer
+hands its fp32 stream and its fp16 copy to another full layer: there the gradient on the stream is dense (on TINY it is zero but for the B CLS
+rows) and meets the next QKV Linear's dense fp16 dx in the layer's second LayerNorm backward. tests/test_encoder_chain_host.py shows that a
+defect in that hand-off leaves every TINY gradient unchanged. The TINY cases keep the ids they had; DEEP's are `DEEP-...` and `..._on_deep`.
 
 A  forward: the chain's embeddings against RobertaRetriever.encode_q and the fp64 model.
 B  every taped function, on the device tensors it really saw and the upstream gradient autograd really delivered: the raw backward re-run,
@@ -36,14 +41,23 @@ import encoder_chain_ref as ch
 import layernorm_grad_ref as nref
 import linear_grad_ref as lref
 import mhop_loss_ref
-from encoder_chain_dev import E_, EPS, F, GEOM, H, NH, PAD, Chain, _np, _p, check_e, grads_np, params, poison, same_bits  # noqa: F401
+from encoder_chain_dev import E_, Chain, _np, _p, check_e, grads_np, params, poison, same_bits
 from oracle import seeded
 from oracle import trunk_rows_oracle as tr
 
 pytestmark = pytest.mark.gpu
 
-TINY_BAR = (6e-3, 1.2e-3)  # tests/test_encoder_gpu.py's TOL["tiny"]: max and mean |error| of the embeddings against fp64
+GEOMS = {"TINY": seeded.TINY, "DEEP": seeded.DEEP}
+TINY_BAR = (6e-3, 1.2e-3)  # tests/test_encoder_gpu.py's TOL["tiny"]: max and mean |error| of the embeddings against fp64. TINY's alone.
 CONFIGS = [("L160", 1.0), ("L160", 256.0), ("L48", 1.0), ("L48", 256.0)]
+BC_DEEP = [("L160", 1.0), ("L48", 256.0)]  # both attention kernels and both scales once; E runs all four
+
+
+def cases(configs_tiny, configs_deep):
+    """(geometry name, *config): TINY's ids are what they were before the second geometry came"""
+    one = lambda c: c if isinstance(c, tuple) else (c,)  # noqa: E731
+    return ([pytest.param("TINY", *one(c), id="-".join(str(v) for v in one(c))) for c in configs_tiny]
+            + [pytest.param("DEEP", *one(c), id="-".join(["DEEP"] + [str(v) for v in one(c)])) for c in configs_deep])
 
 
 # ---- B: one stage's raw backward, re-run on the taped tensors, inside the derived bound ------------------------------------------------------
@@ -55,7 +69,8 @@ def rerun(c, rec):
     """-> (device results, {input key: dx}, {param name: gradient}, {output: share of the bound}); asserts the bound"""
     from multihop_dense_retrieval_amd import attention, embedding, layernorm, linear
     kind, lab, g = rec["kind"], rec["label"], rec["g"]
-    P = c.P
+    P, geom = c.P, c.geom
+    H, NH, EPS, PAD = geom["hidden"], geom["heads"], geom["ln_eps"], geom["pad_id"]
     shares, fails = {}, []
 
     def ratio(name, got, r, bnd, wr=lref.worst_ratio):
@@ -110,7 +125,7 @@ def rerun(c, rec):
         names = [E_ + n for n in ("word_embeddings.weight", "position_embeddings.weight", "token_type_embeddings.weight", "LayerNorm.weight", "LayerNorm.bias")]
         word, pos, typ, wt = (P[n].detach() for n in names[:4])
         dy16, dy2 = g["y16"].to(torch.float16).contiguous(), g["y32"].to(torch.float32).contiguous()
-        plan = embedding.embedding_plan(c.ids, c.src, c.pid, c.total, c.cap, GEOM["vocab"], GEOM["max_pos"], PAD)
+        plan = embedding.embedding_plan(c.ids, c.src, c.pid, c.total, c.cap, geom["vocab"], geom["max_pos"], PAD)
         outs = [_f32(word.shape), _f32(pos.shape), _f32((H,)), _f32((H,)), _f32((H,)), torch.zeros((c.cap, H), dtype=torch.float32, device="cuda")]
         embedding.embedding_backward(c.ids, c.src, c.pid, c.total, c.cap, word, pos, typ[0], wt, EPS, dy16, dy2, plan, *outs)
         case = dict(ids=c.ids_np, tok_src=_np(c.src), tok_pid=_np(c.pid), total=c.T, word=_np(word), pos=_np(pos), type0=_np(typ[0]), g=_np(wt),
@@ -156,83 +171,107 @@ def check_wiring(c, st, param_grads_used_once=True):
             m = c.T if t.shape[0] == c.cap else t.shape[0]
             assert same_bits(hooked[:m], dx[:m]), (rec["label"], k, "<-", r2["label"], k2)
             n += 1
-    assert n >= 16
+    # every output but the last LayerNorm's fp32 one and the head's has one consumer: 2 of the embedding, 9 of a full layer, 10 of the last
+    # layer with the gather and project.0 (21 on two layers)
+    assert n == 9 * c.geom["layers"] + 3, n
     if param_grads_used_once:
         seen = set()
         for lab, (_, _, pg, _) in st.items():
             for name, gr in pg.items():
                 assert same_bits(c.P[name].grad, gr.reshape(c.P[name].shape).contiguous()), (lab, name)
                 seen.add(name)
-        assert seen == set(ch.param_names()), set(ch.param_names()) ^ seen
+        assert seen == set(ch.param_names(c.geom)), set(ch.param_names(c.geom)) ^ seen
 
 
 # ---- the runs, each made once ----------------------------------------------------------------------------------------------------------------
 _RUNS = {}
 
 
-def dense_run(name, scale, with_poison=False):
-    ids, mask = ch.batch(name)
-    P = params()
+def dense_run(gn, name, scale, with_poison=False):
+    geom = GEOMS[gn]
+    ids, mask = ch.batch(name, geom)
+    P = params(geom)
     if with_poison:
-        poison()
-    c = Chain(P, ids, mask)
-    G = torch.from_numpy(ch.cotangent(len(ids)) * np.float32(scale)).cuda()
+        poison(geom=geom)
+    c = Chain(P, ids, mask, geom=geom)
+    G = torch.from_numpy(ch.cotangent(len(ids), geom) * np.float32(scale)).cuda()
     if with_poison:
-        poison()
+        poison(geom=geom)
     c.out.backward(G)
     torch.cuda.synchronize()
     return c
 
 
-def loss_run(with_poison=False):
+def loss_run(gn, with_poison=False):
     from multihop_dense_retrieval_amd import criterions
-    P = params()
-    batches = ch.loss_batches()
+    geom = GEOMS[gn]
+    P = params(geom)
+    batches = ch.loss_batches(geom)
     if with_poison:
-        poison()
-    cs = {k: Chain(P, *batches[k]) for k in ch.KEYS}
+        poison(geom=geom)
+    cs = {k: Chain(P, *batches[k], geom=geom) for k in ch.KEYS}
     loss = criterions.mhop_loss_outputs({k: cs[k].out for k in ch.KEYS}, types.SimpleNamespace(fp16=True))
     if with_poison:
-        poison()
+        poison(geom=geom)
     loss.backward()
     torch.cuda.synchronize()
     return cs, loss, P
 
 
-def run(key):
+def run(*key):
+    """run("TINY", "L160", 1.0) or run("DEEP", "loss")"""
     if key not in _RUNS:
-        _RUNS[key] = loss_run() if key == "loss" else dense_run(*key)
+        _RUNS[key] = loss_run(key[0]) if key[1] == "loss" else dense_run(*key)
     return _RUNS[key]
 
 
 _HOST = {}
 
 
-def host_dense(name):
-    """model64 and the regime at scales 1 and 2^8 on the CPU, once per batch"""
-    if name not in _HOST:
-        sd = ch.state_dict()
-        ids, mask = ch.batch(name)
-        G = ch.cotangent(len(ids))
-        emb64, g64 = ch.grads_cotangent("model64", sd, GEOM, ids, mask, G)
-        _HOST[name] = dict(emb64=emb64, g64=g64, reg={s: ch.grads_cotangent("regime", sd, GEOM, ids, mask, G, s)[1] for s in (1.0, 256.0)})
-    return _HOST[name]
+def host_dense(gn, name):
+    """model64 and the regime at scales 1 and 2^8 on the CPU, once per geometry and batch"""
+    if (gn, name) not in _HOST:
+        t0 = time.time()
+        geom = GEOMS[gn]
+        sd = ch.state_dict(geom)
+        ids, mask = ch.batch(name, geom)
+        G = ch.cotangent(len(ids), geom)
+        emb64, g64 = ch.grads_cotangent("model64", sd, geom, ids, mask, G)
+        reg = {s: ch.grads_cotangent("regime", sd, geom, ids, mask, G, s) for s in (1.0, 256.0)}
+        _HOST[gn, name] = dict(emb64=emb64, g64=g64, emb_reg=reg[1.0][0], reg={s: r[1] for s, r in reg.items()})
+        print(f"WALL host references {gn} {name} {time.time() - t0:.2f} s")
+    return _HOST[gn, name]
+
+
+def host_loss(gn):
+    """model64 and the regime under the in-batch loss on the CPU, once per geometry"""
+    if (gn, "loss") not in _HOST:
+        t0 = time.time()
+        geom = GEOMS[gn]
+        sd, batches = ch.state_dict(geom), ch.loss_batches(geom)
+        _HOST[gn, "loss"] = dict(batches=batches, m64=ch.grads_loss("model64", sd, geom, batches), reg=ch.grads_loss("regime", sd, geom, batches))
+        print(f"WALL host references {gn} loss {time.time() - t0:.2f} s")
+    return _HOST[gn, "loss"]
 
 
 # ---- A ---------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(ch.BATCHES))
-def test_a_forward_is_the_products_up_to_the_fp16_head(name):
+@pytest.mark.parametrize("gn,name", cases(list(ch.BATCHES), list(ch.BATCHES)))
+def test_a_forward_is_the_products_up_to_the_fp16_head(gn, name):
     from multihop_dense_retrieval_amd import _lib, retriever
     t0 = time.time()
-    c = run((name, 1.0))
-    ids, mask = ch.batch(name)
-    cfg = retriever.RobertaConfig(vocab_size=GEOM["vocab"], hidden_size=H, num_hidden_layers=GEOM["layers"], num_attention_heads=NH, intermediate_size=F)
+    geom = GEOMS[gn]
+    H, EPS = geom["hidden"], geom["ln_eps"]
+    c = run(gn, name, 1.0)
+    ids, mask = ch.batch(name, geom)
+    cfg = retriever.RobertaConfig(vocab_size=geom["vocab"], hidden_size=H, num_hidden_layers=geom["layers"], num_attention_heads=geom["heads"],
+                                  intermediate_size=geom["ffn"])
     m = retriever.RobertaRetriever(cfg, None)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in seeded.make_state_dict(ch.WEIGHT_SEED, GEOM).items()})
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in seeded.make_state_dict(ch.WEIGHT_SEED, geom).items()})
     m.to("cuda").eval()
     assert int(m.residual_fp32) == 2
     prod = m.encode_q(torch.from_numpy(ids).cuda(), torch.from_numpy(mask).cuda(), None)
-    chain, e64 = _np(c.out).astype(np.float64), host_dense(name)["emb64"]
+    host = host_dense(gn, name)
+    chain, e64 = _np(c.out).astype(np.float64), host["emb64"]
     pr = _np(prod).astype(np.float64)
     d_cp, d_c64, d_p64 = np.abs(chain - pr), np.abs(chain - e64), np.abs(pr - e64)
     # everything in front of project.0: the product's head (bias -> fp32 epilogue, then the LayerNorm of the fp32 sums) on the CHAIN's last fp16
@@ -248,26 +287,39 @@ def test_a_forward_is_the_products_up_to_the_fp16_head(name):
                                      _p(out16), _p(out32), 0, _lib.current_stream_ptr()))
     torch.cuda.synchronize()
     biteq = same_bits(out32, prod.detach().to(torch.float32))
-    print(f"FWD {name}: mean |chain - encode_q| {d_cp.mean():.3e} (max {d_cp.max():.3e}); chain - model64 mean {d_c64.mean():.3e} max {d_c64.max():.3e}; "
+    d_r64 = np.abs(host["emb_reg"] - e64)
+    # the bar. TINY: the encoder test's. Any other geometry: twice the host regime's own forward distance to the fp64 model, max and mean --
+    # criterion E's argument: the device and the regime share the rounding points but not the summation orders, two draws of one size
+    bar = TINY_BAR if gn == "TINY" else (2.0 * d_r64.max(), 2.0 * d_r64.mean())
+    print(f"FWD {gn} {name}: regime - model64 mean {d_r64.mean():.3e} max {d_r64.max():.3e} (CPU); bar max {bar[0]:.3e} mean {bar[1]:.3e}")
+    print(f"FWD {gn} {name}: mean |chain - encode_q| {d_cp.mean():.3e} (max {d_cp.max():.3e}); chain - model64 mean {d_c64.mean():.3e} max {d_c64.max():.3e}; "
           f"encode_q - model64 mean {d_p64.mean():.3e} max {d_p64.max():.3e}; the chain in front of project.0 + the product's fp32 head == encode_q bit for bit: {biteq}")
     assert biteq, "the chain in front of project.0 does not compose to the product's forward"
     assert d_cp.mean() <= d_c64.mean() and d_cp.mean() <= d_p64.mean()
     for d in (d_c64, d_p64):
-        assert d.max() <= TINY_BAR[0] and d.mean() <= TINY_BAR[1]
-    print(f"WALL a {name} {time.time() - t0:.2f} s")
+        assert d.max() <= bar[0] and d.mean() <= bar[1]
+    print(f"WALL a {gn} {name} {time.time() - t0:.2f} s")
 
 
 # ---- B and C ---------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,scale", CONFIGS)
-def test_bc_stages_within_derived_bounds_and_wiring_bit_for_bit(name, scale):
+@pytest.mark.parametrize("gn,name,scale", cases(CONFIGS, BC_DEEP))
+def test_bc_stages_within_derived_bounds_and_wiring_bit_for_bit(gn, name, scale):
     from multihop_dense_retrieval_amd import layernorm
     t0 = time.time()
-    c = run((name, scale))
+    c = run(gn, name, scale)
     st = stages(c)
     torch.cuda.synchronize()
     check_wiring(c, st)
+    last = GEOMS[gn]["layers"] - 1
+    # a full layer behind a full layer (none on TINY): the gradient on its fp32 stream and the one on its fp16 copy are DENSE, every token row
+    # of both is non-zero, and both enter the same LayerNorm backward (check_wiring held them to the next layer's ln1 and qkv re-runs)
+    assert (last - 1 > 0) == (gn == "DEEP")
+    for i in range(last - 1):
+        g = [r for r in c.tape if r["label"] == f"L{i}.ln2"][0]["g"]
+        for k in ("y16", "y32"):
+            assert k in g, (i, k, "no gradient reached a middle layer's output")
+            assert bool(g[k][:c.T].ne(0).any(1).all()), (i, k, "a token row of a middle layer's incoming gradient is all zero")
     # the fp32 stream of the last full layer: zero but for the CLS rows, which hold the tail's first LayerNorm's dx32
-    last = GEOM["layers"] - 1
     ln2 = [r for r in c.tape if r["label"] == f"L{last - 1}.ln2"][0]
     d32 = ln2["g"]["y32"]
     rest = torch.ones(c.cap, dtype=torch.bool, device="cuda")
@@ -283,12 +335,12 @@ def test_bc_stages_within_derived_bounds_and_wiring_bit_for_bit(name, scale):
     want = dxq.clone()
     want[c.starts] = (dxq[c.starts].float() + d_cls.float()).to(torch.float16)
     assert same_bits(mine[:c.T], want[:c.T]) and same_bits(mine[:c.T], t.grad[:c.T])
-    print(f"WALL bc {name} scale {scale:g} {time.time() - t0:.2f} s")
+    print(f"WALL bc {gn} {name} scale {scale:g} {time.time() - t0:.2f} s")
 
 
-def test_bc_loss_stages_and_the_six_encode_sums():
+def _bc_loss_stages_and_the_six_encode_sums(gn):
     t0 = time.time()
-    cs, loss, P = run("loss")
+    cs, loss, P = run(gn, "loss")
     emb = {k: _np(cs[k].out) for k in ch.KEYS}
     ref = mhop_loss_ref.loss_and_grads(emb, o1=True)
     got = {k: _np(cs[k].tape[-1]["g"]["y32"]) for k in ch.KEYS}
@@ -304,65 +356,101 @@ def test_bc_loss_stages_and_the_six_encode_sums():
             per[k].update(pg)
     # autograd runs the node made last first: the fp32 sum starts with the last encode's term
     order = list(reversed(ch.KEYS))
-    for name in ch.param_names():
+    for name in ch.param_names(GEOMS[gn]):
         acc = per[order[0]][name].reshape(P[name].shape).clone()
         for k in order[1:]:
             acc = acc + per[k][name].reshape(P[name].shape)
         assert same_bits(P[name].grad, acc.contiguous()), name
-    print(f"WALL bc loss {time.time() - t0:.2f} s")
+    print(f"WALL bc {gn} loss {time.time() - t0:.2f} s")
 
 
-def test_c_two_whole_runs_give_the_same_bits():
+def test_bc_loss_stages_and_the_six_encode_sums():
+    _bc_loss_stages_and_the_six_encode_sums("TINY")
+
+
+def test_bc_loss_stages_and_the_six_encode_sums_on_deep():
+    _bc_loss_stages_and_the_six_encode_sums("DEEP")
+
+
+def _c_two_whole_runs_give_the_same_bits(gn):
     t0 = time.time()
-    a, b = run(("L160", 1.0)), dense_run("L160", 1.0)
+    a, b = run(gn, "L160", 1.0), dense_run(gn, "L160", 1.0)
     for k in a.P:
         assert same_bits(a.P[k].grad, b.P[k].grad), k
     assert same_bits(a.out, b.out)
-    _, loss_a, Pa = run("loss")
-    _, loss_b, Pb = loss_run()
+    _, loss_a, Pa = run(gn, "loss")
+    _, loss_b, Pb = loss_run(gn)
     assert same_bits(loss_a.reshape(1), loss_b.reshape(1))
     for k in Pa:
         assert same_bits(Pa[k].grad, Pb[k].grad), k
-    print(f"WALL c {time.time() - t0:.2f} s")
+    print(f"WALL c {gn} {time.time() - t0:.2f} s")
+
+
+def test_c_two_whole_runs_give_the_same_bits():
+    _c_two_whole_runs_give_the_same_bits("TINY")
+
+
+def test_c_two_whole_runs_give_the_same_bits_on_deep():
+    _c_two_whole_runs_give_the_same_bits("DEEP")
 
 
 # ---- D ---------------------------------------------------------------------------------------------------------------------------------------
-def test_d_unwritten_rows_are_never_read():
+def _d_unwritten_rows_are_never_read(gn):
     t0 = time.time()
-    run(("L160", 1.0))
-    poison()  # the premise: what torch.empty hands out after the seeding is NaN, in the chain's own sizes
+    geom = GEOMS[gn]
+    H = geom["hidden"]
+    run(gn, "L160", 1.0)
+    poison(geom=geom)  # the premise: what torch.empty hands out after the seeding is NaN, in the chain's own sizes
     probe = [torch.empty(s, dtype=d, device="cuda") for s, d in (((1280, H), torch.float16), ((1280, 3 * H), torch.float16), ((8, H), torch.float32))]
+    print(f"D {gn}: share of NaN in the probes {[round(float(torch.isnan(t).float().mean()), 4) for t in probe]}; reserved "
+          f"{torch.cuda.memory_reserved() >> 20} MiB, allocated {torch.cuda.memory_allocated() >> 20} MiB")
     assert all(bool(torch.isnan(t).all()) for t in probe), "the allocator did not hand the seeded blocks out: this test would show nothing"
     del probe
     for name in ch.BATCHES:
-        a, b = run((name, 1.0)), dense_run(name, 1.0, with_poison=True)
+        a, b = run(gn, name, 1.0), dense_run(gn, name, 1.0, with_poison=True)
         for k in a.P:
             assert torch.isfinite(b.P[k].grad).all(), (name, k)
             assert same_bits(a.P[k].grad, b.P[k].grad), (name, k)
-    _, _, Pa = run("loss")
-    _, loss_b, Pb = loss_run(with_poison=True)
+    _, _, Pa = run(gn, "loss")
+    _, loss_b, Pb = loss_run(gn, with_poison=True)
     assert torch.isfinite(loss_b)
     for k in Pa:
         assert torch.isfinite(Pb[k].grad).all(), k
         assert same_bits(Pa[k].grad, Pb[k].grad), k
-    print(f"WALL d {time.time() - t0:.2f} s")
+    print(f"WALL d {gn} {time.time() - t0:.2f} s")
+
+
+def test_d_unwritten_rows_are_never_read():
+    _d_unwritten_rows_are_never_read("TINY")
+
+
+def test_d_unwritten_rows_are_never_read_on_deep():
+    _d_unwritten_rows_are_never_read("DEEP")
 
 
 # ---- E ---------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,scale", CONFIGS)
-def test_e_gradients_against_the_fp64_model(name, scale):
+@pytest.mark.parametrize("gn,name,scale", cases(CONFIGS, CONFIGS))
+def test_e_gradients_against_the_fp64_model(gn, name, scale):
     t0 = time.time()
-    c, h = run((name, scale)), host_dense(name)
-    check_e(grads_np(c.P, scale), h["reg"][scale], h["g64"], [ch.batch(name)], f"{name} scale {scale:g}")
-    print(f"WALL e {name} scale {scale:g} {time.time() - t0:.2f} s")
+    geom = GEOMS[gn]
+    c, h = run(gn, name, scale), host_dense(gn, name)
+    check_e(grads_np(c.P, scale), h["reg"][scale], h["g64"], [ch.batch(name, geom)], f"{gn} {name} scale {scale:g}", geom)
+    print(f"WALL e {gn} {name} scale {scale:g} {time.time() - t0:.2f} s")
+
+
+def _e_loss_gradients_against_the_fp64_model(gn):
+    t0 = time.time()
+    _, loss, P = run(gn, "loss")
+    h = host_loss(gn)
+    (l64, g64, _, _), (lreg, g_reg, _, _) = h["m64"], h["reg"]
+    print(f"E {gn} loss: device {float(loss.detach()):.6f} regime {lreg:.6f} model64 {l64:.6f}")
+    check_e(grads_np(P), g_reg, g64, list(h["batches"].values()), f"{gn} in-batch loss", GEOMS[gn])
+    print(f"WALL e {gn} loss {time.time() - t0:.2f} s")
 
 
 def test_e_loss_gradients_against_the_fp64_model():
-    t0 = time.time()
-    _, loss, P = run("loss")
-    sd, batches = ch.state_dict(), ch.loss_batches()
-    l64, g64, _, _ = ch.grads_loss("model64", sd, GEOM, batches)
-    lreg, g_reg, _, _ = ch.grads_loss("regime", sd, GEOM, batches)
-    print(f"E loss: device {float(loss.detach()):.6f} regime {lreg:.6f} model64 {l64:.6f}")
-    check_e(grads_np(P), g_reg, g64, list(batches.values()), "in-batch loss")
-    print(f"WALL e loss {time.time() - t0:.2f} s")
+    _e_loss_gradients_against_the_fp64_model("TINY")
+
+
+def test_e_loss_gradients_against_the_fp64_model_on_deep():
+    _e_loss_gradients_against_the_fp64_model("DEEP")

@@ -1,55 +1,81 @@
-"""CPU: the host statements of the whole encoder's backward (tests/encoder_chain_ref.py) hold each other. model64 is the oracle's forward and
-tests/mhop_loss_ref.py's loss; a second correct implementation of the device chain's numerics (regime_b: fp32 arithmetic, the batch reversed)
-passes criterion E against the reference regime, and each wiring mutation fails it on at least one tensor. Every line prints its figures."""
+"""CPU: the host statements of the whole encoder's backward (tests/encoder_chain_ref.py) hold each other, on both geometries of the chain tests:
+oracle.seeded.TINY (two layers: the first and the CLS-only last) and DEEP (four layers: the smallest depth with a full layer behind a full
+layer). model64 is the oracle's forward and tests/mhop_loss_ref.py's loss; a second correct implementation of the device chain's numerics
+(regime_b: fp32 arithmetic, the batch reversed) passes criterion E against the reference regime, and each wiring mutation fails it on at least
+one tensor. The mutations of a middle layer change NOTHING on TINY and fail on DEEP: that is why DEEP exists. Every line prints its figures.
+
+A test that had no parameter keeps its name on TINY and has a sibling `..._on_deep`; a parametrised one keeps its TINY ids and gains `DEEP-...`."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import encoder_chain_ref as ch
 import mhop_loss_ref
-from oracle import roberta_torch
+from oracle import roberta_torch, seeded
 
-GEOM = ch.GEOM
-
-
-@pytest.fixture(scope="module")
-def sd():
-    return ch.state_dict()
+GEOMS = {"TINY": seeded.TINY, "DEEP": seeded.DEEP}
+TINY_MUTATIONS = tuple(m for m in ch.MUTATIONS if m not in ch.MID_MUTATIONS)
 
 
-@pytest.fixture(scope="module")
-def dense(sd):
-    """the L = 48 batch under the fixed cotangent: model64 and the regime, computed once"""
-    ids, mask = ch.batch("L48")
-    G = ch.cotangent(len(ids))
-    emb64, g64 = ch.grads_cotangent("model64", sd, GEOM, ids, mask, G)
-    emb_reg, g_reg = ch.grads_cotangent("regime", sd, GEOM, ids, mask, G)
+def both(values):
+    """the parameters (geometry name, value): TINY's ids are the bare values, as before the second geometry came"""
+    return [pytest.param(gn, v, id=(str(v) if gn == "TINY" else f"{gn}-{v}")) for gn in GEOMS for v in values]
+
+
+@functools.lru_cache(maxsize=None)
+def sd_of(gn):
+    return ch.state_dict(GEOMS[gn])
+
+
+@functools.lru_cache(maxsize=None)
+def dense_of(gn):
+    """the L = 48 batch under the fixed cotangent: model64 and the regime, computed once per geometry"""
+    geom, sd = GEOMS[gn], sd_of(gn)
+    ids, mask = ch.batch("L48", geom)
+    G = ch.cotangent(len(ids), geom)
+    emb64, g64 = ch.grads_cotangent("model64", sd, geom, ids, mask, G)
+    emb_reg, g_reg = ch.grads_cotangent("regime", sd, geom, ids, mask, G)
     return dict(ids=ids, mask=mask, G=G, emb64=emb64, g64=g64, emb_reg=emb_reg, g_reg=g_reg)
 
 
-@pytest.fixture(scope="module")
-def lossy(sd):
-    """the in-batch loss over six encodes: model64 and the regime, computed once"""
-    batches = ch.loss_batches()
-    return dict(batches=batches, m64=ch.grads_loss("model64", sd, GEOM, batches), reg=ch.grads_loss("regime", sd, GEOM, batches))
+@functools.lru_cache(maxsize=None)
+def lossy_of(gn):
+    """the in-batch loss over six encodes: model64 and the regime, computed once per geometry"""
+    geom, sd = GEOMS[gn], sd_of(gn)
+    batches = ch.loss_batches(geom)
+    return dict(batches=batches, m64=ch.grads_loss("model64", sd, geom, batches), reg=ch.grads_loss("regime", sd, geom, batches))
 
 
-def test_model64_forward_is_the_oracle(sd, dense):
+def _model64_forward_is_the_oracle(gn):
+    geom, sd, dense = GEOMS[gn], sd_of(gn), dense_of(gn)
     for name in ch.BATCHES:
-        ids, mask = ch.batch(name)
-        want = roberta_torch.encode(sd, GEOM, ids, mask, torch.float64).numpy()
+        ids, mask = ch.batch(name, geom)
+        want = roberta_torch.encode(sd, geom, ids, mask, torch.float64).numpy()
         with torch.no_grad():
-            got = ch.model64(ch.leaves(sd), GEOM, ids, mask).numpy()
+            got = ch.model64(ch.leaves(sd), geom, ids, mask).numpy()
         assert np.abs(got - want).max() <= 1e-9, name
-    assert np.abs(dense["emb64"] - roberta_torch.encode(sd, GEOM, dense["ids"], dense["mask"], torch.float64).numpy()).max() <= 1e-9
+    assert np.abs(dense["emb64"] - roberta_torch.encode(sd, geom, dense["ids"], dense["mask"], torch.float64).numpy()).max() <= 1e-9
     # the regime's forward is the oracle's restated mode-2 dataflow up to the roundings that regime keeps fp32 there (scores, P V, the GELU's
-    # input) and the fp16 head: inside the encoder test's TINY bar against fp64
+    # input) and the fp16 head: on TINY inside the encoder test's TINY bar against fp64. That bar belongs to TINY; on DEEP the distance is
+    # printed (it is the yardstick of the device forward there, tests/test_encoder_chain_gpu.py A)
     err = np.abs(dense["emb_reg"] - dense["emb64"])
-    print(f"regime forward against model64: max {err.max():.3e} mean {err.mean():.3e}")
-    assert err.max() <= 6e-3 and err.mean() <= 1.2e-3
+    print(f"{gn}: regime forward against model64: max {err.max():.3e} mean {err.mean():.3e}")
+    if gn == "TINY":
+        assert err.max() <= 6e-3 and err.mean() <= 1.2e-3
 
 
-def test_model64_loss_gradients_are_mhop_loss_ref(lossy):
+def test_model64_forward_is_the_oracle():
+    _model64_forward_is_the_oracle("TINY")
+
+
+def test_model64_forward_is_the_oracle_on_deep():
+    _model64_forward_is_the_oracle("DEEP")
+
+
+def _model64_loss_gradients_are_mhop_loss_ref(gn):
+    lossy = lossy_of(gn)
     loss, _, emb, demb = lossy["m64"]
     ref = mhop_loss_ref.loss_and_grads({k: emb[k] for k in ch.KEYS})
     assert abs(loss - ref["loss"]) <= 1e-9 * max(1.0, abs(ref["loss"]))
@@ -63,48 +89,102 @@ def test_model64_loss_gradients_are_mhop_loss_ref(lossy):
         assert np.abs(demb[k] - ref["grads"][k]).max() <= 1e-12, k
 
 
-def test_key_bias_gradient_is_zero_and_unused_rows_are_exact_zeros(dense, lossy):
+def test_model64_loss_gradients_are_mhop_loss_ref():
+    _model64_loss_gradients_are_mhop_loss_ref("TINY")
+
+
+def test_model64_loss_gradients_are_mhop_loss_ref_on_deep():
+    _model64_loss_gradients_are_mhop_loss_ref("DEEP")
+
+
+def _key_bias_gradient_is_zero_and_unused_rows_are_exact_zeros(gn):
     """softmax is shift-invariant along the keys: in fp64 the key bias's gradient is rounding noise next to its neighbours'"""
+    geom, dense, lossy = GEOMS[gn], dense_of(gn), lossy_of(gn)
+    assert len(ch.zero_grad_names(geom)) == geom["layers"]
     for g64, batches in ((dense["g64"], [(dense["ids"], dense["mask"])]), (lossy["m64"][1], list(lossy["batches"].values()))):
-        for k in ch.zero_grad_names():
+        for k in ch.zero_grad_names(geom):
             mine, qb = np.abs(g64[k]).max(), np.abs(g64[k.replace("key", "query")]).max()
-            print(f"{k}: max |g64| {mine:.3e}, the query bias's {qb:.3e}")
+            print(f"{gn}: {k}: max |g64| {mine:.3e}, the query bias's {qb:.3e}")
             assert mine <= 1e-12 * qb
-        zr = ch.zero_rows(batches)
+        zr = ch.zero_rows(batches, geom)
         assert zr.any() and not zr.all()
         assert not g64["encoder.embeddings.word_embeddings.weight"][zr].any()
         assert np.abs(g64["encoder.embeddings.word_embeddings.weight"][~zr]).max(axis=1).min() > 0
 
 
-@pytest.mark.parametrize("scale", [2.0 ** -10, 1.0, 256.0])
-def test_regime_b_passes_criterion_e(sd, dense, scale):
-    _, g_reg = ch.grads_cotangent("regime", sd, GEOM, dense["ids"], dense["mask"], dense["G"], scale) if scale != 1.0 else (None, dense["g_reg"])
-    _, g_b = ch.grads_cotangent("regime_b", sd, GEOM, dense["ids"], dense["mask"], dense["G"], scale)
-    rows, e_pool = ch.criterion_e(g_b, g_reg, dense["g64"])
-    print(ch.table(rows, e_pool, f"regime_b, L48, scale {scale:g}"))
-    print(f"worst share of the bar {max(r[4] for r in rows):.3f}")
+def test_key_bias_gradient_is_zero_and_unused_rows_are_exact_zeros():
+    _key_bias_gradient_is_zero_and_unused_rows_are_exact_zeros("TINY")
+
+
+def test_key_bias_gradient_is_zero_and_unused_rows_are_exact_zeros_on_deep():
+    _key_bias_gradient_is_zero_and_unused_rows_are_exact_zeros("DEEP")
+
+
+@pytest.mark.parametrize("gn,scale", both([2.0 ** -10, 1.0, 256.0]))
+def test_regime_b_passes_criterion_e(gn, scale):
+    geom, sd, dense = GEOMS[gn], sd_of(gn), dense_of(gn)
+    _, g_reg = ch.grads_cotangent("regime", sd, geom, dense["ids"], dense["mask"], dense["G"], scale) if scale != 1.0 else (None, dense["g_reg"])
+    _, g_b = ch.grads_cotangent("regime_b", sd, geom, dense["ids"], dense["mask"], dense["G"], scale)
+    rows, e_pool = ch.criterion_e(g_b, g_reg, dense["g64"], geom)
+    assert len(rows) == len(ch.param_names(geom)) - geom["layers"]
+    print(ch.table(rows, e_pool, f"{gn}: regime_b, L48, scale {scale:g}"))
+    print(f"{gn}: worst share of the bar {max(r[4] for r in rows):.3f}")
     assert not ch.failures(rows)
-    zr = ch.zero_rows([(dense["ids"], dense["mask"])])
+    zr = ch.zero_rows([(dense["ids"], dense["mask"])], geom)
     for g in (g_reg, g_b):
         assert not g["encoder.embeddings.word_embeddings.weight"][zr].any()
 
 
-def test_regime_b_passes_criterion_e_under_the_loss(sd, lossy):
-    g_b = ch.grads_loss("regime_b", sd, GEOM, lossy["batches"])[1]
-    rows, e_pool = ch.criterion_e(g_b, lossy["reg"][1], lossy["m64"][1])
-    print(ch.table(rows, e_pool, "regime_b, in-batch loss"))
-    print(f"worst share of the bar {max(r[4] for r in rows):.3f}")
+def _regime_b_passes_criterion_e_under_the_loss(gn):
+    geom, lossy = GEOMS[gn], lossy_of(gn)
+    g_b = ch.grads_loss("regime_b", sd_of(gn), geom, lossy["batches"])[1]
+    rows, e_pool = ch.criterion_e(g_b, lossy["reg"][1], lossy["m64"][1], geom)
+    print(ch.table(rows, e_pool, f"{gn}: regime_b, in-batch loss"))
+    print(f"{gn}: worst share of the bar {max(r[4] for r in rows):.3f}")
     assert not ch.failures(rows)
 
 
-@pytest.mark.parametrize("mutation", ch.MUTATIONS)
-def test_every_mutation_fails_criterion_e(sd, dense, lossy, mutation):
-    if mutation == "last_call_only":  # only the loss uses the weights more than once
-        g_m = ch.grads_loss("regime", sd, GEOM, lossy["batches"], mutation)[1]
-        rows, _ = ch.criterion_e(g_m, lossy["reg"][1], lossy["m64"][1])
-    else:
-        _, g_m = ch.grads_cotangent("regime", sd, GEOM, dense["ids"], dense["mask"], dense["G"], 1.0, mutation)
-        rows, _ = ch.criterion_e(g_m, dense["g_reg"], dense["g64"])
+def test_regime_b_passes_criterion_e_under_the_loss():
+    _regime_b_passes_criterion_e_under_the_loss("TINY")
+
+
+def test_regime_b_passes_criterion_e_under_the_loss_on_deep():
+    _regime_b_passes_criterion_e_under_the_loss("DEEP")
+
+
+def mutated_rows(gn, mutation):
+    """(the mutated regime's gradients, criterion E's rows for them): under the loss for last_call_only (only the loss uses the weights more
+    than once), under the dense cotangent otherwise"""
+    geom, sd = GEOMS[gn], sd_of(gn)
+    if mutation == "last_call_only":
+        lossy = lossy_of(gn)
+        g_m = ch.grads_loss("regime", sd, geom, lossy["batches"], mutation)[1]
+        return g_m, ch.criterion_e(g_m, lossy["reg"][1], lossy["m64"][1], geom)[0]
+    dense = dense_of(gn)
+    _, g_m = ch.grads_cotangent("regime", sd, geom, dense["ids"], dense["mask"], dense["G"], 1.0, mutation)
+    return g_m, ch.criterion_e(g_m, dense["g_reg"], dense["g64"], geom)[0]
+
+
+@pytest.mark.parametrize("gn,mutation", [pytest.param("TINY", m, id=m) for m in TINY_MUTATIONS] + [pytest.param("DEEP", m, id="DEEP-" + m) for m in ch.MUTATIONS])
+def test_every_mutation_fails_criterion_e(gn, mutation):
+    _, rows = mutated_rows(gn, mutation)
     bad = ch.failures(rows)
-    print(f"{mutation}: {len(bad)} of {len(rows)} tensors over the bar, up to {max(r[4] for r in rows):.3g} x")
+    print(f"{gn}: {mutation}: {len(bad)} of {len(rows)} tensors over the bar, up to {max(r[4] for r in rows):.3g} x")
+    assert bad
+
+
+@pytest.mark.parametrize("mutation", ch.MID_MUTATIONS)
+def test_two_layers_cannot_show_a_middle_layers_defect(mutation):
+    """the blind spot that DEEP closes. A defect in the hand-off from a full layer to a full layer (0 < i < layers - 1) leaves every TINY
+    gradient EQUAL to the unmutated regime's, element for element: no test on TINY can see it, whatever its tolerance. On DEEP it fails
+    criterion E."""
+    assert GEOMS["TINY"]["layers"] == 2 and GEOMS["DEEP"]["layers"] >= 4
+    g_m, rows = mutated_rows("TINY", mutation)
+    g_reg = dense_of("TINY")["g_reg"]
+    assert set(g_m) == set(g_reg)
+    differ = [k for k in g_reg if not np.array_equal(g_m[k], g_reg[k])]
+    assert not differ and not ch.failures(rows), differ
+    _, rows = mutated_rows("DEEP", mutation)
+    bad = ch.failures(rows)
+    print(f"{mutation}: TINY 0 of {len(g_reg)} tensors differ from the regime's; DEEP {len(bad)} of {len(rows)} over the bar, up to {max(r[4] for r in rows):.3g} x")
     assert bad
