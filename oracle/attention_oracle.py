@@ -44,14 +44,10 @@ v_exp_f32 / v_rcp_f32; no term was taken from an fp32 CPU restatement or from a 
 """
 import numpy as np
 
-U32 = 2.0 ** -24
-H16 = 2.0 ** -11
-Z16 = 2.0 ** -25
-MIN16 = 2.0 ** -14
-X1ULP = 2.0 ** -23
+from oracle.fp import H16, LOG2E32, N16, U32, X1ULP, Z16, exp2_32, fma32
+
 JOB = 96
 PAIR = 32
-LOG2E32 = np.float32(1.4426950408889634)
 
 MUTATIONS = ("a_extra_key", "b_drop_last", "c_swap_v", "d_skip_o_rescale", "e_skip_l_rescale", "f_patch_prev", "f_patch_none", "g_next_head_k",
              "h_first_block_q", "i_job_shift")
@@ -126,18 +122,18 @@ def reference_and_bound(qkv, cu, heads, kernel):
         th = (1 + A) * (1 + C) / (1 - Abar) - 1
         if kernel == 2:
             ehi = e * (1 + np.expm1(dS) + Aexp)
-            r = np.where(ehi >= MIN16, H16 * ehi, Z16)
+            r = np.where(ehi >= N16, H16 * ehi, Z16)
             r = r * np.exp(mk - M) / W * (1 + C) / (1 - Abar) * (1 + A.max(axis=2, keepdims=True))
         else:
             phi = p * (1 + th)
-            r = np.where(phi >= MIN16, H16 * phi, Z16)
+            r = np.where(phi >= N16, H16 * phi, Z16)
         dP = p * th + r
         acc_c = (n * U32) if kernel == 3 else (npad * X1ULP + njobs * U32)
         absV = np.abs(V)
         o = p @ V
         err = dP @ absV + acc_c * ((p + dP) @ absV)
         y = np.abs(o) + err
-        err = err + np.where(y >= MIN16, H16 * y, Z16)
+        err = err + np.where(y >= N16, H16 * y, Z16)
         _store(ref, cu, b, kernel, o)
         _store(bnd, cu, b, kernel, err)
     return ref, bnd
@@ -164,12 +160,12 @@ def cls_rows(x, cu):
     return x[np.asarray(cu[:-1], dtype=np.int64)]
 
 
-def _exp2_32(t):
-    return np.exp2(t.astype(np.float32)).astype(np.float32)
-
-
-def _fma32(a, b, c):  # one rounding: the fp64 product of two fp32 is exact
-    return (a.astype(np.float64) * np.float64(b) + np.asarray(c, np.float64)).astype(np.float32)
+def locator(cu, kernel):
+    """index (row, column) of a kernel's output -> "sequence b, len n, head h": the `where` of fp.assert_within"""
+    def where(at):
+        b = at[0] if kernel == 3 else int(np.searchsorted(cu, at[0], side="right") - 1)
+        return f"sequence {b}, len {int(cu[b + 1] - cu[b])}, head {at[1] // 64}"
+    return where
 
 
 def emulate(qkv, cu, heads, kernel, mutation=None, mut_job=1):
@@ -210,7 +206,7 @@ def emulate(qkv, cu, heads, kernel, mutation=None, mut_job=1):
                 Vp = np.concatenate([Vp, np.zeros_like(V[:, :1])], axis=1)
             s = (Q @ Kp.transpose(0, 2, 1)) * f32(0.125)
             mx = s.max(axis=2, keepdims=True)
-            e = _exp2_32((s - mx) * LOG2E32)
+            e = exp2_32((s - mx) * LOG2E32)
             inv = f32(1) / e.sum(axis=2, keepdims=True, dtype=f32)
             p16 = (e * inv).astype(np.float16)
             o = p16.astype(f32) @ Vp
@@ -240,8 +236,8 @@ def emulate(qkv, cu, heads, kernel, mutation=None, mut_job=1):
             s[:, :, dead] = -np.inf
             m_new = np.maximum(m_run, s.max(axis=2, keepdims=True))
             with np.errstate(invalid="ignore"):
-                alpha = _exp2_32((m_run - m_new) * LOG2E32)              # 0 on the first job
-            e = _exp2_32(_fma32(s, LOG2E32, -m_new * LOG2E32))
+                alpha = exp2_32((m_run - m_new) * LOG2E32)              # 0 on the first job
+            e = exp2_32(fma32(s, LOG2E32, -m_new * LOG2E32))
             csum = e.sum(axis=2, keepdims=True, dtype=f32)
             skip = job == mut_job
             l_run = (l_run if (mutation == "e_skip_l_rescale" and skip) else l_run * alpha) + csum

@@ -55,9 +55,8 @@ Where the interval crosses at most one boundary this IS the one-neighbour rule.
 """
 import numpy as np
 
-U = 2.0 ** -24
-SENTINEL = 777.0          # float buffers: finite, fp16-exact, far outside every expected output
-ISENTINEL = -123456789    # int buffers
+from oracle import fp
+from oracle.fp import U32
 
 
 # ---- integer results ---------------------------------------------------------------------------------------------------------------------
@@ -120,7 +119,7 @@ def ln_inputs(inp, res=None):
     if res is None:
         return x, np.zeros_like(x)
     x = x + np.asarray(res).astype(np.float64)
-    return x, U * np.abs(x)
+    return x, U32 * np.abs(x)
 
 
 def embed_rows(ids_flat, src, pid, word, pos, typ, ty=None, reader_L=None):
@@ -138,7 +137,7 @@ def embed_inputs(word, pos, typ, wid, prow, trow):
     """-> (x, dx) for x = (word[wid] + pos[prow]) + type[trow]: two rounded adds."""
     w, p, t = (np.asarray(a).astype(np.float64) for a in (word[wid], pos[prow], typ[trow]))
     x = w + p + t
-    return x, U * np.abs(w + p) + U * np.abs(x)
+    return x, U32 * np.abs(w + p) + U32 * np.abs(x)
 
 
 def bound(x, dx, g, b, eps):
@@ -152,18 +151,18 @@ def bound(x, dx, g, b, eps):
     d = x - mu
     A = mean(d * d) + eps
     r = 1.0 / np.sqrt(A)
-    dmu = mean(dx) + D * U * mean(np.abs(x)) + 3 * U * np.abs(mu)
-    e = dx + U * (np.abs(d) + dmu + dx)
-    rho_A = (2 * mean(np.abs(d) * e) + mean((dmu + e) ** 2)) / A + (D + 5) * U
+    dmu = mean(dx) + D * U32 * mean(np.abs(x)) + 3 * U32 * np.abs(mu)
+    e = dx + U32 * (np.abs(d) + dmu + dx)
+    rho_A = (2 * mean(np.abs(d) * e) + mean((dmu + e) ** 2)) / A + (D + 5) * U32
     with np.errstate(divide="ignore", invalid="ignore"):
-        hi = np.where(rho_A < 1, (1 - np.minimum(rho_A, 1 - 1e-300)) ** -0.5 * (1 + 2 * U) - 1, np.inf)
-    lo = 1 - (1 + rho_A) ** -0.5 * (1 - 2 * U)
+        hi = np.where(rho_A < 1, (1 - np.minimum(rho_A, 1 - 1e-300)) ** -0.5 * (1 + 2 * U32) - 1, np.inf)
+    lo = 1 - (1 + rho_A) ** -0.5 * (1 - 2 * U32)
     rho_r = np.maximum(hi, lo)
     t = np.abs(d) * r
-    dt = r * (dmu + e) * (1 + rho_r) + t * (rho_r + U)
+    dt = r * (dmu + e) * (1 + rho_r) + t * (rho_r + U32)
     y = np.abs(d * r * g + b)
     ag = np.abs(g)
-    return (ag * dt + U * ag * (t + dt) + U * (y + ag * dt)) * (1 + 2.0 ** -10)
+    return (ag * dt + U32 * ag * (t + dt) + U32 * (y + ag * dt)) * (1 + 2.0 ** -10)
 
 
 # ---- the assertions both tests apply -------------------------------------------------------------------------------------------------------
@@ -176,12 +175,9 @@ def assert_f32(got, ref, bnd, label=""):
     got = np.asarray(got)
     assert got.dtype == np.float32 and got.shape == ref.shape, (label, got.dtype, got.shape, ref.shape)
     assert np.isfinite(bnd).all(), f"{label}: the bound says nothing here (rho_A >= 1): not a family to test with"
-    err = np.abs(got.astype(np.float64) - ref)
-    ratio = np.where(bnd > 0, err / np.where(bnd > 0, bnd, 1), np.where(err == 0, 0.0, np.inf))
-    worst = float(ratio.max()) if ratio.size else 0.0
+    worst, i = fp.worst_ratio(got, ref, bnd)
     if not worst <= 1.0:
-        i = np.unravel_index(np.nanargmax(np.where(np.isnan(ratio), np.inf, ratio)), ratio.shape)
-        raise AssertionError(f"{label}: {int((~(ratio <= 1)).sum())} fp32 elements outside the bound; worst {worst:.3g} x at {tuple(int(k) for k in i)}: "
+        raise AssertionError(f"{label}: {int((~(np.abs(got.astype(np.float64) - ref) <= bnd)).sum())} fp32 elements outside the bound; worst {worst:.3g} x at {i}: "
                              f"got {got[i]!r}, reference {ref[i]!r}, bound {bnd[i]:.3e}")
     return worst
 
@@ -216,16 +212,16 @@ def assert_ints(got, exp, name, label=""):
         raise AssertionError(f"{label}: {name} differs in {int((got != exp).sum())} places; first at {i}: got {int(got.reshape(-1)[i])}, expected {int(exp.reshape(-1)[i])}")
 
 
-def assert_pack(got, ids, mask, pad_id, label=""):
-    """got: dict of the hook's buffers, each starting as ISENTINEL: lens [B], cu [B + 1], total [1], order [B], tok_src / tok_pid [B * L]."""
+def assert_pack(got, ids, mask, pad_id, sentinel, label=""):
+    """got: dict of the hook's buffers, each starting as `sentinel`: lens [B], cu [B + 1], total [1], order [B], tok_src / tok_pid [B * L]."""
     exp = pack(ids, mask, pad_id)
     B, T = len(exp["lens"]), int(exp["total"][0])
     for k in ("lens", "cu", "total"):
         assert_ints(got[k], exp[k], k, label)
-    assert_ints(got["order"], exp["order"] if B <= 1024 else np.full(B, ISENTINEL, np.int32), "order", label)
+    assert_ints(got["order"], exp["order"] if B <= 1024 else np.full(B, sentinel, np.int32), "order", label)
     for k in ("tok_src", "tok_pid"):
         assert_ints(got[k][:T], exp[k], k, label)
-        assert_ints(got[k][T:], np.full(len(got[k]) - T, ISENTINEL, np.int32), k + " beyond total", label)
+        assert_ints(got[k][T:], np.full(len(got[k]) - T, sentinel, np.int32), k + " beyond total", label)
 
 
 # ---- input families ------------------------------------------------------------------------------------------------------------------------
@@ -282,7 +278,7 @@ def _f16_max(rng, R, H):
 
 def _f16_subnormal(rng, R, H):
     g, b = _affine(rng, H)
-    return (rng.integers(-1023, 1024, (R, H)) * 2.0 ** -24).astype(np.float32), g, b  # every fp16 subnormal magnitude is k * 2^-24, k < 1024
+    return (rng.integers(-1023, 1024, (R, H)) * (2 * fp.Z16)).astype(np.float32), g, b  # every fp16 subnormal magnitude is k * 2^-24, k < 1024
 
 
 # name -> (generator(rng, rows, H) -> (x fp32 [rows, H], g, b), the input types it applies to, the eps values it runs with)
@@ -366,9 +362,9 @@ def f16_conversion_values():
     parities), values just beside the ties, the subnormal range and below, the overflow threshold, zeros, infinities, NaN."""
     k = np.arange(1024, dtype=np.float64)
     ties = 1.0 + (k + 0.5) * 2.0 ** -10
-    sub_ties = (np.arange(0, 1024) + 0.5) * 2.0 ** -24
+    sub_ties = (np.arange(0, 1024) + 0.5) * (2 * fp.Z16)   # (the fp16 subnormal spacing, 2^-24)
     vals = np.concatenate([ties, -ties, np.nextafter(ties.astype(np.float32), np.float32(0)), np.nextafter(ties.astype(np.float32), np.float32(4)),
-                           sub_ties, -sub_ties, np.arange(0, 1024) * 2.0 ** -24, [2.0 ** -25, np.nextafter(np.float32(2.0 ** -25), np.float32(1)), 2.0 ** -26, 1e-30, 1e-45],
+                           sub_ties, -sub_ties, np.arange(0, 1024) * (2 * fp.Z16), [2.0 ** -25, np.nextafter(np.float32(2.0 ** -25), np.float32(1)), 2.0 ** -26, 1e-30, 1e-45],
                            [65504.0, -65504.0, 65519.0, -65519.0, 65519.996, 65520.0, -65520.0, 65536.0, 1e38, 0.0, -0.0, np.inf, -np.inf, np.nan]])
     return vals.astype(np.float32)
 

@@ -49,14 +49,10 @@ second implementation of the dataflow: the host test shows that it stays inside 
 import numpy as np
 import torch
 
-U32 = 2.0 ** -24
-X1ULP = 2.0 ** -23
-H16 = 2.0 ** -11
-Z16 = 2.0 ** -25
+from oracle.fp import F16_MAX, H16, LOG2E32, U32, X1ULP, Z16, exp2_32, fma32
+
 CHUNK = 64       # swept rows per step of the MFMA kernels, and owners per workgroup
 TILE = 16        # rows of an MFMA tile
-LOG2E32 = np.float32(1.4426950408889634)
-F16_MAX = 65504.0
 
 MUTATIONS = ("extra_key", "drop_last_key", "no_delta", "no_scale_dq", "no_scale_dk", "dk_next_head", "dv_unnormalised", "first_block_do",
              "cls_dq_next_row")
@@ -90,10 +86,6 @@ def _store(out, cu, b, heads, dQ, dK, dV):
     for i, x in enumerate((dQ, dK, dV)):
         rows[:x.shape[1], i * hidden:(i + 1) * hidden] = x.transpose(1, 0, 2).reshape(x.shape[1], hidden)
     return n
-
-
-def _r16(y):
-    return np.maximum(H16 * y, Z16)
 
 
 def _T(x):
@@ -212,15 +204,6 @@ def reference(qkv, dctx, cu, heads, mode=0):
     return ref
 
 
-def _exp2_32(t):
-    with np.errstate(under="ignore"):
-        return np.exp2(t.astype(np.float32)).astype(np.float32)
-
-
-def _fma32(a, b, c):  # one rounding: the fp64 product of two fp32 is exact
-    return (a.astype(np.float64) * np.float64(b) + np.asarray(c, np.float64)).astype(np.float32)
-
-
 def emulate(qkv, dctx, cu, heads, mode=0, mutation=None):
     """The kernels' dataflow in numpy: fp32 scores and dP, the running (max, sum, sum of e dP) over chunks of 64 keys (mode 3: one pass against the
     true maximum), lse and delta in fp32, p = exp2((s - lse) log2 e), dS = p (dP - delta), fp16 p and dS as contraction operands, fp32
@@ -263,7 +246,7 @@ def emulate(qkv, dctx, cu, heads, mode=0, mutation=None):
         with np.errstate(invalid="ignore", under="ignore"):
             if mode == 3:
                 mx = s.max(axis=2, keepdims=True)
-                e = _exp2_32((s - mx) * LOG2E32)
+                e = exp2_32((s - mx) * LOG2E32)
                 inv = f32(1) / e.sum(axis=2, keepdims=True, dtype=f32)
                 delta = (e * dP).sum(axis=2, keepdims=True, dtype=f32) * inv
                 p = e * inv
@@ -275,18 +258,18 @@ def emulate(qkv, dctx, cu, heads, mode=0, mutation=None):
                 for c0 in range(0, nk, CHUNK):
                     sc, dc = s[:, :, c0:c0 + CHUNK], dP[:, :, c0:c0 + CHUNK]
                     m_new = np.maximum(m_run, sc.max(axis=2, keepdims=True))
-                    alpha = _exp2_32((m_run - m_new) * LOG2E32)
-                    e = _exp2_32(_fma32(sc, LOG2E32, -m_new * LOG2E32))
+                    alpha = exp2_32((m_run - m_new) * LOG2E32)
+                    e = exp2_32(fma32(sc, LOG2E32, -m_new * LOG2E32))
                     l_run = l_run * alpha + e.sum(axis=2, keepdims=True, dtype=f32)
                     d_run = d_run * alpha + (e * dc).sum(axis=2, keepdims=True, dtype=f32)
                     m_run = m_new
                 lse = m_run + np.log(l_run).astype(f32)
                 delta = d_run / l_run
-                p = _exp2_32((s - lse) * LOG2E32)
+                p = exp2_32((s - lse) * LOG2E32)
             if mutation == "no_delta":
                 delta = np.zeros_like(delta)
             dS16 = (p * (dP - delta)).astype(np.float16).astype(f32)
-            pv = _exp2_32((s - m_run) * LOG2E32) if mutation == "dv_unnormalised" else p
+            pv = exp2_32((s - m_run) * LOG2E32) if mutation == "dv_unnormalised" else p
             p16 = pv.astype(np.float16).astype(f32)
         dQ = (dS16 @ Kp) * f32(8.0 if mutation == "no_scale_dq" else 0.125)
         dK = (_T(dS16) @ Q) * f32(8.0 if mutation == "no_scale_dk" else 0.125)
@@ -300,17 +283,6 @@ def emulate(qkv, dctx, cu, heads, mode=0, mutation=None):
             dQ = np.concatenate([np.zeros_like(dQ), dQ], axis=1)
         _store(out, cu, b, heads, dQ, dK, dV)
     return out
-
-
-def worst_ratio(got, ref, bnd):
-    """(largest |got - ref| / bound, its (row, column)); an element with bound 0 must be exact, a non-finite value where the reference is finite is
-    infinitely far."""
-    err = np.abs(np.asarray(got, np.float64) - ref)
-    err = np.where(np.isfinite(err), err, np.inf)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.where(err == 0, 0.0, err / bnd)
-    i = np.unravel_index(np.argmax(ratio), ratio.shape)
-    return float(ratio[i]), (int(i[0]), int(i[1]))
 
 
 # ---- makers for dctx -----------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """Host restatement of the embedding backward (include/mdr_embedding_grad.h): the plan in numpy, the five gradients in fp64, a derived
 elementwise error bound, an fp32 emulation of the kernels' dataflow (plan, pieces, order; with switchable mutations) and makers for the
-inputs. numpy only; nothing here is measured from a kernel. Test helper (tests/test_embedding_grad_host.py, tests/test_embedding_grad_gpu.py).
+inputs. numpy (the int sentinel comes from tests/guarded.py); nothing here is measured from a kernel. Test helper (tests/test_embedding_grad_host.py, tests/test_embedding_grad_gpu.py).
 
 A case is a dict: ids int64 (any shape, indexed flat by tok_src), tok_src / tok_pid int32 [cap], total, word fp32 [vocab, H], pos fp32
 [max_pos, H], type0, g fp32 [H], dy16 None or fp16 [cap, H], dy2 None or fp16 / fp32 [cap, H], pad_row.
@@ -32,9 +32,11 @@ v_rsq_f32; no term was read off a device.
 import numpy as np
 
 import layernorm_grad_ref as lref
+from guarded import ISENTINEL
+from oracle import fp
 from oracle import trunk_rows_oracle as tr
+from oracle.fp import U32
 
-U = tr.U
 P = 16                        # MDR_EMBEDDING_PIECE
 PLAN_HEADER = 16
 PLAN_MAGIC = 0x4D455031
@@ -44,7 +46,6 @@ MAX_CHUNKS = 1024
 MAX_PARTIAL_BYTES = 4 << 20
 EPS = 1e-5
 VOCAB, MAX_POS = 97, 40       # small tables: collisions are the rule
-SENTINEL, ISENTINEL = tr.SENTINEL, tr.ISENTINEL
 OUTPUTS = ("d", "dword", "dpos", "dtype0", "dg", "db")
 
 MUTATIONS = ("pad_not_skipped", "oob_dropped", "last_token_dropped", "first_piece_dropped", "pos_from_src", "dtype0_mean", "accumulate_ignored",
@@ -161,32 +162,32 @@ def ln_terms(x, ex, dy16, dy2, g, eps):
     G = np.asarray(g, np.float64)
     dy, Edy = lref._dy64(dy16, dy2, m)
     a = dy * G
-    Ea = np.abs(G) * Edy + U * (np.abs(a) + np.abs(G) * Edy)
+    Ea = np.abs(G) * Edy + U32 * (np.abs(a) + np.abs(G) * Edy)
     c1 = mean(a)
-    Ec1 = mean(Ea) + D * U * mean(np.abs(a) + Ea) + 3 * U * np.abs(c1)
+    Ec1 = mean(Ea) + D * U32 * mean(np.abs(a) + Ea) + 3 * U32 * np.abs(c1)
     p = a * t
     Ep = at * Ea + (np.abs(a) + Ea) * Et
-    Ep = Ep + U * (np.abs(p) + Ep)
+    Ep = Ep + U32 * (np.abs(p) + Ep)
     c2 = mean(p)
-    Ec2 = mean(Ep) + D * U * mean(np.abs(p) + Ep) + 3 * U * np.abs(c2)
+    Ec2 = mean(Ep) + D * U32 * mean(np.abs(p) + Ep) + 3 * U32 * np.abs(c2)
     q = t * c2
     Eq = at * Ec2 + (np.abs(c2) + Ec2) * Et
-    Eq = Eq + U * (np.abs(q) + Eq)
+    Eq = Eq + U32 * (np.abs(q) + Eq)
     E1 = Ea + Ec1
-    E1 = E1 + U * (np.abs(a - c1) + E1)
+    E1 = E1 + U32 * (np.abs(a - c1) + E1)
     w = a - c1 - q
     Ew = E1 + Eq
-    Ew = Ew + U * (np.abs(w) + Ew)
+    Ew = Ew + U32 * (np.abs(w) + Ew)
     d = r * w
     Ed = r * (1 + rho_r) * Ew
-    Ed = (Ed + np.abs(d) * (rho_r + U) + U * Ed) * (1 + 2.0 ** -10)
+    Ed = (Ed + np.abs(d) * (rho_r + U32) + U32 * Ed) * (1 + 2.0 ** -10)
     return dict(d=d, Ed=Ed, dy=dy, Edy=Edy, t=t, Et=Et)
 
 
 def _sum_bound(term, Eterm, nadd, old):
     """value and bound of a sum of terms (axis 0) that pass through at most nadd additions, the old value last"""
     o = np.zeros(term.shape[1]) if old is None else old.astype(np.float64)
-    return term.sum(axis=0) + o, (Eterm.sum(axis=0) + nadd * U * ((np.abs(term) + Eterm).sum(axis=0) + np.abs(o))) * (1 + 2.0 ** -10)
+    return term.sum(axis=0) + o, (Eterm.sum(axis=0) + nadd * U32 * ((np.abs(term) + Eterm).sum(axis=0) + np.abs(o))) * (1 + 2.0 ** -10)
 
 
 def _table(d, Ed, keys, nrows, pad_row, old):
@@ -225,7 +226,7 @@ def reference_and_bound(case, eps=EPS, old=None, d_given=None):
         dy, Edy, t, Et = T["dy"], T["Edy"], T["t"], T["Et"]
         term = dy * t
         Eterm = np.abs(t) * Edy + (np.abs(dy) + Edy) * Et
-        Eterm = Eterm + U * (np.abs(term) + Eterm)
+        Eterm = Eterm + U32 * (np.abs(term) + Eterm)
         out["dg"] = _sum_bound(term, Eterm, nadd, old.get("dg"))
         out["db"] = _sum_bound(dy, Edy, nadd, old.get("db"))
     return out
@@ -339,8 +340,8 @@ def emulate(case, eps=EPS, old=None, accumulate=False, mutation=None):
 
 
 def worst_shares(got, rb, keys=None):
-    """{output: largest |got - ref| / bound} (layernorm_grad_ref.worst_ratio per output)"""
-    return {k: lref.worst_ratio(got[k], *rb[k])[0] for k in (keys or rb) if k in got}
+    """{output: largest |got - ref| / bound} (oracle/fp.py, worst_ratio, per output)"""
+    return {k: fp.worst_ratio(got[k], *rb[k])[0] for k in (keys or rb) if k in got}
 
 
 # ---- makers --------------------------------------------------------------------------------------------------------------------------------
@@ -419,10 +420,6 @@ def make_flat(counts, seed, cap_extra=3, vocab=VOCAB, max_pos=MAX_POS):
     src, pid = np.full(cap, ISENTINEL, np.int32), np.full(cap, ISENTINEL, np.int32)
     src[:total], pid[:total] = np.arange(total), rng.integers(0, max_pos, total)
     return dict(ids=ids, tok_src=src, tok_pid=pid, total=total)
-
-
-def grid(shape, seed, scale=1.0):
-    return lref.grid(shape, seed, scale)
 
 
 def exact_tables(case, d32, old=None):

@@ -2,20 +2,16 @@
 package's differentiable functions (Chain, with a tape of every call and a hook on every output), its leaves (params), the NaN seeding of the
 caching allocator (poison), the bit comparisons, and criterion E's assertion (check_e). The host side is tests/encoder_chain_ref.py.
 Chain, params, poison and check_e take the geometry (oracle.seeded.TINY or DEEP); the default is TINY."""
-import ctypes
 import functools
 
 import numpy as np
 import torch
 
 import encoder_chain_ref as ch
+from multihop_dense_retrieval_amd._lib import ptr
 
 GEOM = ch.GEOM
 E_ = "encoder.embeddings."
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _np(t):
@@ -83,7 +79,7 @@ class Chain:
         tids, tmask = torch.from_numpy(ids).cuda(), torch.from_numpy(mask).cuda()
         i32 = lambda n: torch.zeros(n, dtype=torch.int32, device="cuda")  # noqa: E731
         lens, cu, total, order, src, pid = i32(B), i32(B + 1), i32(1), i32(B), i32(self.cap), i32(self.cap)
-        _lib.check(_lib.lib().mdr_test_pack(_p(tids), _p(tmask), B, L, PAD, _p(lens), _p(cu), _p(total), _p(order), _p(src), _p(pid), 0, _lib.current_stream_ptr()))
+        _lib.check(_lib.lib().mdr_test_pack(ptr(tids), ptr(tmask), B, L, PAD, ptr(lens), ptr(cu), ptr(total), ptr(order), ptr(src), ptr(pid), 0, _lib.current_stream_ptr()))
         self.ids, self.cu, self.total, self.src, self.pid = tids, cu, total, src, pid
         self.T = int(mask.sum())
         self.starts = torch.from_numpy(np.concatenate([[0], np.cumsum(mask.sum(1))[:-1]]).astype(np.int64)).cuda()

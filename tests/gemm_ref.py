@@ -9,7 +9,7 @@ z = x w^T + b accumulated in fp32.
 
 The grid
 --------
-x, w multiples of 1/8 of magnitude at most 2 (linear_grad_ref.grid), b and res multiples of 1/8 of magnitude at most 2: every product is a
+x, w multiples of 1/8 of magnitude at most 2 (oracle/fp.py, grid), b and res multiples of 1/8 of magnitude at most 2: every product is a
 multiple of 1/64 of magnitude at most 4, so any fp32 sum of K <= 4096 of them plus the bias and the residual is a whole number of 1/64 that
 stays below 2^24 of them: exact in any order. exact() asserts that condition. fp32 outputs must EQUAL it, fp16 outputs its one
 round-to-nearest-even.
@@ -25,7 +25,7 @@ From the rounding points listed above gelu_erf2, for an EXACT fp32 u, g = u Phi(
   add loses half an ulp of the result, counted twice to cover |g'| instead of |g|:
       e32 = |u| (PHI_ERR + X1ULP) + 2 U32 |g|.
   For a > 16 the clamp replaces Phi(-a) by Phi(-16) < 1e-57: covered by PHI_ERR.
-  5. the fp16 rounding r(y) = max(H16 y, Z16) of a value of magnitude at most y (as linear_grad_ref._r16):
+  5. the fp16 rounding r(y) = max(H16 y, Z16) of a value of magnitude at most y (oracle/fp.py, r16):
       gelu_bound = e32 + r(|g| + e32).
 When u itself carries an error du (realistic rows), |gelu'| <= 1.13 turns it into 1.13 du and the terms above are taken at |u| + du.
 
@@ -40,7 +40,8 @@ import numpy as np
 import torch
 
 import linear_grad_ref as lref
-from linear_grad_ref import F16_MAX, H16, PHI_ERR, U32, X1ULP, Z16, _exp2_32, _fma32, _fma32v, _r16, bias, grid, realistic, worst_ratio  # noqa: F401
+from linear_grad_ref import PHI_ERR, bias, realistic  # noqa: F401
+from oracle.fp import F16_MAX, H16, U32, X1ULP, Z16, exp2_32, fma32, r16
 
 GELU_MUTATIONS = ("no_clamp", "no_half_x", "sign_lost")
 GEMM_MUTATIONS = ("drop_k_tile", "row_off_by_one", "neighbour_bias", "double_round16")
@@ -117,11 +118,11 @@ def gelu32(u, mutation=None):
     u = np.asarray(u, f32)
     a = np.abs(u) if mutation == "no_clamp" else np.minimum(np.abs(u), f32(CLAMP))
     with np.errstate(over="ignore", invalid="ignore"):
-        p = _fma32(a, -1.982813420e-05, 6.620948925e-04)
+        p = fma32(a, -1.982813420e-05, 6.620948925e-04)
         for c in (-7.759194708e-03, 5.296392132e-02, 4.590664427e-01, 1.151119066e+00):
-            p = _fma32v(p, a, c)
-        e = _fma32v(p, a, 1.0)
-        t = _exp2_32(-e)
+            p = fma32(p, a, c)
+        e = fma32(p, a, 1.0)
+        t = exp2_32(-e)
         s = f32(0.5) - t
         if mutation != "sign_lost":
             s = np.copysign(s, u)
@@ -140,7 +141,7 @@ def gelu_err32(u, du=0.0):
 def gelu_bound(u, du=0.0):
     """the absolute error allowed for the fp16 GELU output"""
     e = gelu_err32(u, du)
-    return e + _r16(np.abs(gelu64(u)) + e)
+    return e + r16(np.abs(gelu64(u)) + e)
 
 
 def gelu_bound_torch(u):
@@ -167,7 +168,7 @@ def reference_and_bound(x, w, b, epilogue, res=None, res_added=True):
         return z, ez
     if epilogue == 0:
         assert float((np.abs(z) + ez).max(initial=0)) < F16_MAX
-        return z, ez + _r16(np.abs(z) + ez)
+        return z, ez + r16(np.abs(z) + ez)
     assert float((np.abs(z) + ez).max(initial=0)) < F16_MAX
     return gelu64(z), gelu_bound(z, ez)
 

@@ -46,9 +46,8 @@ that it stays inside the bound and that each mutation leaves it.
 import numpy as np
 
 from oracle import trunk_rows_oracle as tr
+from oracle.fp import F16_MAX, U32
 
-U = tr.U
-F16_MAX = 65504.0
 MAX_CHUNKS = 1024             # target number of workgroups ...
 MAX_PARTIAL_BYTES = 4 << 20   # ... as far as the partial sums [S][2][H] stay within 4 MiB
 WAVES = 4
@@ -132,15 +131,15 @@ def stats(x, ex, eps):
     d = x - mu
     A = _mean(d * d) + eps
     r = 1.0 / np.sqrt(A)
-    dmu = _mean(ex) + D * U * _mean(np.abs(x)) + 3 * U * np.abs(mu)
-    e = ex + U * (np.abs(d) + dmu + ex)
-    rho_A = (2 * _mean(np.abs(d) * e) + _mean((dmu + e) ** 2)) / A + (D + 5) * U
+    dmu = _mean(ex) + D * U32 * _mean(np.abs(x)) + 3 * U32 * np.abs(mu)
+    e = ex + U32 * (np.abs(d) + dmu + ex)
+    rho_A = (2 * _mean(np.abs(d) * e) + _mean((dmu + e) ** 2)) / A + (D + 5) * U32
     with np.errstate(divide="ignore", invalid="ignore"):
-        hi = np.where(rho_A < 1, (1 - np.minimum(rho_A, 1 - 1e-300)) ** -0.5 * (1 + 2 * U) - 1, np.inf)
-    lo = 1 - (1 + rho_A) ** -0.5 * (1 - 2 * U)
+        hi = np.where(rho_A < 1, (1 - np.minimum(rho_A, 1 - 1e-300)) ** -0.5 * (1 + 2 * U32) - 1, np.inf)
+    lo = 1 - (1 + rho_A) ** -0.5 * (1 - 2 * U32)
     rho_r = np.maximum(hi, lo)
     t = d * r
-    Et = r * (dmu + e) * (1 + rho_r) + np.abs(t) * (rho_r + U)
+    Et = r * (dmu + e) * (1 + rho_r) + np.abs(t) * (rho_r + U32)
     return dict(mu=mu, d=d, r=r, t=t, Et=Et, rho_r=rho_r)
 
 
@@ -149,7 +148,7 @@ def _dy64(dy16, dy2, m):
     parts = [p[:m].astype(np.float64) for p in (dy16, dy2) if p is not None]
     assert parts, "dy16 and dy2 are both None"
     dy = parts[0] if len(parts) == 1 else parts[0] + parts[1]
-    return dy, (U * np.abs(dy) if len(parts) == 2 else np.zeros_like(dy))
+    return dy, (U32 * np.abs(dy) if len(parts) == 2 else np.zeros_like(dy))
 
 
 def reference_and_bound(inp, res, dy16, dy2, g, eps=EPS, m=None, old_dg=None, old_db=None):
@@ -167,32 +166,32 @@ def reference_and_bound(inp, res, dy16, dy2, g, eps=EPS, m=None, old_dg=None, ol
     G = np.asarray(g, np.float64)
     dy, Edy = _dy64(dy16, dy2, m)
     a = dy * G
-    Ea = np.abs(G) * Edy + U * (np.abs(a) + np.abs(G) * Edy)
+    Ea = np.abs(G) * Edy + U32 * (np.abs(a) + np.abs(G) * Edy)
     c1 = _mean(a)
-    Ec1 = _mean(Ea) + D * U * _mean(np.abs(a) + Ea) + 3 * U * np.abs(c1)
+    Ec1 = _mean(Ea) + D * U32 * _mean(np.abs(a) + Ea) + 3 * U32 * np.abs(c1)
     p = a * t
     Ep = at * Ea + (np.abs(a) + Ea) * Et
-    Ep = Ep + U * (np.abs(p) + Ep)
+    Ep = Ep + U32 * (np.abs(p) + Ep)
     c2 = _mean(p)
-    Ec2 = _mean(Ep) + D * U * _mean(np.abs(p) + Ep) + 3 * U * np.abs(c2)
+    Ec2 = _mean(Ep) + D * U32 * _mean(np.abs(p) + Ep) + 3 * U32 * np.abs(c2)
     q = t * c2
     Eq = at * Ec2 + (np.abs(c2) + Ec2) * Et
-    Eq = Eq + U * (np.abs(q) + Eq)
+    Eq = Eq + U32 * (np.abs(q) + Eq)
     E1 = Ea + Ec1
-    E1 = E1 + U * (np.abs(a - c1) + E1)
+    E1 = E1 + U32 * (np.abs(a - c1) + E1)
     w = a - c1 - q
     Ew = E1 + Eq
-    Ew = Ew + U * (np.abs(w) + Ew)
+    Ew = Ew + U32 * (np.abs(w) + Ew)
     dx = r * w
     Edx = r * (1 + rho_r) * Ew
-    Edx = (Edx + np.abs(dx) * (rho_r + U) + U * Edx) * (1 + 2.0 ** -10)
+    Edx = (Edx + np.abs(dx) * (rho_r + U32) + U32 * Edx) * (1 + 2.0 ** -10)
     assert m == 0 or float((np.abs(dx) + Edx).max()) < F16_MAX, "dx leaves the fp16 range: scale dy down"
-    nadd = (rpc // WAVES + 4 + S + 1) * U
+    nadd = (rpc // WAVES + 4 + S + 1) * U32
     odg = np.zeros(H) if old_dg is None else old_dg.astype(np.float64)
     odb = np.zeros(H) if old_db is None else old_db.astype(np.float64)
     term = dy * t
     Eterm = at * Edy + (np.abs(dy) + Edy) * Et
-    Eterm = Eterm + U * (np.abs(term) + Eterm)
+    Eterm = Eterm + U32 * (np.abs(term) + Eterm)
     dg = term.sum(axis=0) + odg
     Edg = (Eterm.sum(axis=0) + nadd * ((np.abs(term) + Eterm).sum(axis=0) + np.abs(odg))) * (1 + 2.0 ** -10)
     db = dy.sum(axis=0) + odb
@@ -311,20 +310,6 @@ def emulate(inp, res, dy16, dy2, g, eps=EPS, m=None, old_dg=None, old_db=None, m
     return dx16, dx32, dg, db
 
 
-def worst_ratio(got, ref, bnd):
-    """(largest |got - ref| / bound, its index); an element with bound 0 must be exact, a non-finite value where the reference is finite is
-    infinitely far."""
-    got, ref, bnd = (np.atleast_2d(np.asarray(a, np.float64)) for a in (got, ref, bnd))
-    if got.size == 0:
-        return 0.0, (0, 0)
-    err = np.abs(got - ref)
-    err = np.where(np.isfinite(err), err, np.inf)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.where(err == 0, 0.0, err / bnd)
-    i = np.unravel_index(np.argmax(ratio), ratio.shape)
-    return float(ratio[i]), (int(i[0]), int(i[1]))
-
-
 # ---- makers --------------------------------------------------------------------------------------------------------------------------------
 def _rows(family, rng, M, H):
     if family == "unit":
@@ -365,8 +350,3 @@ def make_case(family, combo, M, H, seed, dy_scale=1.0):
         dy2 = d.astype(np.float16 if dy2_type == "f16" else np.float32)
     return dict(inp=inp, res=res, dy16=dy16, dy2=dy2, g=g)
 
-
-def grid(shape, seed, scale=1.0):
-    """float32: seeded multiples of 1/8 in [-2, 2], times `scale` (a power of two); exact in fp16 too."""
-    rng = np.random.default_rng([seed, *shape, 7])
-    return (rng.integers(-16, 17, size=shape) / 8.0 * scale).astype(np.float32)

@@ -48,16 +48,12 @@ that it stays inside the bound and that each mutation leaves it.
 import numpy as np
 import torch
 
-U32 = 2.0 ** -24
-X1ULP = 2.0 ** -23
-H16 = 2.0 ** -11
-Z16 = 2.0 ** -25
-N16 = 2.0 ** -14  # fp16's smallest normal: the exponent field of every subnormal and of zero
+from oracle.fp import F16_MAX, N16, U32, X1ULP, exp2_32, fma32, r16
+
 PHI_ERR = 2.1e-7
 SLAB = 64        # token rows per staged slab of the weight-gradient kernel
 TILE = 128       # edge of a dW tile
 TARGET_WGS = 512
-F16_MAX = 65504.0
 C_EXP = -0.72134752044448170   # -log2(e) / 2
 K_PHI = 0.3989422804014327     # 1 / sqrt(2 pi)
 
@@ -102,10 +98,6 @@ def chunks(M, N, K):
     return (slabs + per - 1) // per, per * SLAB
 
 
-def _r16(y):
-    return np.maximum(H16 * y, Z16)
-
-
 def gelu_grad64(u):
     """Phi(u) + u phi(u) in float64."""
     u = np.asarray(u, np.float64)
@@ -121,30 +113,17 @@ def gelu_grad_bound(u):
     return PHI_ERR + U32 + uphi * (X1ULP + 3 * U32 + 2 * np.log(2.0) * U32 * arg) + u * 2.0 ** -126 + U32 * np.abs(gelu_grad64(u))
 
 
-def _fma32(a, b, c):  # one rounding: the fp64 product of two fp32 is exact
-    return (np.asarray(a, np.float32).astype(np.float64) * np.float64(np.float32(b)) + np.float64(np.float32(c))).astype(np.float32)
-
-
-def _fma32v(a, b, c):
-    return (a.astype(np.float64) * b.astype(np.float64) + np.float64(np.float32(c))).astype(np.float32)
-
-
-def _exp2_32(t):
-    with np.errstate(under="ignore", over="ignore"):
-        return np.exp2(t.astype(np.float32)).astype(np.float32)
-
-
 def gelu_grad32(u, mutation=None):
     """The kernel's fp32 gelu'(u): the forward's tail polynomial at min(|u|, 16) for Phi, one exp2 for phi."""
     f32 = np.float32
     u = np.asarray(u, np.float16).astype(f32)
     a = np.minimum(np.abs(u), f32(16))
-    p = _fma32(a, -1.982813420e-05, 6.620948925e-04)
+    p = fma32(a, -1.982813420e-05, 6.620948925e-04)
     for c in (-7.759194708e-03, 5.296392132e-02, 4.590664427e-01, 1.151119066e+00):
-        p = _fma32v(p, a, c)
-    e = _fma32v(p, a, 1.0)
-    s = np.copysign(f32(0.5) - _exp2_32(-e), u)
-    dens = _exp2_32(u * u * f32(C_EXP)) * f32(K_PHI)
+        p = fma32(p, a, c)
+    e = fma32(p, a, 1.0)
+    s = np.copysign(f32(0.5) - exp2_32(-e), u)
+    dens = exp2_32(u * u * f32(C_EXP)) * f32(K_PHI)
     if mutation == "gelu_no_uphi":
         return s + f32(0.5)
     return (s + f32(0.5)) + u * dens
@@ -205,12 +184,12 @@ def reference_and_bound(x, w, dy, pre=None, m=None, old_dw=None, old_db=None):
         g = gelu_grad64(u)
         dz = DY * g
         e = np.abs(DY) * gelu_grad_bound(u) + U32 * np.abs(dz)
-        edz = e + _r16(np.abs(dz) + e)
+        edz = e + r16(np.abs(dz) + e)
         assert m == 0 or float((np.abs(dz) + edz).max()) < F16_MAX, "dZ leaves the fp16 range: scale dy down"
     adz = np.abs(dz) + edz
     dx = dz @ W
     e = edz @ np.abs(W) + gemm_accum_bound(adz, np.abs(W), N) + field_floor_term(adz, np.abs(W))
-    edx = e + _r16(np.abs(dx) + e)
+    edx = e + r16(np.abs(dx) + e)
     assert m == 0 or float((np.abs(dx) + edx).max()) < F16_MAX, "dX leaves the fp16 range: scale w down"
     cnt = ((m + SLAB - 1) // SLAB * SLAB + S + 1) * X1ULP
     odw = np.zeros((N, K)) if old_dw is None else old_dw.astype(np.float64)
@@ -276,27 +255,7 @@ def emulate(x, w, dy, pre=None, m=None, old_dw=None, old_db=None, mutation=None)
     return dx, dw, db
 
 
-def worst_ratio(got, ref, bnd):
-    """(largest |got - ref| / bound, its index); an element with bound 0 must be exact, a non-finite value where the reference is finite is
-    infinitely far."""
-    got, ref, bnd = (np.atleast_2d(np.asarray(a, np.float64)) for a in (got, ref, bnd))
-    if got.size == 0:
-        return 0.0, (0, 0)
-    err = np.abs(got - ref)
-    err = np.where(np.isfinite(err), err, np.inf)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.where(err == 0, 0.0, err / bnd)
-    i = np.unravel_index(np.argmax(ratio), ratio.shape)
-    return float(ratio[i]), (int(i[0]), int(i[1]))
-
-
 # ---- makers --------------------------------------------------------------------------------------------------------------------------------
-def grid(shape, seed, scale=1.0):
-    """float16: seeded multiples of 1/8 in [-2, 2], times `scale` (a power of two)."""
-    rng = np.random.default_rng([seed, *shape, 7])
-    return (rng.integers(-16, 17, size=shape) / 8.0 * scale).astype(np.float16)
-
-
 def realistic(M, N, K, seed, dy_scale=1.0):
     """(x, w, dy) float16: N(0, 1) activations, weights x 0.02, N(0, 1) gradients times dy_scale (a loss scale)."""
     rng = np.random.default_rng([seed, M, N, K, 3])

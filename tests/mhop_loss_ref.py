@@ -28,7 +28,8 @@ kernels and for any other correct fp32 evaluation, and it is far below what any 
 """
 import numpy as np
 
-U32 = 2.0 ** -24
+from oracle.fp import U32
+
 KEYS = ("q", "q_sp1", "c1", "c2", "neg_1", "neg_2")
 MUTATIONS = ("no_mask", "no_onehot", "no_inv_b", "no_queue_in_lse", "swap_dneg", "hop2_target_i", "dctx_no_hop2")
 

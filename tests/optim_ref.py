@@ -5,20 +5,17 @@ checks the kernels against the model."""
 import numpy as np
 import torch
 
+from oracle.fp import U32, gamma
+
 F = np.float32
 CHUNK = 4096
-U = 2.0 ** -24
-
-
-def gamma(k):
-    return k * U / (1 - k * U)
 
 
 # csrc/mdr_optim.hip, rounding points 1 - 3: a term passes through at most 30 fp32 roundings on its way into a chunk sum (inv, the product and
 # the square count five, the thread's 16 additions, the butterfly's 6, the waves' 3), every term is >= 0, so a chunk sum is within gamma_30 of
 # its exact value; the chunk sums are added in fp64 (n_chunks * 2^-53: nothing); the square root halves a relative error; fp32(sqrt) adds u,
 # and one more u pays for the fp64 steps and the second-order terms.
-NORM_REL_BOUND = gamma(30) / 2 + 2 * U
+NORM_REL_BOUND = gamma(30) / 2 + 2 * U32
 
 
 def chunks(sizes):

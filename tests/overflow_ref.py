@@ -22,9 +22,8 @@ import numpy as np
 import layernorm_grad_ref as nref
 import linear_grad_ref as lref
 import optim_ref
+from oracle.fp import F16_EDGE, F16_MAX
 
-F16_MAX = 65504.0
-F16_EDGE = 65520.0
 LEFT_OUT, FINITE, INF, POISON = 0, 1, 2, 3
 NAMES = {LEFT_OUT: "left out", FINITE: "finite", INF: "inf", POISON: "poison"}
 MAX_LEFT_OUT, MIN_CLASS = 0.02, 0.05   # the caps: share of the live elements of one output

@@ -16,11 +16,13 @@ import numpy as np
 import pytest
 import torch
 
+from guarded import Guarded
 from oracle import attention_oracle as ao
+from oracle import fp
+from oracle.fp import bits
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 777.0  # finite, fp16-exact, far outside every expected output
 GUARD = 64        # rows of ctx in front of and behind the call's own, which must keep their bits
 EDGES = [1, 2, 15, 16, 17, 31, 32, 33, 64, 95, 96, 97, 127, 128, 129, 160, 191, 192, 193, 255, 256, 257, 288, 289, 300, 383, 384, 385, 480, 511, 512]
 SHORT = [1, 31, 100, 128]  # sequences that end before the second query block
@@ -64,18 +66,11 @@ def run(qkv, cu, heads, kernel, L, order=None):
     q = torch.from_numpy(qkv).cuda()
     c = torch.from_numpy(np.asarray(cu, np.int32)).cuda()
     o = torch.from_numpy(np.asarray(order, np.int32)).cuda() if order is not None else None
-    buf = torch.full((GUARD + rows + GUARD, hidden), SENTINEL, dtype=torch.float16, device="cuda")
-    own = buf[GUARD:GUARD + rows]
-    _lib.check(lib.mdr_test_attention(q.data_ptr(), c.data_ptr(), o.data_ptr() if o is not None else None, B, L, hidden, heads, kernel, own.data_ptr(),
+    ctx = Guarded(rows, (hidden,), torch.float16, GUARD, GUARD)
+    _lib.check(lib.mdr_test_attention(q.data_ptr(), c.data_ptr(), o.data_ptr() if o is not None else None, B, L, hidden, heads, kernel, ctx.own.data_ptr(),
                                       0, _lib.current_stream_ptr()))
     torch.cuda.synchronize()
-    got = buf.cpu().numpy()
-    assert (got[:GUARD] == np.float16(SENTINEL)).all() and (got[GUARD + rows:] == np.float16(SENTINEL)).all(), "rows outside the call were written"
-    return got[GUARD:GUARD + rows]
-
-
-def bits(x):
-    return np.ascontiguousarray(x).view(np.uint16)
+    return ctx.checked()
 
 
 def first_mismatch(got, exp, cu, kernel):
@@ -89,14 +84,8 @@ def first_mismatch(got, exp, cu, kernel):
 
 def check_bound(got, qkv, cu, heads, kernel, label):
     ref, bnd = ao.reference_and_bound(qkv, cu, heads, kernel)
-    ratio = np.abs(got.astype(np.float64) - ref) / bnd
-    worst = float(ratio.max())
+    worst = fp.assert_within(got, ref, bnd, f"{label} kernel {kernel}", ao.locator(cu, kernel))
     print(f"RATIO kernel={kernel} {label} worst |err| / bound = {worst:.4f}")
-    if worst > 1.0:
-        r, c = (int(x) for x in np.unravel_index(ratio.argmax(), ratio.shape))
-        b = r if kernel == 3 else int(np.searchsorted(cu, r, side="right") - 1)
-        pytest.fail(f"{label} kernel {kernel}: {int((ratio > 1).sum())} elements outside the bound; worst {worst:.3f} at row {r} (sequence {b}, len "
-                    f"{int(cu[b + 1] - cu[b])}), column {c}: got {float(got[r, c])!r}, reference {ref[r, c]!r}, bound {bnd[r, c]:.3e}")
     return worst
 
 

@@ -17,19 +17,17 @@ import pytest
 import torch
 
 import attention_grad_ref as ref
+from guarded import E_INVALID, E_WORKSPACE, OK, SENTINEL, Guarded
+from multihop_dense_retrieval_amd._lib import ptr
 from oracle import attention_oracle as ao
+from oracle import fp
+from oracle.fp import bits
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 777.0  # finite, fp16-exact, far outside every expected output
 GUARD = 64        # rows of dqkv in front of and behind the call's own, which must keep their bits
-OK, E_INVALID, E_WORKSPACE = 0, -1, -4
 LENS = [pytest.param(1, 129, ref.LENS_SWEEP, id="h1-L129-sweep")] + [
     pytest.param(12, 512, ref.LENS_EDGES[g::4], id=f"h12-L512-edges{g}") for g in range(4)]
-
-
-def bits(x):
-    return np.ascontiguousarray(x).view(np.uint16)
 
 
 def call(qkv, dctx, cu, heads, L, mode, out, ws="auto", stream="current"):
@@ -39,8 +37,7 @@ def call(qkv, dctx, cu, heads, L, mode, out, ws="auto", stream="current"):
     B, hidden = cu.numel() - 1, 64 * heads
     need = int(lib.mdr_attention_backward_workspace_bytes(B, L, heads, mode))
     w = torch.empty(max(need, 16), dtype=torch.uint8, device="cuda") if ws == "auto" else ws
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    return lib.mdr_attention_backward(p(qkv), p(dctx), p(cu), B, L, hidden, heads, mode, p(out), p(w), w.numel() if w is not None else 0, 0,
+    return lib.mdr_attention_backward(ptr(qkv), ptr(dctx), ptr(cu), B, L, hidden, heads, mode, ptr(out), ptr(w), w.numel() if w is not None else 0, 0,
                                       _lib.current_stream_ptr() if stream == "current" else stream)
 
 
@@ -52,27 +49,25 @@ def run(qkv, dctx, cu, heads, L, mode=0):
     assert lens.max() <= L and lens.min() >= 0  # the caller's promise
     T, hidden = int(cu[-1]), 64 * heads
     assert qkv.shape == (T, 3 * hidden) and dctx.shape == ((len(cu) - 1) if mode == 3 else T, hidden)
-    buf = torch.full((GUARD + T + GUARD, 3 * hidden), SENTINEL, dtype=torch.float16, device="cuda")
+    dqkv = Guarded(T, (3 * hidden,), torch.float16, GUARD, GUARD)
     _lib.check(call(torch.from_numpy(qkv).cuda(), torch.from_numpy(dctx).cuda(), torch.from_numpy(np.asarray(cu, np.int32)).cuda(), heads, L, mode,
-                    buf[GUARD:GUARD + T]))
+                    dqkv.own))
     torch.cuda.synchronize()
-    got = buf.cpu().numpy()
-    assert (got[:GUARD] == np.float16(SENTINEL)).all() and (got[GUARD + T:] == np.float16(SENTINEL)).all(), "rows outside the call were written"
-    return got[GUARD:GUARD + T]
+    return dqkv.checked()
 
 
 def check_bound(got, qkv, dctx, cu, heads, mode, label, parts=(0, 1, 2)):
     r, bnd = ref.reference_and_bound(qkv, dctx, cu, heads, mode)
     hidden = 64 * heads
     cols = np.concatenate([np.arange(i * hidden, (i + 1) * hidden) for i in parts])
-    worst, (row, col) = ref.worst_ratio(got[:, cols], r[:, cols], bnd[:, cols])
+
+    def where(at):
+        col = int(cols[at[1]])
+        b = int(np.searchsorted(cu, at[0], side="right") - 1)
+        return f"sequence {b}, len {int(cu[b + 1] - cu[b])}, token {at[0] - int(cu[b])}, column {col}: {'dQ dK dV'.split()[col // hidden]}, head {col % hidden // 64}"
+
+    worst = fp.assert_within(got[:, cols], r[:, cols], bnd[:, cols], f"{label} mode {mode}", where)
     print(f"RATIO mode={mode} {label} worst |err| / bound = {worst:.4f}")
-    if worst > 1.0:
-        col = int(cols[col])
-        b = int(np.searchsorted(cu, row, side="right") - 1)
-        pytest.fail(f"{label} mode {mode}: outside the bound; worst {worst:.3f} at row {row} (sequence {b}, len {int(cu[b + 1] - cu[b])}, token "
-                    f"{row - int(cu[b])}), column {col} ({'dQ dK dV'.split()[col // hidden]}, head {col % hidden // 64}): got {float(got[row, col])!r}, "
-                    f"reference {r[row, col]!r}, bound {bnd[row, col]:.3e}")
     return r, bnd
 
 
@@ -241,7 +236,7 @@ def test_first_query_mode_against_every_query_mode():
     d0 = ref.dctx_first_rows(d3, cu, hidden)
     g3, g0 = run(qkv, d3, cu, heads, L, 3), run(qkv, d0, cu, heads, L, 0)
     r3, b3 = check_bound(g3, qkv, d3, cu, heads, 3, "first query, mode 3")
-    worst, at = ref.worst_ratio(g0, r3, b3)  # the SAME reference and bound
+    worst, at = fp.worst_ratio(g0, r3, b3)  # the SAME reference and bound
     print(f"RATIO mode=0 on mode 3's reference worst |err| / bound = {worst:.4f}")
     first = np.zeros(int(cu[-1]), bool)
     first[np.asarray(cu[:-1], np.int64)] = True

@@ -8,6 +8,7 @@ import torch
 
 import attention_grad_ref as ref
 from oracle import attention_oracle as ao
+from oracle import fp
 
 
 def test_fp64_statement_agrees_with_torch_autograd():
@@ -41,7 +42,7 @@ def test_emulation_stays_inside_the_bound(heads, lens, family, scale):
     for mode in (0, 3):
         dctx = ref.dctx_grid(len(lens) if mode == 3 else int(cu[-1]), 64 * heads, 2, scale)
         r, bnd = ref.reference_and_bound(qkv, dctx, cu, heads, mode)
-        worst, at = ref.worst_ratio(ref.emulate(qkv, dctx, cu, heads, mode), r, bnd)
+        worst, at = fp.worst_ratio(ref.emulate(qkv, dctx, cu, heads, mode), r, bnd)
         print(f"RATIO emulation mode={mode} family={family} scale={scale} worst |err| / bound = {worst:.4f}")
         assert worst <= 1.0, (mode, worst, at)
 
@@ -56,9 +57,9 @@ def test_each_mutation_leaves_the_bound(mutation):
         qkv, cu = ao.FAMILIES[family](lens, heads, 11)
         dctx = ref.dctx_grid(len(lens) if mode == 3 else int(cu[-1]), 64 * heads, 2)
         r, bnd = ref.reference_and_bound(qkv, dctx, cu, heads, mode)
-        assert ref.worst_ratio(ref.emulate(qkv, dctx, cu, heads, mode), r, bnd)[0] <= 1.0
-        worst, _ = ref.worst_ratio(ref.emulate(qkv, dctx, cu, heads, mode, mutation), r, bnd)
-        if worst > 1.0:
+        assert fp.worst_ratio(ref.emulate(qkv, dctx, cu, heads, mode), r, bnd)[0] <= 1.0
+        worst, _ = fp.worst_ratio(ref.emulate(qkv, dctx, cu, heads, mode, mutation), r, bnd)
+        if not worst <= 1.0:
             caught.append(family)
     print(f"mutation {mutation}: outside the bound on {caught}")
     assert caught, mutation

@@ -9,15 +9,12 @@ import numpy as np
 import pytest
 
 from oracle import attention_oracle as ao
+from oracle import fp
 
 LENS = [1, 2, 3, 15, 16, 17, 18, 31, 32, 33, 63, 64, 65, 95, 96, 97, 127, 128, 129, 130, 160, 191, 192, 193, 224, 255, 256, 257, 288, 289, 300,
         383, 384, 385, 480, 481, 511, 512]
 HEADS = 2
 KERNELS = (1, 2, 3)
-
-
-def worst_ratio(got, ref, bnd):
-    return float((np.abs(got.astype(np.float64) - ref) / bnd).max())
 
 
 @pytest.mark.parametrize("family", sorted(ao.FAMILIES))
@@ -28,9 +25,8 @@ def test_emulation_sits_inside_the_bound(family):
         assert np.isfinite(bnd).all() and (bnd > 0).all()
         full = ao.reference(qkv, cu, HEADS)
         assert np.allclose(ref, ao.cls_rows(full, cu) if kernel == 3 else full, rtol=0, atol=1e-12)  # (fp64; BLAS may order a one-row product apart)
-        r = worst_ratio(ao.emulate(qkv, cu, HEADS, kernel), ref, bnd)
+        r = fp.assert_within(ao.emulate(qkv, cu, HEADS, kernel), ref, bnd, f"{family} kernel {kernel}", ao.locator(cu, kernel))
         print(f"{family} kernel {kernel}: emulate worst |err| / bound = {r:.3f}")
-        assert r <= 1.0, (family, kernel, r)
 
 
 def test_bound_is_of_the_size_of_two_fp16_roundings():
@@ -57,7 +53,7 @@ def test_onehot_is_bit_exact_and_its_margin_holds():
         exp = ao.cls_rows(expected, cu) if kernel == 3 else expected
         assert np.array_equal(got.view(np.uint16), exp.view(np.uint16)), kernel
         ref, bnd = ao.reference_and_bound(qkv, cu, HEADS, kernel)
-        assert worst_ratio(exp, ref, bnd) <= 1.0
+        fp.assert_within(exp, ref, bnd, f"onehot kernel {kernel}", ao.locator(cu, kernel))
 
 
 def test_uniform_ones_are_bit_known():
@@ -97,6 +93,22 @@ MUTATION_CASES = {
 }
 
 
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_a_planted_nan_fails_the_check_of_the_gpu_test(kernel):
+    """One NaN in a live row of a correct output: the comparison tests/test_attention_gpu.py applies must fail and name the element. (A
+    `ratio.max() > 1.0` does not: the maximum is NaN and the comparison False.)"""
+    lens = [5, 97, 33]
+    qkv, cu = ao.FAMILIES["realistic1"](lens, HEADS, 11)
+    ref, bnd = ao.reference_and_bound(qkv, cu, HEADS, kernel)
+    got = ao.emulate(qkv, cu, HEADS, kernel)
+    assert fp.assert_within(got, ref, bnd, "clean", ao.locator(cu, kernel)) <= 1.0
+    row = 1 if kernel == 3 else 5 + 40
+    got[row, 64 + 3] = np.nan
+    assert fp.worst_ratio(got, ref, bnd) == (np.inf, (row, 67))
+    with pytest.raises(AssertionError, match=r"1 element\(s\) outside the bound.*\(%d, 67\).*sequence 1, len 97, head 1.*got nan" % row):
+        fp.assert_within(got, ref, bnd, "planted", ao.locator(cu, kernel))
+
+
 def test_every_mutation_has_cases():
     assert sorted(MUTATION_CASES) == sorted(ao.MUTATIONS)
 
@@ -107,10 +119,10 @@ def test_mutation_violates_the_bound(mutation):
     for family, kernel in MUTATION_CASES[mutation]:
         qkv, cu = _inputs(family)
         ref, bnd = ao.reference_and_bound(qkv, cu, HEADS, kernel)
-        assert worst_ratio(ao.emulate(qkv, cu, HEADS, kernel), ref, bnd) <= 1.0  # the unmutated dataflow passes the same check
+        fp.assert_within(ao.emulate(qkv, cu, HEADS, kernel), ref, bnd, f"{family} kernel {kernel}")  # the unmutated dataflow passes the same check
         for mut_job in ((1, 2, 5) if mutation in ("d_skip_o_rescale", "e_skip_l_rescale") else (1,)):
-            r = worst_ratio(ao.emulate(qkv, cu, HEADS, kernel, mutation, mut_job), ref, bnd)
-            print(f"mutation {mutation} (job {mut_job}) on {family}, kernel {kernel}: worst |err| / bound = {r:.3g} -> {'CAUGHT' if r > 1 else 'missed'}")
-            caught.append(r > 1.0)
+            r = fp.worst_ratio(ao.emulate(qkv, cu, HEADS, kernel, mutation, mut_job), ref, bnd)[0]
+            print(f"mutation {mutation} (job {mut_job}) on {family}, kernel {kernel}: worst |err| / bound = {r:.3g} -> {'missed' if r <= 1.0 else 'CAUGHT'}")
+            caught.append(not r <= 1.0)
     assert caught[0], f"{mutation} slips through its first designed input"
     assert all(caught), f"{mutation} slips through some designed input: {caught}"

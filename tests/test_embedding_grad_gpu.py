@@ -13,32 +13,20 @@ values) with guard rows behind it, the plan as ISENTINEL; tok_src / tok_pid hold
 Token counts: 1, 3, 4, 5 and a few hundred; and embedding_grad_ref.BL_LARGE, a batch of 150 sequences, where a wave walks three tokens of a
 chunk, chunks lie behind `total` and table rows own more than the 8 pieces that the scatter sums per round (segments of up to 232 pieces).
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import embedding_grad_ref as ref
+from guarded import E_INVALID, E_WORKSPACE, ISENTINEL, SENTINEL, Guarded, assert_untouched, dev
+from multihop_dense_retrieval_amd._lib import ptr
+from oracle import fp
+from oracle.fp import bits
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL, ISENTINEL = ref.SENTINEL, ref.ISENTINEL
 GUARD = 8  # rows of a table / elements of a vector behind the call's own, which must keep their bits
-OK, E_INVALID, E_WORKSPACE = 0, -1, -4
 P = ref.P
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def dev(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def emb():
@@ -67,8 +55,8 @@ def build_plan(case, pk=None):
     nbytes = int(emb().lib().mdr_embedding_plan_bytes(cap))
     assert nbytes >= 4 * ref.plan_layout(cap)["words"]
     plan = torch.full((nbytes // 4 + GUARD,), ISENTINEL, dtype=torch.int32, device="cuda")
-    check(emb().lib().mdr_embedding_plan(_p(pk["ids"]), _p(pk["src"]), _p(pk["pid"]), _p(pk["total"]), cap, case["word"].shape[0], case["pos"].shape[0],
-                                         case["pad_row"], _p(plan), nbytes, 0, stream()))
+    check(emb().lib().mdr_embedding_plan(ptr(pk["ids"]), ptr(pk["src"]), ptr(pk["pid"]), ptr(pk["total"]), cap, case["word"].shape[0], case["pos"].shape[0],
+                                         case["pad_row"], ptr(plan), nbytes, 0, stream()))
     torch.cuda.synchronize()
     words = plan.cpu().numpy()
     assert (words[ref.plan_layout(cap)["words"]:] == ISENTINEL).all(), "the plan wrote behind its layout"
@@ -82,26 +70,16 @@ class Outs:
         H = case["word"].shape[1]
         self.shapes = {"dword": (case["word"].shape[0], H), "dpos": (case["pos"].shape[0], H), "dtype0": (H,), "dg": (H,), "db": (H,),
                        "d": (len(case["tok_src"]), H)}
-        self.buf = {}
-        for k in which:
-            n = self.shapes[k][0]
-            b = torch.full((n + GUARD,) + self.shapes[k][1:], SENTINEL, dtype=torch.float32, device="cuda")
-            if old is not None and k in old:
-                b[:n] = dev(old[k])
-            self.buf[k] = b
+        self.out = {k: Guarded(self.shapes[k][0], self.shapes[k][1:], torch.float32, 0, GUARD, (old or {}).get(k),
+                               outside=f"{k}: the guard behind the output was written") for k in which}
+        self.buf = {k: g.buf for k, g in self.out.items()}
 
     def ptr(self, k):
-        return _p(self.buf[k]) if k in self.buf else None
+        return self.out[k].ptr() if k in self.out else None
 
     def host(self):
         torch.cuda.synchronize()
-        out = {}
-        for k, b in self.buf.items():
-            a = b.cpu().numpy()
-            n = self.shapes[k][0]
-            assert (a[n:] == np.float32(SENTINEL)).all(), f"{k}: the guard behind the output was written"
-            out[k] = a[:n]
-        return out
+        return {k: g.checked() for k, g in self.out.items()}
 
 
 def run_scatter(case, d32, plan, which=("dword", "dpos", "dtype0"), old=None, accumulate=False):
@@ -110,8 +88,8 @@ def run_scatter(case, d32, plan, which=("dword", "dpos", "dtype0"), old=None, ac
     need = int(emb().lib().mdr_embedding_scatter_workspace_bytes(cap, H))
     ws = torch.empty(need, dtype=torch.uint8, device="cuda")
     td = dev(d32)
-    check(emb().lib().mdr_embedding_scatter(_p(td), _p(plan), cap, H, case["word"].shape[0], case["pos"].shape[0], o.ptr("dword"), o.ptr("dpos"), o.ptr("dtype0"),
-                                            1 if accumulate else 0, _p(ws), need, 0, stream()))
+    check(emb().lib().mdr_embedding_scatter(ptr(td), ptr(plan), cap, H, case["word"].shape[0], case["pos"].shape[0], o.ptr("dword"), o.ptr("dpos"), o.ptr("dtype0"),
+                                            1 if accumulate else 0, ptr(ws), need, 0, stream()))
     return o.host()
 
 
@@ -125,13 +103,13 @@ def run_backward(case, plan=None, which=ref.OUTPUTS, old=None, accumulate=False,
     need = int(emb().lib().mdr_embedding_backward_workspace_bytes(cap, H)) + ws_extra
     ws = torch.empty(need, dtype=torch.uint8, device="cuda")
     held = [dev(case[k]) for k in ("word", "pos", "type0", "g", "dy16", "dy2")]
-    check(emb().lib().mdr_embedding_backward(_p(pk["ids"]), _p(pk["src"]), _p(pk["pid"]), _p(pk["total"]), cap, _p(held[0]), _p(held[1]), _p(held[2]), _p(held[3]),
-                                             H, case["word"].shape[0], case["pos"].shape[0], eps, _p(held[4]), _p(held[5]),
-                                             1 if case["dy2"] is not None and case["dy2"].dtype == np.float32 else 0, _p(plan), o.ptr("dword"), o.ptr("dpos"),
-                                             o.ptr("dtype0"), o.ptr("dg"), o.ptr("db"), o.ptr("d"), 1 if accumulate else 0, _p(ws), need, 0, stream()))
+    check(emb().lib().mdr_embedding_backward(ptr(pk["ids"]), ptr(pk["src"]), ptr(pk["pid"]), ptr(pk["total"]), cap, ptr(held[0]), ptr(held[1]), ptr(held[2]), ptr(held[3]),
+                                             H, case["word"].shape[0], case["pos"].shape[0], eps, ptr(held[4]), ptr(held[5]),
+                                             1 if case["dy2"] is not None and case["dy2"].dtype == np.float32 else 0, ptr(plan), o.ptr("dword"), o.ptr("dpos"),
+                                             o.ptr("dtype0"), o.ptr("dg"), o.ptr("db"), o.ptr("d"), 1 if accumulate else 0, ptr(ws), need, 0, stream()))
     got = o.host()
     if "d" in got:
-        assert (got["d"][case["total"]:] == np.float32(SENTINEL)).all(), "d rows at or behind total were written"
+        assert_untouched(got["d"][case["total"]:], "d rows at or behind total were written")
         got["d"] = got["d"][:case["total"]]
     return got
 
@@ -168,13 +146,13 @@ def test_plan_equals_numpy_stable_argsort(kind, B, L):
 # ---- the segmented sum, exactly ------------------------------------------------------------------------------------------------------------
 def old_tables(case, seed):
     H = case["word"].shape[1]
-    return {"dword": ref.grid(case["word"].shape, seed, 4.0), "dpos": ref.grid(case["pos"].shape, seed + 1, 4.0), "dtype0": ref.grid((H,), seed + 2, 4.0)}
+    return {"dword": fp.grid(case["word"].shape, seed, 4.0), "dpos": fp.grid(case["pos"].shape, seed + 1, 4.0), "dtype0": fp.grid((H,), seed + 2, 4.0)}
 
 
 def sentinel_tables(case):
     H = case["word"].shape[1]
     return {"dword": np.full(case["word"].shape, SENTINEL, np.float32), "dpos": np.full(case["pos"].shape, SENTINEL, np.float32),
-            "dtype0": ref.grid((H,), 77, 4.0)}
+            "dtype0": fp.grid((H,), 77, 4.0)}
 
 
 def check_exact(case, d32, plan, label):
@@ -208,7 +186,7 @@ def test_scatter_on_the_grid_equals_the_integer_sums(H):
                      ("five", ref.make_flat({2: 3, 4: 2}, 8))):
         for pad_row in (1, -1):
             case = dict(pk, **tables, pad_row=pad_row)
-            d32 = ref.grid((len(pk["tok_src"]), H), 4)
+            d32 = fp.grid((len(pk["tok_src"]), H), 4)
             d32[pk["total"]:] = np.nan  # rows at or behind total are never read as values
             plan, words = build_plan(case)
             ref.assert_plan(words, case, name)
@@ -226,7 +204,7 @@ def test_scatter_rounds_on_the_grid_equal_the_integer_sums(H):
         for pad_row in (1, -1):
             case = dict(pk, **tables, pad_row=pad_row)
             assert ref.longest_summed_segments(case)[0] == max(counts.values() if name == "rounds" else [3700])
-            d32 = ref.grid((len(pk["tok_src"]), H), 14)
+            d32 = fp.grid((len(pk["tok_src"]), H), 14)
             d32[pk["total"]:] = np.nan  # rows at or behind total are never read as values
             plan, words = build_plan(case)
             ref.assert_plan(words, case, name)
@@ -255,7 +233,7 @@ def test_scatter_total_zero_and_real_table_height():
     case = dict(pk, word=np.zeros((vocab, H), np.float32), pos=np.zeros((514, H), np.float32), pad_row=1)
     plan, words = build_plan(case)
     ref.assert_plan(words, case, "real height")
-    d32 = ref.grid((cap, H), 10)
+    d32 = fp.grid((cap, H), 10)
     old = {"dword": np.full((vocab, H), SENTINEL, np.float32), "dpos": np.full((514, H), SENTINEL, np.float32)}
     got = run_scatter(case, d32, plan, which=("dword", "dpos"), old=old, accumulate=True)
     exact = ref.exact_tables(case, d32, old)
@@ -319,7 +297,7 @@ def poison(case):
 
 def old_values(case, seed):
     H = case["word"].shape[1]
-    return dict(old_tables(case, seed), dg=ref.grid((H,), seed + 3, 4.0), db=ref.grid((H,), seed + 4, 4.0))
+    return dict(old_tables(case, seed), dg=fp.grid((H,), seed + 3, 4.0), db=fp.grid((H,), seed + 4, 4.0))
 
 
 @pytest.mark.parametrize("family", ref.FAMILIES)
@@ -493,8 +471,8 @@ def test_packed_embedding_layer_norm(keep32):
     y16, y32 = out if keep32 else (out, None)
     f16 = torch.zeros((cap, H), dtype=torch.float16, device="cuda")
     f32 = torch.zeros((cap, H), dtype=torch.float32, device="cuda")
-    check(_lib.lib().mdr_test_embed_ln(0, _p(pk["ids"]), None, _p(pk["src"]), _p(pk["pid"]), _p(pk["total"]), cap, 0, _p(params[0]), _p(params[1]), _p(params[2]), 1,
-                                       _p(params[3]), _p(params[4]), H, ref.VOCAB, ref.MAX_POS, ref.EPS, _p(f16), _p(f32), 0, stream()))
+    check(_lib.lib().mdr_test_embed_ln(0, ptr(pk["ids"]), None, ptr(pk["src"]), ptr(pk["pid"]), ptr(pk["total"]), cap, 0, ptr(params[0]), ptr(params[1]), ptr(params[2]), 1,
+                                       ptr(params[3]), ptr(params[4]), H, ref.VOCAB, ref.MAX_POS, ref.EPS, ptr(f16), ptr(f32), 0, stream()))
     assert y16.dtype == torch.float16 and torch.equal(y16.detach().view(torch.int16), f16.view(torch.int16)), "forward bits differ from the encoder's"
     if keep32:
         assert torch.equal(y32.detach().view(torch.int32), f32.view(torch.int32)), "forward fp32 bits differ from the encoder's"
@@ -527,7 +505,7 @@ def test_host_validation_writes_nothing():
                                 ("misaligned plan", E_INVALID, dict(plan=plan[1:])), ("NULL plan", E_WORKSPACE, dict(plan=None)),
                                 ("short plan", E_WORKSPACE, dict(nbytes=4 * ref.plan_layout(cap)["words"] - 1))]:
         a = dict(base, **change)
-        rc = lib.mdr_embedding_plan(_p(a["ids"]), _p(a["src"]), _p(a["pid"]), _p(a["total"]), a["cap"], a["vocab"], a["max_pos"], a["pad_row"], _p(a["plan"]),
+        rc = lib.mdr_embedding_plan(ptr(a["ids"]), ptr(a["src"]), ptr(a["pid"]), ptr(a["total"]), a["cap"], a["vocab"], a["max_pos"], a["pad_row"], ptr(a["plan"]),
                                     a["nbytes"], 0, stream())
         assert rc == code and lib.mdr_last_error(), (label, rc)
     torch.cuda.synchronize()
@@ -535,7 +513,7 @@ def test_host_validation_writes_nothing():
     plan = build_plan(case, pk)[0]
 
     o = Outs(case, ref.OUTPUTS)
-    d32 = dev(ref.grid((cap, H), 1))
+    d32 = dev(fp.grid((cap, H), 1))
     sneed = int(lib.mdr_embedding_scatter_workspace_bytes(cap, H))
     bneed = int(lib.mdr_embedding_backward_workspace_bytes(cap, H))
     ws = torch.full((bneed,), 0x5A, dtype=torch.uint8, device="cuda")
@@ -548,8 +526,8 @@ def test_host_validation_writes_nothing():
                                 ("misaligned dword", E_INVALID, dict(dword=o.buf["dword"].reshape(-1)[1:])), ("misaligned d32", E_INVALID, dict(d32=d32.reshape(-1)[1:])),
                                 ("short workspace", E_WORKSPACE, dict(nbytes=ref.chunks(cap, H)[0] * H * 4 - 1)), ("NULL workspace", E_WORKSPACE, dict(ws=None))]:
         a = dict(sbase, **change)
-        rc = lib.mdr_embedding_scatter(_p(a["d32"]), _p(a["plan"]), a["cap"], a["H"], a["vocab"], a["max_pos"], _p(a["dword"]), _p(a["dpos"]), _p(a["dtype0"]),
-                                       a["accumulate"], _p(a["ws"]), a["nbytes"], 0, stream())
+        rc = lib.mdr_embedding_scatter(ptr(a["d32"]), ptr(a["plan"]), a["cap"], a["H"], a["vocab"], a["max_pos"], ptr(a["dword"]), ptr(a["dpos"]), ptr(a["dtype0"]),
+                                       a["accumulate"], ptr(a["ws"]), a["nbytes"], 0, stream())
         assert rc == code and lib.mdr_last_error(), (label, rc)
 
     held = {k: dev(case[k]) for k in ("word", "pos", "type0", "g", "dy16", "dy2")}
@@ -565,9 +543,9 @@ def test_host_validation_writes_nothing():
                                 ("misaligned dg", E_INVALID, dict(dg=o.buf["dg"][1:])), ("misaligned dy16", E_INVALID, dict(dy16=held["dy16"].reshape(-1)[1:])),
                                 ("short workspace", E_WORKSPACE, dict(nbytes=cap * H * 4)), ("NULL workspace", E_WORKSPACE, dict(ws=None))]:
         a = dict(bbase, **change)
-        rc = lib.mdr_embedding_backward(_p(a["ids"]), _p(a["src"]), _p(a["pid"]), _p(a["total"]), a["cap"], _p(a["word"]), _p(a["pos"]), _p(a["type0"]), _p(a["g"]),
-                                        a["H"], a["vocab"], a["max_pos"], ref.EPS, _p(a["dy16"]), _p(a["dy2"]), a["dy2_f32"], _p(a["plan"]), _p(a["dword"]),
-                                        _p(a["dpos"]), _p(a["dtype0"]), _p(a["dg"]), _p(a["db"]), _p(a["d"]), a["accumulate"], _p(a["ws"]), a["nbytes"], 0, stream())
+        rc = lib.mdr_embedding_backward(ptr(a["ids"]), ptr(a["src"]), ptr(a["pid"]), ptr(a["total"]), a["cap"], ptr(a["word"]), ptr(a["pos"]), ptr(a["type0"]), ptr(a["g"]),
+                                        a["H"], a["vocab"], a["max_pos"], ref.EPS, ptr(a["dy16"]), ptr(a["dy2"]), a["dy2_f32"], ptr(a["plan"]), ptr(a["dword"]),
+                                        ptr(a["dpos"]), ptr(a["dtype0"]), ptr(a["dg"]), ptr(a["db"]), ptr(a["d"]), a["accumulate"], ptr(a["ws"]), a["nbytes"], 0, stream())
         assert rc == code and lib.mdr_last_error(), (label, rc)
     torch.cuda.synchronize()
     assert all((b == SENTINEL).all() for b in o.buf.values()) and (ws == 0x5A).all(), "a rejected call wrote something"

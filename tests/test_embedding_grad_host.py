@@ -10,14 +10,15 @@ import torch
 
 import embedding_grad_ref as ref
 import layernorm_grad_ref as lref
+from oracle import fp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def old_values(case, seed):
     H = case["word"].shape[1]
-    return {"dword": ref.grid(case["word"].shape, seed, 4.0), "dpos": ref.grid(case["pos"].shape, seed + 1, 4.0), "dtype0": ref.grid((H,), seed + 2, 4.0),
-            "dg": ref.grid((H,), seed + 3, 4.0), "db": ref.grid((H,), seed + 4, 4.0)}
+    return {"dword": fp.grid(case["word"].shape, seed, 4.0), "dpos": fp.grid(case["pos"].shape, seed + 1, 4.0), "dtype0": fp.grid((H,), seed + 2, 4.0),
+            "dg": fp.grid((H,), seed + 3, 4.0), "db": fp.grid((H,), seed + 4, 4.0)}
 
 
 @pytest.mark.parametrize("kind", ["random", "range"])
@@ -111,7 +112,7 @@ def test_emulated_scatter_on_the_grid_is_exact():
     P = ref.P
     pk = ref.make_flat({3: 1, 5: P - 1, 7: P, 9: P + 1, 11: 2 * P + 1, 1: 4}, 7)
     case = dict(pk, **ref.make_tables("unit", 64, 7), pad_row=1)
-    d32 = ref.grid((len(pk["tok_src"]), 64), 8)
+    d32 = fp.grid((len(pk["tok_src"]), 64), 8)
     wid, prow = ref.rows(case)
     exact = ref.exact_tables(case, d32)
     assert np.array_equal(ref.emulate_scatter(d32, wid, ref.VOCAB, 1), exact["dword"])
@@ -120,7 +121,7 @@ def test_emulated_scatter_on_the_grid_is_exact():
     # and over several rounds of eight pieces (the GPU test's "rounds" case)
     pk = ref.make_flat({3: 8 * P, 5: 8 * P + 1, 7: 16 * P - 1, 9: 16 * P + 1, 11: 40 * P + 5, 1: 4, 0: 2}, 15)
     case = dict(pk, **ref.make_tables("unit", 64, 7), pad_row=-1)
-    d32 = ref.grid((len(pk["tok_src"]), 64), 14)
+    d32 = fp.grid((len(pk["tok_src"]), 64), 14)
     wid, prow = ref.rows(case)
     exact = ref.exact_tables(case, d32)
     assert np.array_equal(ref.emulate_scatter(d32, wid, ref.VOCAB, -1), exact["dword"]) and np.array_equal(ref.emulate_scatter(d32, prow, ref.MAX_POS, -1), exact["dpos"])

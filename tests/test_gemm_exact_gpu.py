@@ -22,23 +22,17 @@ import pytest
 import torch
 
 import gemm_ref as ref
+from guarded import E_INVALID, E_STATE, OK, SENTINEL, Guarded, dev
+from multihop_dense_retrieval_amd._lib import ptr
+from oracle import fp
+from oracle.fp import bits
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 777.0  # finite, fp16-exact, far from every expected output
 GUARD = 64        # rows in front of and behind the call's own
-OK, E_INVALID, E_STATE = 0, -1, -5
 ONE_TILE = ("small", "mid")
 KERNEL_OF = {"small": 1, "mid": 2, "persist": 4, "big": 6, "quad": 7}
 ALL_NK = [pytest.param(N, K, id=f"N{N}-K{K}") for N, K in ref.SMALL_NK]
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def dev(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def num_cus():
@@ -47,7 +41,7 @@ def num_cus():
 
 def raw_call(x, w, b, res, M, M_est, m_dev, N, K, out, epilogue, kernel, flag):
     from multihop_dense_retrieval_amd import _lib
-    return _lib.lib().mdr_test_gemm_ex(_p(x), _p(w), _p(b), _p(res), M, M_est, _p(m_dev), N, K, _p(out), epilogue, kernel, flag, 0, _lib.current_stream_ptr())
+    return _lib.lib().mdr_test_gemm_ex(ptr(x), ptr(w), ptr(b), ptr(res), M, M_est, ptr(m_dev), N, K, ptr(out), epilogue, kernel, flag, 0, _lib.current_stream_ptr())
 
 
 def run_dev(tx, tw, tb, epilogue, kernel, tres=None, m=None, M_est=None):
@@ -56,26 +50,20 @@ def run_dev(tx, tw, tb, epilogue, kernel, tres=None, m=None, M_est=None):
     from multihop_dense_retrieval_amd import _lib
     M, K = tx.shape
     N = tw.shape[0]
-    buf = torch.full((GUARD + M + GUARD, N), SENTINEL, dtype=torch.float16 if epilogue in (0, 1) else torch.float32, device="cuda")
+    out = Guarded(M, (N,), torch.float16 if epilogue in (0, 1) else torch.float32, GUARD, GUARD)
     m_dev = None if m is None else torch.tensor([m], dtype=torch.int32, device="cuda")
     flag = ctypes.c_int(-1)
-    _lib.check(raw_call(tx, tw, tb, tres, M, M if M_est is None else M_est, m_dev, N, K, buf[GUARD:GUARD + M], epilogue, kernel, ctypes.byref(flag)))
+    _lib.check(raw_call(tx, tw, tb, tres, M, M if M_est is None else M_est, m_dev, N, K, out.own, epilogue, kernel, ctypes.byref(flag)))
     torch.cuda.synchronize()
     assert flag.value in (0, 1)
-    mm = M if m is None else m
-    assert bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[GUARD + M:] == SENTINEL).all()), "rows outside the call were written"
-    assert bool((buf[GUARD + mm:GUARD + M] == SENTINEL).all()), "rows at or behind the valid count were written"
-    return buf, bool(flag.value)
+    out.checked(out.buf, valid=M if m is None else m)  # (on the device: the callers bring to the host what they compare)
+    return out.buf, bool(flag.value)
 
 
 def run(x, w, b, epilogue, kernel, res=None, m=None, M_est=None):
     """One call on numpy inputs -> (numpy [M, N], rows at or behind m still SENTINEL; res_added)."""
     buf, added = run_dev(dev(x), dev(w), dev(b), epilogue, kernel, dev(res) if epilogue == 2 else None, m, M_est)
     return buf[GUARD:GUARD + x.shape[0]].cpu().numpy(), added
-
-
-def bits(a):
-    return a.view(np.uint16 if a.dtype == np.float16 else np.uint32)
 
 
 def assert_equal(got, want, label):
@@ -87,20 +75,17 @@ def assert_equal(got, want, label):
 
 
 def check_bound(got, r, bnd, label, worst_of=None):
-    worst, at = ref.worst_ratio(got, r, bnd)
+    worst = fp.assert_within(got, r, bnd, label)
     if worst_of is not None:
         worst_of[0] = max(worst_of[0], worst)
-    if worst > 1.0:
-        g2, r2, b2 = (np.atleast_2d(a) for a in (got, r, bnd))
-        pytest.fail(f"{label}: outside the bound: worst {worst:.3f} at row {at[0]}, column {at[1]}: got {float(g2[at])!r}, reference {r2[at]!r}, bound {b2[at]:.3e}")
     return worst
 
 
 def grid_case(M, N, K, seed, positive=False):
-    x, w = ref.grid((M, K), seed), ref.grid((N, K), seed + 1)
+    x, w = fp.grid((M, K), seed, dtype=np.float16), fp.grid((N, K), seed + 1, dtype=np.float16)
     if positive:  # sums of a few hundred: most values are rounded by the fp16 conversion, some from just beside a tie
         x, w = np.abs(x), np.abs(w)
-    return x, w, ref.grid_bias(N, seed + 2), ref.grid((M, N), seed + 3)
+    return x, w, ref.grid_bias(N, seed + 2), fp.grid((M, N), seed + 3, dtype=np.float16)
 
 
 def expected_grid(x, w, b, res, epilogue, res_added):
@@ -198,7 +183,7 @@ def exact_dev(tx, tw, tb):
     assert tx.shape[1] <= 4096 and float(tx.abs().max()) <= 2 and float(tw.abs().max()) <= 2
     z = tx.double() @ tw.double().T + tb.double()
     total = tx.abs().double() @ tw.abs().double().T + tb.abs().double()
-    assert float(total.max()) * 64 <= 2.0 ** 24 and bool((z.float().double() == z).all()) and float(z.abs().max()) < ref.F16_MAX
+    assert float(total.max()) * 64 <= 2.0 ** 24 and bool((z.float().double() == z).all()) and float(z.abs().max()) < fp.F16_MAX
     return z
 
 
@@ -261,8 +246,8 @@ def test_gelu_ladder(kernel):
     near = ~far
     un, emu = u[near].astype(np.float64), ref.gelu32(u[near])
     g = np.abs(ref.gelu64(un))
-    d = np.abs(un) * (ref.X1ULP * 0.5 * torch.special.erfc(torch.from_numpy(np.abs(un) / np.sqrt(2.0))).numpy() + ref.U32) + ref.U32 * g
-    tol = d + 2 * ref._r16(g + ref.gelu_err32(un) + d)
+    d = np.abs(un) * (fp.X1ULP * 0.5 * torch.special.erfc(torch.from_numpy(np.abs(un) / np.sqrt(2.0))).numpy() + fp.U32) + fp.U32 * g
+    tol = d + 2 * fp.r16(g + ref.gelu_err32(un) + d)
     diff = np.abs(got[near].astype(np.float64) - emu.astype(np.float16).astype(np.float64))
     print(f"kernel {kernel}: {int((diff != 0).sum())} of {diff.size} outputs at |u| <= 16 differ from the emulation's fp16, worst |diff| / tolerance {float((diff / tol).max()):.4f}")
     assert (diff <= tol).all()

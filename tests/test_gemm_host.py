@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import gemm_ref as ref
+from oracle import fp
 
 
 def gelu_inputs():
@@ -72,7 +73,7 @@ def test_torch_bound_is_the_numpy_bound():
 
 
 def grid_case(M, N, K, seed):
-    return ref.grid((M, K), seed), ref.grid((N, K), seed + 1), ref.grid_bias(N, seed + 2), ref.grid((M, N), seed + 3)
+    return fp.grid((M, K), seed, dtype=np.float16), fp.grid((N, K), seed + 1, dtype=np.float16), ref.grid_bias(N, seed + 2), fp.grid((M, N), seed + 3, dtype=np.float16)
 
 
 def expected_grid(x, w, b, res, epilogue, res_added=True):
@@ -93,14 +94,14 @@ def test_emulation_equals_the_grid_and_stays_inside_the_bound(N, K):
                 want = expected_grid(x, w, b, res, epi, added)
                 assert got.dtype == want.dtype and np.array_equal(got, want), (M, epi, added)
         u = ref.exact(x, w, b)
-        worst, at = ref.worst_ratio(ref.emulate(x, w, b, 1), ref.gelu64(u), ref.gelu_bound(u))
+        worst, at = fp.worst_ratio(ref.emulate(x, w, b, 1), ref.gelu64(u), ref.gelu_bound(u))
         assert worst <= 1.0, ("grid gelu", M, worst, at)
         x, w, _ = ref.realistic(M, N, K, 11)
         b, res = ref.bias(N, 11), ref.realistic(M, 64, N, 12)[0]
         for epi in (0, 1, 2, 3):
             for added in ((True, False) if epi == 2 else (True,)):
                 r, bnd = ref.reference_and_bound(x, w, b, epi, res, added)
-                worst, at = ref.worst_ratio(ref.emulate(x, w, b, epi, res, added), r, bnd)
+                worst, at = fp.worst_ratio(ref.emulate(x, w, b, epi, res, added), r, bnd)
                 assert worst <= 1.0, ("realistic", M, epi, added, worst, at)
 
 

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import fp
+
 pytestmark = pytest.mark.gpu
 
 F32, O1 = 0, 1
@@ -136,7 +138,7 @@ def test_realistic_rows_mode_f32():
         if h == 0:
             keep[np.arange(B), B + np.arange(B)] = False
         st = s[np.arange(B), t][:, None]
-        m = 2 * 768 * 2.0 ** -24 * (ab + ab[np.arange(B), t][:, None])
+        m = 2 * 768 * fp.U32 * (ab + ab[np.arange(B), t][:, None])
         lo = 1 + ((s > st + m) & keep).sum(1)
         hi = ((s >= st - m) & keep).sum(1)
         decided = (lo == hi).mean()
@@ -144,7 +146,7 @@ def test_realistic_rows_mode_f32():
         assert decided >= 0.95
         assert ((got[name] >= lo) & (got[name] <= hi)).all(), np.nonzero((got[name] < lo) | (got[name] > hi))[0][:10]
         ts = got["tscore1" if h == 0 else "tscore2"].astype(np.float64)
-        assert (np.abs(ts - st[:, 0]) <= 768 * 2.0 ** -24 * ab[np.arange(B), t]).all()
+        assert (np.abs(ts - st[:, 0]) <= 768 * fp.U32 * ab[np.arange(B), t]).all()
 
 
 @pytest.mark.parametrize("mode", [F32, O1])

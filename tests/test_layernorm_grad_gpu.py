@@ -16,20 +16,20 @@ of a workgroup and one and two chunks, 300, and for H = 64 two M found by callin
 and number >= 3; and layernorm_grad_ref.LARGE_HM, the shipping widths at the smallest training row counts at which a wave walks three rows
 with dg and db in registers, the last chunk is ragged and a strand of the reduction adds more than sixteen chunks.
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import layernorm_grad_ref as ref
+from guarded import E_INVALID, E_WORKSPACE, SENTINEL, Guarded, dev
+from multihop_dense_retrieval_amd._lib import ptr
+from oracle import fp
 from oracle import trunk_rows_oracle as tr
+from oracle.fp import bits
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 777.0  # finite, fp16-exact, far from every expected output
 GUARD = 64        # rows of dx / elements of dg and db in front of and behind the call's own, which must keep their bits
-OK, E_INVALID, E_WORKSPACE = 0, -1, -4
 
 
 def ms_for(H):
@@ -40,22 +40,10 @@ def combos_for(M):
     return ref.COMBOS if M in (5, 300) else ref.TRUNK_COMBOS
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def dev(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint16 if a.dtype == np.float16 else np.uint32)
-
-
 def raw_call(inp, in_f16, res16, res32, dy16, dy2, dy2_f32, M, m_dev, H, g, eps, dx16, dx32, dg, db, accumulate, ws, ws_bytes):
     from multihop_dense_retrieval_amd import _lib, layernorm
-    return layernorm.lib().mdr_layernorm_backward(_p(inp), in_f16, _p(res16), _p(res32), _p(dy16), _p(dy2), dy2_f32, M, _p(m_dev), H, _p(g), eps,
-                                                  _p(dx16), _p(dx32), _p(dg), _p(db), accumulate, _p(ws), ws_bytes, 0, _lib.current_stream_ptr())
+    return layernorm.lib().mdr_layernorm_backward(ptr(inp), in_f16, ptr(res16), ptr(res32), ptr(dy16), ptr(dy2), dy2_f32, M, ptr(m_dev), H, ptr(g), eps,
+                                                  ptr(dx16), ptr(dx32), ptr(dg), ptr(db), accumulate, ptr(ws), ws_bytes, 0, _lib.current_stream_ptr())
 
 
 def run(inp, res, dy16, dy2, g, eps=ref.EPS, m=None, outs="xXgb", old_dg=None, old_db=None, accumulate=False, ws_extra=0):
@@ -64,14 +52,9 @@ def run(inp, res, dy16, dy2, g, eps=ref.EPS, m=None, outs="xXgb", old_dg=None, o
     asserting MDR_OK, that the guards and the rows at or behind m kept their bits and that an output not asked for was not written."""
     from multihop_dense_retrieval_amd import _lib, layernorm
     M, H = inp.shape
-    b16 = torch.full((GUARD + M + GUARD, H), SENTINEL, dtype=torch.float16, device="cuda")
-    b32 = torch.full((GUARD + M + GUARD, H), SENTINEL, dtype=torch.float32, device="cuda")
-    bg = torch.full((GUARD + H + GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
-    bb = torch.full((GUARD + H + GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
-    if old_dg is not None:
-        bg[GUARD:GUARD + H] = dev(old_dg.astype(np.float32))
-    if old_db is not None:
-        bb[GUARD:GUARD + H] = dev(old_db.astype(np.float32))
+    b16, b32 = (Guarded(M, (H,), t, GUARD, GUARD, name=name) for t, name in ((torch.float16, "dx16"), (torch.float32, "dx32")))
+    bg, bb = (Guarded(H, (), torch.float32, GUARD, GUARD, None if old is None else old.astype(np.float32), name, "elements")
+              for old, name in ((old_dg, "dg"), (old_db, "db")))
     want = (1 if "g" in outs else 0) | (2 if "b" in outs else 0)
     need = int(layernorm.lib().mdr_layernorm_backward_workspace_bytes(M, H, want))
     ws = torch.empty(max(need + ws_extra, 16), dtype=torch.uint8, device="cuda")
@@ -80,25 +63,12 @@ def run(inp, res, dy16, dy2, g, eps=ref.EPS, m=None, outs="xXgb", old_dg=None, o
     res32 = res if res is not None and res.dtype == np.float32 else None
     held = [dev(a) for a in (inp, res16, res32, dy16, dy2, g)]  # (held until the synchronise below)
     _lib.check(raw_call(held[0], 1 if inp.dtype == np.float16 else 0, held[1], held[2], held[3], held[4], 1 if dy2 is not None and dy2.dtype == np.float32 else 0,
-                        M, m_dev, H, held[5], eps, b16[GUARD:GUARD + M] if "x" in outs else None, b32[GUARD:GUARD + M] if "X" in outs else None,
-                        bg[GUARD:GUARD + H] if "g" in outs else None, bb[GUARD:GUARD + H] if "b" in outs else None, 1 if accumulate else 0, ws,
-                        need + ws_extra))
+                        M, m_dev, H, held[5], eps, b16.own if "x" in outs else None, b32.own if "X" in outs else None,
+                        bg.own if "g" in outs else None, bb.own if "b" in outs else None, 1 if accumulate else 0, ws, need + ws_extra))
     torch.cuda.synchronize()
-    g16, g32, gg, gb = b16.cpu().numpy(), b32.cpu().numpy(), bg.cpu().numpy(), bb.cpu().numpy()
     mm = M if m is None else min(max(m, 0), M)
-    for name, buf, key in (("dx16", g16, "x"), ("dx32", g32, "X")):
-        s = buf.dtype.type(SENTINEL)
-        assert (buf[:GUARD] == s).all() and (buf[GUARD + M:] == s).all(), f"{name} rows outside the call were written"
-        if key in outs:
-            assert (buf[GUARD + mm:GUARD + M] == s).all(), f"{name} rows at or behind the valid count were written"
-        else:
-            assert (buf == s).all(), f"{name} written though not asked for"
-    for name, buf, key, old in (("dg", gg, "g", old_dg), ("db", gb, "b", old_db)):
-        s = np.float32(SENTINEL)
-        assert (buf[:GUARD] == s).all() and (buf[GUARD + H:] == s).all(), f"{name} elements outside the call were written"
-        if key not in outs and old is None:
-            assert (buf == s).all(), f"{name} written though not asked for"
-    return {"dx16": g16[GUARD:GUARD + M], "dx32": g32[GUARD:GUARD + M], "dg": gg[GUARD:GUARD + H], "db": gb[GUARD:GUARD + H]}
+    return {"dx16": b16.checked(valid=mm, asked="x" in outs), "dx32": b32.checked(valid=mm, asked="X" in outs),
+            "dg": bg.checked(asked="g" in outs), "db": bb.checked(asked="b" in outs)}
 
 
 def check_bound(got, rb, m, label):
@@ -106,16 +76,9 @@ def check_bound(got, rb, m, label):
     r, bnd = rb["dx"]
     odd = tr.assert_f16(got["dx16"][:m], r, bnd, label + " dx16")
     shares = {"dx32": tr.assert_f32(got["dx32"][:m], r, bnd, label + " dx32")}
-    fails = []
     for name in ("dg", "db"):
-        worst, at = ref.worst_ratio(got[name], *rb[name])
-        shares[name] = worst
-        if worst > 1.0:
-            fails.append(f"{name} outside the bound: worst {worst:.3f} at column {at[1]}: got {float(got[name][at[1]])!r}, reference {rb[name][0][at[1]]!r}, "
-                         f"bound {rb[name][1][at[1]]:.3e}")
+        shares[name] = fp.assert_within(got[name], *rb[name], f"{label}: {name}")
     print(f"SHARE {label} " + " ".join(f"{k}={v:.4f}" for k, v in shares.items()) + f" dx16_not_rne={odd}")
-    if fails:
-        pytest.fail(f"{label}: " + "; ".join(fails))
     return shares
 
 
@@ -166,7 +129,7 @@ def test_families_within_the_derived_bound(H, family):
                 label = f"family={family} H={H} M={M} combo={'-'.join(map(str, combo))} scale={scale:g}"
                 sh = check_bound(run(**case), ref.reference_and_bound(**case), M, label)
                 if M == 300:
-                    old_dg, old_db = ref.grid((H,), 12, 4.0), ref.grid((H,), 13, 4.0)
+                    old_dg, old_db = fp.grid((H,), 12, 4.0), fp.grid((H,), 13, 4.0)
                     got = run(**case, m=M - 1, old_dg=old_dg, old_db=old_db, accumulate=True)
                     check_bound(got, ref.reference_and_bound(**case, m=M - 1, old_dg=old_dg, old_db=old_db), M - 1, label + " m=M-1 accumulate")
                 for k, v in sh.items():
@@ -178,9 +141,9 @@ def grid_case(M, H, seed, combo=ref.TRUNK_COMBOS[0]):
     """a realistic x with dy16 and dy2 on the grid of multiples of 1/8"""
     case = ref.make_case("unit", combo, M, H, seed)
     if case["dy16"] is not None:
-        case["dy16"] = ref.grid((M, H), seed + 1).astype(np.float16)
+        case["dy16"] = fp.grid((M, H), seed + 1).astype(np.float16)
     if case["dy2"] is not None:
-        case["dy2"] = ref.grid((M, H), seed + 2).astype(case["dy2"].dtype)
+        case["dy2"] = fp.grid((M, H), seed + 2).astype(case["dy2"].dtype)
     return case
 
 
@@ -194,7 +157,7 @@ def exact_db(case, m, old=None):
 @pytest.mark.parametrize("H", ref.HS)
 def test_db_on_the_grid_equals_the_integer_column_sums(H):
     """every shape, row count and S, with accumulate too: the chunk seams, the ragged last chunk, the wave order and the reduction without a tolerance"""
-    old = ref.grid((H,), 5, 4.0)
+    old = fp.grid((H,), 5, 4.0)
     for M in ms_for(H):
         for combo in ref.TRUNK_COMBOS[:2] + ref.OTHER_COMBOS[:2]:
             case = grid_case(M, H, 3, combo)
@@ -212,7 +175,7 @@ def test_db_on_the_grid_equals_the_integer_column_sums(H):
 def test_db_on_the_grid_equals_the_integer_column_sums_at_training_row_counts(H, M):
     """test_db_on_the_grid_equals_the_integer_column_sums at LARGE_HM: the row walk of a wave, 342 to 684 chunks through the sixteen strands and
     the ragged last chunk without a tolerance; valid-row counts inside a chunk with hundreds of whole chunks, and with one, behind them"""
-    old = ref.grid((H,), 5, 4.0)
+    old = fp.grid((H,), 5, 4.0)
     for combo in ref.TRUNK_COMBOS[:2]:
         case = grid_case(M, H, 3, combo)
         for m in (None,) + ref.large_ms(M, H)[:3]:
@@ -225,7 +188,7 @@ def test_db_on_the_grid_equals_the_integer_column_sums_at_training_row_counts(H,
 
 @pytest.mark.parametrize("H", ref.HS)
 def test_zero_dy_and_zero_gamma_give_exact_zeros(H):
-    old_dg, old_db = ref.grid((H,), 6, 4.0) + 0.125, ref.grid((H,), 7, 4.0) + 0.125  # (no zero among them: an old -0 would not keep its sign)
+    old_dg, old_db = fp.grid((H,), 6, 4.0) + 0.125, fp.grid((H,), 7, 4.0) + 0.125  # (no zero among them: an old -0 would not keep its sign)
     for M in (1, 5, 300) + (tuple(ref.split_ms(H)[:1]) if H == 64 else ()):
         for combo in ref.TRUNK_COMBOS:
             case = ref.make_case("unit", combo, M, H, 41)
@@ -260,7 +223,7 @@ def test_rows_behind_m_dev_do_not_exist(H, M, combo):
     it), rows at or behind m NaN and Inf in every input: the results are those of the call on the first m rows alone, bit for bit (the two calls cut the rows alike wherever rows_per_chunk agrees, and the chunks behind m add +0); m = 0 gives zeros, or the old
     bits with accumulate; m = M + 7 is clamped to M. dx rows at or behind m keep the sentinel (run() asserts it)."""
     case = ref.make_case("unit", combo, M, H, 17)
-    old_dg, old_db = ref.grid((H,), 18, 4.0) + 0.125, ref.grid((H,), 19, 4.0) + 0.125
+    old_dg, old_db = fp.grid((H,), 18, 4.0) + 0.125, fp.grid((H,), 19, 4.0) + 0.125
     full = run(**case)
     over = run(**case, m=M + 7)
     for k in full:
@@ -280,7 +243,7 @@ def test_rows_behind_m_dev_do_not_exist(H, M, combo):
             assert np.array_equal(bits(got["dg"]), bits(alone["dg"])) and np.array_equal(bits(got["db"]), bits(alone["db"])), m
         else:  # another cut, another summation order: the same sums inside the bound
             rb = ref.reference_and_bound(**case, m=m)
-            assert ref.worst_ratio(got["dg"], *rb["dg"])[0] <= 1.0 and ref.worst_ratio(got["db"], *rb["db"])[0] <= 1.0, m
+            assert fp.worst_ratio(got["dg"], *rb["dg"])[0] <= 1.0 and fp.worst_ratio(got["db"], *rb["db"])[0] <= 1.0, m
     assert ref.chunks(1, H)[1] == ref.chunks(M, H)[1] or M > 4096  # the small shapes compare dg and db bit for bit at every m
 
 
@@ -385,8 +348,8 @@ def forward_hook(inp, res, g, b, eps, m, want32):
     o32 = torch.zeros((M, H), dtype=torch.float32, device="cuda") if want32 else None
     m_dev = None if m is None else torch.tensor([m], dtype=torch.int32, device="cuda")
     held = [dev(a) for a in (inp, res if res is not None and res.dtype == np.float16 else None, res if res is not None and res.dtype == np.float32 else None, g, b)]
-    _lib.check(_lib.lib().mdr_test_layernorm(_p(held[0]), 1 if inp.dtype == np.float16 else 0, _p(held[1]), _p(held[2]), M, _p(m_dev), H, _p(held[3]), _p(held[4]),
-                                             eps, _p(o16), _p(o32), 0, _lib.current_stream_ptr()))
+    _lib.check(_lib.lib().mdr_test_layernorm(ptr(held[0]), 1 if inp.dtype == np.float16 else 0, ptr(held[1]), ptr(held[2]), M, ptr(m_dev), H, ptr(held[3]), ptr(held[4]),
+                                             eps, ptr(o16), ptr(o32), 0, _lib.current_stream_ptr()))
     torch.cuda.synchronize()
     return o16.cpu().numpy(), None if o32 is None else o32.cpu().numpy()
 
@@ -431,7 +394,7 @@ def test_packed_layer_norm(combo, keep32, rows):
             print(f"SHARE {label} d{name}={tr.assert_f32(got[:mm], *rb['dx'], f'{label} d{name}'):.4f}")
     assert tw.grad.dtype == torch.float32 and tb.grad.dtype == torch.float32 and tuple(tw.grad.shape) == (H,) and tuple(tb.grad.shape) == (H,)
     for name, t in (("dg", tw), ("db", tb)):
-        worst, at = ref.worst_ratio(t.grad.cpu().numpy(), *rb[name])
+        worst, at = fp.worst_ratio(t.grad.cpu().numpy(), *rb[name])
         print(f"SHARE {label} {name}={worst:.4f}")
         assert worst <= 1.0, (label, name, worst, at)
 
@@ -439,7 +402,7 @@ def test_packed_layer_norm(combo, keep32, rows):
 # ---- the CLS gather's backward --------------------------------------------------------------------------------------------------------------
 def cls_call(d, cu, B, H, acc):
     from multihop_dense_retrieval_amd import _lib, layernorm
-    return layernorm.lib().mdr_gather_cls_backward(_p(d), _p(cu), B, H, _p(acc), 0, _lib.current_stream_ptr())
+    return layernorm.lib().mdr_gather_cls_backward(ptr(d), ptr(cu), B, H, ptr(acc), 0, _lib.current_stream_ptr())
 
 
 @pytest.mark.parametrize("H", [64, 192, 768, 1024])
@@ -452,8 +415,8 @@ def test_gather_cls_backward_on_the_grid(lens, H):
     B, cu = len(lens), np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
     T = int(cu[-1])
     acc0 = np.full((GUARD + T + GUARD, H), SENTINEL, np.float16)
-    acc0[GUARD:GUARD + T] = ref.grid((T, H), 51).astype(np.float16)
-    d = ref.grid((B, H), 52).astype(np.float16)
+    acc0[GUARD:GUARD + T] = fp.grid((T, H), 51).astype(np.float16)
+    d = fp.grid((B, H), 52).astype(np.float16)
     want = acc0.copy()
     for b in range(B):
         if lens[b] > 0:
@@ -474,7 +437,7 @@ def test_gather_cls_backward_host_validation_writes_nothing():
     lib = layernorm.lib()
     B, H = 3, 128
     cu = dev(np.asarray([0, 2, 4, 6], np.int32))
-    d = dev(ref.grid((B, H), 53).astype(np.float16))
+    d = dev(fp.grid((B, H), 53).astype(np.float16))
     acc = torch.full((6, H), SENTINEL, dtype=torch.float16, device="cuda")
     for label, change in (("NULL d", dict(d=None)), ("NULL cu", dict(cu=None)), ("NULL acc", dict(acc=None)), ("B = 0", dict(B=0)), ("B < 0", dict(B=-1)),
                           ("H = 96", dict(H=96)), ("H = 0", dict(H=0)), ("H = 1088", dict(H=1088)), ("misaligned acc", dict(acc=acc.reshape(-1)[1:])),

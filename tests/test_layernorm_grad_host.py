@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import layernorm_grad_ref as ref
+from oracle import fp
 from oracle import trunk_rows_oracle as tr
 
 OUTPUTS = ("dx", "dg", "db")
@@ -17,13 +18,13 @@ def _ratios(emu, rb):
     their largest share of the bound"""
     dx16, dx32, dg, db = emu
     tr.assert_f16(dx16, *rb["dx"], "dx16")
-    return {k: ref.worst_ratio(got, *rb[k]) for k, got in zip(OUTPUTS, (dx32, dg, db))}
+    return {k: fp.worst_ratio(got, *rb[k]) for k, got in zip(OUTPUTS, (dx32, dg, db))}
 
 
 def _outside(emu, rb):
     """whether any output leaves the bound (dx16 by the monotonic rule)"""
     dx16, dx32, dg, db = emu
-    if max(ref.worst_ratio(got, *rb[k])[0] for k, got in zip(OUTPUTS, (dx32, dg, db))) > 1.0:
+    if max(fp.worst_ratio(got, *rb[k])[0] for k, got in zip(OUTPUTS, (dx32, dg, db))) > 1.0:
         return True
     try:
         tr.assert_f16(dx16, *rb["dx"], "dx16")
@@ -68,7 +69,7 @@ def test_stats_restate_the_forward_derivation():
         x, ex = tr.ln_inputs(case["inp"], case["res"])
         st = ref.stats(x, ex, ref.EPS)
         t, Et = np.abs(st["t"]), st["Et"]
-        mine = (Et + tr.U * (t + Et) + tr.U * (t + Et)) * (1 + 2.0 ** -10)
+        mine = (Et + fp.U32 * (t + Et) + fp.U32 * (t + Et)) * (1 + 2.0 ** -10)
         theirs = tr.bound(x, ex, np.ones(192), np.zeros(192), ref.EPS)
         assert np.allclose(mine, theirs, rtol=1e-12, atol=0), family
         assert np.allclose(st["t"], tr.layer_norm(x, np.ones(192), np.zeros(192), ref.EPS), rtol=1e-12, atol=1e-300), family
@@ -88,7 +89,7 @@ def test_emulation_stays_inside_the_bound(H, family):
         for combo in (ref.COMBOS if M in (5, 300) else ref.TRUNK_COMBOS):
             for scale in _scales(family):
                 case = ref.make_case(family, combo, M, H, 11, scale)
-                old_dg, old_db = ref.grid((H,), 12, 4.0), ref.grid((H,), 13, 4.0)
+                old_dg, old_db = fp.grid((H,), 12, 4.0), fp.grid((H,), 13, 4.0)
                 for m, odg, odb in ((None, None, None), (max(M - 1, 0), old_dg, old_db)):
                     rb = ref.reference_and_bound(**case, m=m, old_dg=odg, old_db=odb)
                     for k, (w, at) in _ratios(ref.emulate(**case, m=m, old_dg=odg, old_db=odb), rb).items():
@@ -104,7 +105,7 @@ def test_emulation_stays_inside_the_bound_at_training_row_counts(H, M, family):
     with a valid-row count in the middle and old values; the unit family under the loss scale, as in training. One fp64 reference per
     combination keeps a case at a few seconds."""
     worst = dict.fromkeys(OUTPUTS, 0.0)
-    old_dg, old_db = ref.grid((H,), 12, 4.0), ref.grid((H,), 13, 4.0)
+    old_dg, old_db = fp.grid((H,), 12, 4.0), fp.grid((H,), 13, 4.0)
     for combo, (m, odg, odb) in zip(ref.TRUNK_COMBOS, ((None, None, None), (None, None, None), (ref.large_ms(M, H)[1], old_dg, old_db))):
         case = ref.make_case(family, combo, M, H, 11, 256.0 if family == "unit" else 1.0)
         rb = ref.reference_and_bound(**case, m=m, old_dg=odg, old_db=odb)
@@ -122,12 +123,12 @@ def test_each_mutation_leaves_the_bound(mutation):
     assert S > 1
     family = "const" if mutation == "no_eps" else "unit"
     case = ref.make_case(family, ref.TRUNK_COMBOS[0], M, H, 21)
-    old_dg, old_db = ref.grid((H,), 22, 4.0), ref.grid((H,), 23, 4.0)
+    old_dg, old_db = fp.grid((H,), 22, 4.0), fp.grid((H,), 23, 4.0)
     m = M - 2
     rb = ref.reference_and_bound(**case, m=m, old_dg=old_dg, old_db=old_db)
     assert not _outside(ref.emulate(**case, m=m, old_dg=old_dg, old_db=old_db), rb)
     emu = ref.emulate(**case, m=m, old_dg=old_dg, old_db=old_db, mutation=mutation)
-    r = {k: ref.worst_ratio(got, *rb[k])[0] for k, got in zip(OUTPUTS, emu[1:])}
+    r = {k: fp.worst_ratio(got, *rb[k])[0] for k, got in zip(OUTPUTS, emu[1:])}
     print(f"mutation {mutation}: worst |err| / bound " + ", ".join(f"{k} {v:.3g}" for k, v in r.items()))
     assert max(r.values()) > 1.0, mutation
     assert _outside(emu, rb)

@@ -16,19 +16,18 @@ the four Linears of roberta-base at M = 300; and linear_grad_ref.LARGE_MNK, the 
 weight-gradient kernel holds three slabs or more (its register double buffer in the steady state, S >= 3 partials, a ragged last chunk) and
 at which dX of FFN2 leaves the one-tile GEMMs for a persistent kernel with its device-side row count.
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import linear_grad_ref as ref
+from guarded import E_INVALID, E_WORKSPACE, SENTINEL, Guarded, dev
+from multihop_dense_retrieval_amd._lib import ptr
+from oracle import fp
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 777.0  # finite, fp16-exact, far from every expected output
 GUARD = 64        # rows of dx / elements of dw and db in front of and behind the call's own, which must keep their bits
-OK, E_INVALID, E_WORKSPACE = 0, -1, -4
 # (M, N, K): M None is the shape's sweep of small row counts (ms_for); LARGE_MNK gives its own M
 ALL_NK = [pytest.param(None, N, K, id=f"N{N}-K{K}") for N, K in ref.SMALL_NK + ref.MODEL_NK] + \
          [pytest.param(M, N, K, id=f"M{M}-N{N}-K{K}") for M, N, K in ref.LARGE_MNK]
@@ -41,17 +40,9 @@ def ms_for(N, K, M=None):
     return ref.M_SWEEP if (N, K) in ref.SMALL_NK else [300]
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def dev(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def raw_call(x, w, dy, pre, M, m_dev, N, K, dx, dw, db, accumulate, ws, ws_bytes):
     from multihop_dense_retrieval_amd import _lib, linear
-    return linear.lib().mdr_linear_backward(_p(x), _p(w), _p(dy), _p(pre), M, _p(m_dev), N, K, _p(dx), _p(dw), _p(db), accumulate, _p(ws), ws_bytes,
+    return linear.lib().mdr_linear_backward(ptr(x), ptr(w), ptr(dy), ptr(pre), M, ptr(m_dev), N, K, ptr(dx), ptr(dw), ptr(db), accumulate, ptr(ws), ws_bytes,
                                             0, _lib.current_stream_ptr())
 
 
@@ -62,36 +53,18 @@ def run(x, w, dy, pre=None, m=None, outs="xwb", old_dw=None, old_db=None, accumu
     from multihop_dense_retrieval_amd import _lib, linear
     M, K = x.shape
     N = w.shape[0]
-    bx = torch.full((GUARD + M + GUARD, K), SENTINEL, dtype=torch.float16, device="cuda")
-    bw = torch.full((GUARD + N * K + GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
-    bb = torch.full((GUARD + N + GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
-    if old_dw is not None:
-        bw[GUARD:GUARD + N * K] = dev(old_dw.astype(np.float32)).reshape(-1)
-    if old_db is not None:
-        bb[GUARD:GUARD + N] = dev(old_db.astype(np.float32))
+    bx = Guarded(M, (K,), torch.float16, GUARD, GUARD, name="dx")
+    bw = Guarded(N * K, (), torch.float32, GUARD, GUARD, None if old_dw is None else old_dw.astype(np.float32), "dw", "elements")
+    bb = Guarded(N, (), torch.float32, GUARD, GUARD, None if old_db is None else old_db.astype(np.float32), "db", "elements")
     want = (1 if "x" in outs else 0) | (2 if "w" in outs else 0) | (4 if "b" in outs else 0) | (8 if pre is not None else 0)
     need = int(linear.lib().mdr_linear_backward_workspace_bytes(M, N, K, want))
     ws = torch.empty(max(need + ws_extra, 16), dtype=torch.uint8, device="cuda")
     m_dev = None if m is None else torch.tensor([m], dtype=torch.int32, device="cuda")
-    _lib.check(raw_call(dev(x), dev(w), dev(dy), dev(pre), M, m_dev, N, K, bx[GUARD:GUARD + M] if "x" in outs else None,
-                        bw[GUARD:GUARD + N * K] if "w" in outs else None, bb[GUARD:GUARD + N] if "b" in outs else None, 1 if accumulate else 0, ws,
-                        need + ws_extra))
+    _lib.check(raw_call(dev(x), dev(w), dev(dy), dev(pre), M, m_dev, N, K, bx.own if "x" in outs else None, bw.own if "w" in outs else None,
+                        bb.own if "b" in outs else None, 1 if accumulate else 0, ws, need + ws_extra))
     torch.cuda.synchronize()
-    gx, gw, gb = bx.cpu().numpy(), bw.cpu().numpy(), bb.cpu().numpy()
-    s16, s32 = np.float16(SENTINEL), np.float32(SENTINEL)
-    assert (gx[:GUARD] == s16).all() and (gx[GUARD + M:] == s16).all(), "dx rows outside the call were written"
-    assert (gw[:GUARD] == s32).all() and (gw[GUARD + N * K:] == s32).all(), "dw elements outside the call were written"
-    assert (gb[:GUARD] == s32).all() and (gb[GUARD + N:] == s32).all(), "db elements outside the call were written"
-    mm = M if m is None else m
-    if "x" in outs:
-        assert (gx[GUARD + mm:GUARD + M] == s16).all(), "dx rows at or behind the valid count were written"
-    else:
-        assert (gx == s16).all(), "dx written though not asked for"
-    if "w" not in outs and old_dw is None:
-        assert (gw == s32).all(), "dw written though not asked for"
-    if "b" not in outs and old_db is None:
-        assert (gb == s32).all(), "db written though not asked for"
-    return {"dx": gx[GUARD:GUARD + M], "dw": gw[GUARD:GUARD + N * K].reshape(N, K), "db": gb[GUARD:GUARD + N]}
+    return {"dx": bx.checked(valid=M if m is None else m, asked="x" in outs), "dw": bw.checked(asked="w" in outs).reshape(N, K),
+            "db": bb.checked(asked="b" in outs)}
 
 
 def forward_hook(x, w, b, epilogue, m=None):
@@ -102,7 +75,7 @@ def forward_hook(x, w, b, epilogue, m=None):
     out = torch.zeros((M, N), dtype=torch.float16, device="cuda")
     m_dev = None if m is None else torch.tensor([m], dtype=torch.int32, device="cuda")
     tx, tw, tb = dev(x), dev(w), dev(b)  # (held until the synchronise below)
-    _lib.check(_lib.lib().mdr_test_gemm_f16(_p(tx), _p(tw), _p(tb), M, _p(m_dev), N, K, _p(out), epilogue, 0, 0, _lib.current_stream_ptr()))
+    _lib.check(_lib.lib().mdr_test_gemm_f16(ptr(tx), ptr(tw), ptr(tb), M, ptr(m_dev), N, K, ptr(out), epilogue, 0, 0, _lib.current_stream_ptr()))
     torch.cuda.synchronize()
     return out.cpu().numpy()
 
@@ -126,7 +99,7 @@ def exact_grid(x, w, dz, m=None, old_dw=None, old_db=None):
                            (np.abs(DZ).T @ np.abs(X) + np.abs(odw), min(_quantum(DZ) * _quantum(X), _quantum(odw))),
                            (np.abs(DZ).sum(axis=0) + np.abs(odb), min(_quantum(DZ), _quantum(odb)))):
         assert total.size == 0 or total.max() / quantum <= 2.0 ** 24, "the grid no longer guarantees exact fp32 sums"
-    assert dx.size == 0 or np.abs(dx).max() < ref.F16_MAX, "an exact dX leaves the fp16 range: shrink w"
+    assert dx.size == 0 or np.abs(dx).max() < fp.F16_MAX, "an exact dX leaves the fp16 range: shrink w"
     assert (dw.astype(np.float32) == dw).all() and (db.astype(np.float32) == db).all()
     return dx.astype(np.float16), dw.astype(np.float32), db.astype(np.float32)
 
@@ -155,7 +128,7 @@ def assert_equal(got, want, m, label):
 
 
 def grid_inputs(M, N, K, seed, loss_scale=False):
-    x, w, dy = ref.grid((M, K), seed), ref.grid((N, K), seed + 1), ref.grid((M, N), seed + 2)
+    x, w, dy = (fp.grid(shape, seed + i, dtype=np.float16) for i, shape in enumerate(((M, K), (N, K), (M, N))))
     if loss_scale:  # dy x 2^8 as under a loss scale; w shrunk by 2^-4 so that no exact dX leaves the fp16 range (asserted in exact_grid)
         w, dy = (w.astype(np.float32) / 16).astype(np.float16), (dy.astype(np.float32) * 256).astype(np.float16)
     return x, w, dy
@@ -200,7 +173,7 @@ def test_exact_grid_equality(M, N, K, loss_scale):
 def test_accumulate_on_the_grid(M, N, K):
     for M in ms_for(N, K, M):
         x, w, dy = grid_inputs(M, N, K, 5)
-        old_dw, old_db = ref.grid((N, K), 8).astype(np.float32) * 4, ref.grid((N,), 9).astype(np.float32) * 4
+        old_dw, old_db = fp.grid((N, K), 8, 4.0), fp.grid((N,), 9, 4.0)
         got = run(x, w, dy, old_dw=old_dw, old_db=old_db, accumulate=True)
         assert_equal(got, exact_grid(x, w, dy, None, old_dw, old_db), M, f"accumulate M={M} N={N} K={K}")
         got = run(x, w, dy, old_dw=old_dw, old_db=old_db, accumulate=False)
@@ -208,17 +181,11 @@ def test_accumulate_on_the_grid(M, N, K):
 
 
 def check_bound(got, rb, m, label):
-    fails = []
     for name in ("dx", "dw", "db"):
         g = got[name][:m] if name == "dx" else got[name]
         r, bnd = rb[name]
-        worst, at = ref.worst_ratio(g, r, bnd)
+        worst = fp.assert_within(g, r, bnd, f"{label}: {name}")
         print(f"RATIO {label} {name} worst |err| / bound = {worst:.4f}")
-        if worst > 1.0:
-            g2, r2, b2 = (np.atleast_2d(a) for a in (g, r, bnd))
-            fails.append(f"{name} outside the bound: worst {worst:.3f} at row {at[0]}, column {at[1]}: got {float(g2[at])!r}, reference {r2[at]!r}, bound {b2[at]:.3e}")
-    if fails:
-        pytest.fail(f"{label}: " + "; ".join(fails))
 
 
 @pytest.mark.parametrize("scale", [1.0, 256.0], ids=["unit", "x256"])
@@ -254,7 +221,7 @@ def test_subnormal_operand_columns_within_the_derived_bound():
     check_bound(got, rb, M, f"subnormal columns M={M} N={N} K={K}")
     r, bnd = rb["dw"]
     without_f = bnd - ref.field_floor_term(np.abs(dy.astype(np.float64)).T, np.abs(x.astype(np.float64)))
-    print(f"RATIO subnormal columns dw against the bound WITHOUT the exponent-field term: {ref.worst_ratio(got['dw'], r, without_f)[0]:.4f}")
+    print(f"RATIO subnormal columns dw against the bound WITHOUT the exponent-field term: {fp.worst_ratio(got['dw'], r, without_f)[0]:.4f}")
 
 
 @pytest.mark.parametrize("M,N,K", ALL_NK)
@@ -288,7 +255,7 @@ def test_rows_behind_m_dev_do_not_exist(M, N, K, gelu0):
     dx rows at or behind m keep the sentinel (run() asserts it); m = 0 gives zeros, or the old value with accumulate."""
     x, w, dy = grid_inputs(M, N, K, 17)
     pre = np.zeros((M, N), np.float16) if gelu0 else None
-    old_dw, old_db = ref.grid((N, K), 18).astype(np.float32), ref.grid((N,), 19).astype(np.float32)
+    old_dw, old_db = fp.grid((N, K), 18), fp.grid((N,), 19)
     for m in ((0, 1, M - 1, M) if M == 200 else large_ms(M, N, K)):
         xb, dyb = x.copy(), dy.copy()
         xb[m:], dyb[m:] = np.nan, np.inf

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import linear_grad_ref as ref
+from oracle import fp
 
 OUTPUTS = ("dx", "dw", "db")
 
@@ -17,7 +18,7 @@ def _pre(x, w, b):
 
 
 def _ratios(got, rb):
-    return {k: ref.worst_ratio(g, *rb[k]) for k, g in zip(OUTPUTS, got)}
+    return {k: fp.worst_ratio(g, *rb[k]) for k, g in zip(OUTPUTS, got)}
 
 
 @pytest.mark.parametrize("gelu", [False, True])
@@ -144,10 +145,10 @@ def test_the_exponent_field_term_covers_subnormal_columns_and_is_zero_otherwise(
     r, bnd = ref.reference_and_bound(x, w, dy)["dw"]
     f = ref.field_floor_term(np.abs(dy.astype(np.float64)).T, np.abs(x.astype(np.float64)))
     got = ref.aligned_dw(x, dy)
-    with_f, without_f = ref.worst_ratio(got, r, bnd)[0], ref.worst_ratio(got, r, bnd - f)[0]
+    with_f, without_f = fp.worst_ratio(got, r, bnd)[0], fp.worst_ratio(got, r, bnd - f)[0]
     print(f"aligned model, subnormal columns: share of the bound {with_f:.3f}, without F {without_f:.3f}, {int((np.abs(got - r) > bnd - f).sum())} elements over")
     assert with_f <= 1.0 < without_f
     xn, _, dyn = ref.realistic(4, 256, 384, 18)
-    assert not (np.abs(xn) < ref.N16).any() and not (np.abs(dyn) < ref.N16).any()
+    assert not (np.abs(xn) < fp.N16).any() and not (np.abs(dyn) < fp.N16).any()
     assert not ref.field_floor_term(np.abs(dyn.astype(np.float64)).T, np.abs(xn.astype(np.float64))).any()
-    assert ref.worst_ratio(ref.aligned_dw(xn, dyn), *ref.reference_and_bound(xn, _, dyn)["dw"])[0] <= 1.0  # normal operands: inside the ulp count
+    assert fp.worst_ratio(ref.aligned_dw(xn, dyn), *ref.reference_and_bound(xn, _, dyn)["dw"])[0] <= 1.0  # normal operands: inside the ulp count

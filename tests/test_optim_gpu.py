@@ -13,13 +13,13 @@ expressions of the device's grad_norm, bit for bit.
 
 The trajectory's bar is e(ours) <= 2 e(torch fp32), e the largest |p - p64| / (|p64| + 1e-3) over the 12 tensors after 20 steps: two
 correct fp32 implementations differ from fp64 by their own roundings (criterion E)."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import optim_ref as ref
+from multihop_dense_retrieval_amd._lib import ptr
+from oracle.fp import bits, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -29,19 +29,6 @@ HYPER = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, max_grad_norm=2.0)
 SMALL = [1, 3, 63, 64, 65, 4095, 4096, 4097, 3 * C + 1]
 BIG = 9_000_001  # 2198 chunks: more than the grid's 2048 workgroups and than the finalize workgroup's 1024 threads
 SLACK = 8        # elements allocated behind every tensor's n
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({2: np.uint16, 4: np.uint32}[a.dtype.itemsize])
-
-
-def same_bits(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def slack_tensor(values, fill, dtype=torch.float32):
@@ -85,7 +72,7 @@ class Table:
         self.table = torch.from_numpy(host).to("cuda")
         self.ws = torch.full((optim.workspace_bytes(sizes) // 4,), fill, dtype=torch.float32, device="cuda")
         self.state = torch.zeros(16, dtype=torch.int32, device="cuda")
-        _lib.check(optim.lib().mdr_optim_state_init(_p(self.state), scale, 0, _lib.current_stream_ptr()))
+        _lib.check(optim.lib().mdr_optim_state_init(ptr(self.state), scale, 0, _lib.current_stream_ptr()))
         self.model = ref.initial_state(scale)
         self.state_kw = dict(dynamic=1, scale_window=2000, max_scale=2.0 ** 24)
         self.state_kw.update(state_kw)
@@ -97,9 +84,9 @@ class Table:
 
     def step(self, lr=HYPER["lr"], zero_grads=1):
         k = self.state_kw
-        self._lib.check(self.optim.lib().mdr_optim_step(_p(self.table), len(self.sizes), self.n_chunks, _p(self.state), lr, HYPER["beta1"], HYPER["beta2"],
+        self._lib.check(self.optim.lib().mdr_optim_step(ptr(self.table), len(self.sizes), self.n_chunks, ptr(self.state), lr, HYPER["beta1"], HYPER["beta2"],
                                                          HYPER["eps"], HYPER["max_grad_norm"], k["dynamic"], k["scale_window"], k["max_scale"], zero_grads,
-                                                         _p(self.ws), self.ws.numel() * 4, 0, self._lib.current_stream_ptr()))
+                                                         ptr(self.ws), self.ws.numel() * 4, 0, self._lib.current_stream_ptr()))
 
     def read_state(self):
         raw = self.state.cpu().numpy().view(np.uint8)[:self.optim.STATE_DTYPE.itemsize].view(self.optim.STATE_DTYPE)[0]

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import optim_ref as ref
+from oracle import fp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, WORKSPACE = -1, -4
@@ -111,7 +112,7 @@ def test_state_machine_window_of_three():
     for k, s in ((1, seen[0]), (3, seen[4]), (4, seen[5])):  # the carried bias terms keep their relative precision; 1 - b2_pow does not
         for name, beta in (("bias1", 0.9), ("bias2", 0.999)):
             exact = 1.0 - float(np.float32(beta)) ** k
-            assert abs(float(s[name]) - exact) <= 4 * k * ref.U * exact, (k, name)
+            assert abs(float(s[name]) - exact) <= 4 * k * fp.U32 * exact, (k, name)
     assert abs(float(np.float32(1) - seen[5]["b2_pow"]) - (1.0 - float(np.float32(0.999)) ** 4)) > 1e-6 * (1.0 - 0.999 ** 4)
 
 

@@ -20,7 +20,8 @@ import torch
 import encoder_chain_ref as ch
 import optim_ref
 import overflow_ref as ov
-from encoder_chain_dev import Chain, _p, check_e, params, poison, same_bits
+from encoder_chain_dev import Chain, check_e, params, poison, same_bits
+from multihop_dense_retrieval_amd._lib import ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -85,7 +86,7 @@ def assert_grads_plus_zero(P, label):
 
 def set_scale(opt, scale):
     from multihop_dense_retrieval_amd import _lib, optim
-    _lib.check(optim.lib().mdr_optim_state_init(_p(opt._state), float(scale), 0, _lib.current_stream_ptr()))
+    _lib.check(optim.lib().mdr_optim_state_init(ptr(opt._state), float(scale), 0, _lib.current_stream_ptr()))
 
 
 # ---- C ---------------------------------------------------------------------------------------------------------------------------------------

@@ -29,7 +29,8 @@ import test_inbatch_grad_gpu as it
 import test_layernorm_grad_gpu as nt
 import test_linear_grad_gpu as lt
 import test_optim_gpu as ot
-from oracle import seeded
+from oracle import fp, seeded
+from oracle.fp import bits, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -40,15 +41,6 @@ TINY = seeded.TINY
 def bad(a):
     """bool array: the non-finite elements"""
     return ~np.isfinite(np.asarray(a).astype(np.float32))
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({2: np.uint16, 4: np.uint32}[a.dtype.itemsize])
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def planted(a, at, v):
@@ -76,7 +68,7 @@ def assert_delivered(grads, label):
     after = t.read()
     for name, a, b in zip("p m v p16".split(), before[:4], after[:4]):
         for x, y in zip(a, b):
-            assert (x is None and y is None) or same(x, y), (label, name, "a skipped step changed it")
+            assert (x is None and y is None) or same_bits(x, y), (label, name, "a skipped step changed it")
     for g, n in zip(after[4], t.sizes):
         assert not bits(g[:n]).any(), (label, "g is not all +0 after the skipped step")
 
@@ -90,10 +82,10 @@ def linear_inputs(M, N, K, gelu):
 
 def assert_dy_sets(got, clean, rows, m0, n0, label):
     assert bad(got["dx"][m0]).all(), (label, "dx row")
-    assert same(got["dx"][:rows][rows_but(rows, m0)], clean["dx"][:rows][rows_but(rows, m0)]), (label, "other dx rows")
+    assert same_bits(got["dx"][:rows][rows_but(rows, m0)], clean["dx"][:rows][rows_but(rows, m0)]), (label, "other dx rows")
     N = got["db"].shape[0]
-    assert bad(got["dw"][n0]).all() and same(got["dw"][rows_but(N, n0)], clean["dw"][rows_but(N, n0)]), (label, "dw")
-    assert bad(got["db"][n0]) and same(got["db"][rows_but(N, n0)], clean["db"][rows_but(N, n0)]), (label, "db")
+    assert bad(got["dw"][n0]).all() and same_bits(got["dw"][rows_but(N, n0)], clean["dw"][rows_but(N, n0)]), (label, "dw")
+    assert bad(got["db"][n0]) and same_bits(got["db"][rows_but(N, n0)], clean["db"][rows_but(N, n0)]), (label, "db")
 
 
 @pytest.mark.parametrize("v", PLANTS)
@@ -117,10 +109,10 @@ def test_a_linear_delivers_and_contains(M, rows, N, K, gelu, v):
         got = lt.run(planted(x, (m0, k0), v), w, dy, pre, m=rows)
         dz = lref.reference_and_bound(x, w, dy, pre, rows)["dz"][0]
         assert (dz[m0] != 0).any() and bad(got["dw"][dz[m0] != 0, k0]).all(), ("x", m0)
-        assert same(got["dw"][:, rows_but(K, k0)], clean["dw"][:, rows_but(K, k0)]) and same(got["db"], clean["db"]), ("x", m0)
-        assert same(got["dx"][:rows], clean["dx"][:rows]), ("x", m0, "dx")
+        assert same_bits(got["dw"][:, rows_but(K, k0)], clean["dw"][:, rows_but(K, k0)]) and same_bits(got["db"], clean["db"]), ("x", m0)
+        assert same_bits(got["dx"][:rows], clean["dx"][:rows]), ("x", m0, "dx")
     # accumulate: finite old values, the same sets
-    old_dw, old_db = lref.grid((N, K), 8).astype(np.float32) * 4, lref.grid((N,), 9).astype(np.float32) * 4
+    old_dw, old_db = fp.grid((N, K), 8, 4.0), fp.grid((N,), 9, 4.0)
     clean_acc = lt.run(x, w, dy, pre, m=rows, old_dw=old_dw, old_db=old_db, accumulate=True)
     got = lt.run(x, w, planted(dy, (last, n0), v), pre, m=rows, old_dw=old_dw, old_db=old_db, accumulate=True)
     assert_dy_sets(got, clean_acc, rows, last, n0, f"accumulate dy[{last}, {n0}] = {v}")
@@ -144,7 +136,7 @@ def test_a_layernorm_delivers_and_contains(M, rows, H, form, v):
     def others_untouched(got, m0, label):
         for k in ("dx16", "dx32"):
             assert bad(got[k][m0]).all(), (label, k, "the row")
-            assert same(got[k][:rows][rows_but(rows, m0)], clean[k][:rows][rows_but(rows, m0)]), (label, k, "other rows")
+            assert same_bits(got[k][:rows][rows_but(rows, m0)], clean[k][:rows][rows_but(rows, m0)]), (label, k, "other rows")
 
     for m0 in (2, rows - 1):
         for key in ("dy16", "dy2") if case["dy2"] is not None else ("dy16",):
@@ -152,14 +144,14 @@ def test_a_layernorm_delivers_and_contains(M, rows, H, form, v):
             label = f"{key}[{m0}, {c0}] = {v}"
             others_untouched(got, m0, label)
             for k in ("dg", "db"):
-                assert bad(got[k][c0]) and same(got[k][rows_but(H, c0)], clean[k][rows_but(H, c0)]), (label, k)
+                assert bad(got[k][c0]) and same_bits(got[k][rows_but(H, c0)], clean[k][rows_but(H, c0)]), (label, k)
         dy = case["dy16"].astype(np.float64) + (0 if case["dy2"] is None else case["dy2"].astype(np.float64))
         for key in ("inp", "res"):
             got = nt.run(**dict(case, **{key: planted(case[key], (m0, c0), v)}), m=rows)
             label = f"{key}[{m0}, {c0}] = {v}"
             others_untouched(got, m0, label)
             assert (dy[m0] != 0).any() and bad(got["dg"][dy[m0] != 0]).all(), (label, "dg")
-            assert same(got["db"], clean["db"]), (label, "db")
+            assert same_bits(got["db"], clean["db"]), (label, "db")
     if H == 64 and form == "dy16":
         got = nt.run(**dict(case, dy16=planted(case["dy16"], (rows - 1, c0), v)), m=rows)
         assert_delivered([got["dg"], got["db"]], "layernorm")
@@ -173,8 +165,8 @@ def test_a_gather_cls_backward_lands_on_its_row_only(v):
     H, lens = 64, [5, 1, 64, 7]
     cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
     T = int(cu[-1])
-    dx = lref.grid((T + 3, H), 51)
-    d_cls = lref.grid((len(lens), H), 52)
+    dx = fp.grid((T + 3, H), 51, dtype=np.float16)
+    d_cls = fp.grid((len(lens), H), 52, dtype=np.float16)
     tcu = torch.from_numpy(cu).cuda()
     clean = layernorm.gather_cls_backward(torch.from_numpy(d_cls).cuda(), tcu, torch.from_numpy(dx).cuda().clone()).cpu().numpy()
     assert not bad(clean).any()
@@ -217,10 +209,10 @@ def test_a_embedding_delivers_and_contains(accumulate, v):
         assert bad(got["dword"][wrow]).all() and bad(got["dpos"][prow[t0_]]).all() and bad(got["dtype0"]).all(), label
         assert bad(got["dg"][c0]) and bad(got["db"][c0]), label
         for k in ("dg", "db"):
-            assert same(got[k][rows_but(H, c0)], clean[k][rows_but(H, c0)]), (label, k)
-        assert same(np.delete(got["dword"], wrow, 0), np.delete(clean["dword"], wrow, 0)), (label, "other word rows")
-        assert same(np.delete(got["dpos"], prow[t0_], 0), np.delete(clean["dpos"], prow[t0_], 0)), (label, "other position rows")
-        assert same(got["d"][rows_but(total, t0_)], clean["d"][rows_but(total, t0_)]) and bad(got["d"][t0_]).all(), (label, "d")
+            assert same_bits(got[k][rows_but(H, c0)], clean[k][rows_but(H, c0)]), (label, k)
+        assert same_bits(np.delete(got["dword"], wrow, 0), np.delete(clean["dword"], wrow, 0)), (label, "other word rows")
+        assert same_bits(np.delete(got["dpos"], prow[t0_], 0), np.delete(clean["dpos"], prow[t0_], 0)), (label, "other position rows")
+        assert same_bits(got["d"][rows_but(total, t0_)], clean["d"][rows_but(total, t0_)]) and bad(got["d"][t0_]).all(), (label, "d")
         if not accumulate:
             empty = owners == 0
             empty[TINY["pad_id"]] = True
@@ -256,10 +248,10 @@ def test_a_inbatch_loss_delivers_and_contains(B, d, K, mode, v):
         loss, got = it.run(dict(inp, **{leaf: planted(inp[leaf], (i0, col), v)}), queue, mode, g0)
         label = f"{leaf}[{i0}, {col}] = {v}"
         assert np.isnan(loss) if np.isnan(v) else not np.isfinite(loss), label
-        assert bad(got[own][i0]).all() and same(got[own][rows_but(B, i0)], clean[own][rows_but(B, i0)]), (label, "its own row of d" + own)
-        assert same(got[other], clean[other]), (label, "the other hop's queries")
+        assert bad(got[own][i0]).all() and same_bits(got[own][rows_but(B, i0)], clean[own][rows_but(B, i0)]), (label, "its own row of d" + own)
+        assert same_bits(got[other], clean[other]), (label, "the other hop's queries")
         for k in ("neg_1", "neg_2"):
-            assert same(got[k][rows_but(B, i0)], clean[k][rows_but(B, i0)]), (label, k, "another row's negatives")
+            assert same_bits(got[k][rows_but(B, i0)], clean[k][rows_but(B, i0)]), (label, k, "another row's negatives")
         # every context row the hop feeds gets g * x[i0, col] at column `col`: g * Inf is Inf, or NaN where g is 0 or NaN -- non-finite whatever v is
         keep = rows_but(B, i0) if leaf == "q" else np.ones(B, bool)
         assert bad(got["c1"][:, col]).all() and bad(got["c2"][keep, col]).all(), (label, "column `col` of the context gradients")
@@ -291,15 +283,15 @@ def test_b_linear_dx_leaves_fp16_as_inf_of_the_right_sign(M, rows, N, K, gelu):
     print(f"B linear M={M} N={N} K={K} gelu={gelu} s_dy={c['s_dy']:g} s_w={c['s_w']:g} classes {sh}")
     # dW and db are fp32: inside the bound, except where an overflowed dZ feeds them, and there non-finite -- the overflow is delivered
     dz, edz = c["ref"]["dz"]
-    over = (np.abs(dz) - edz >= ov.F16_EDGE).any(axis=0)
-    doubt = (np.abs(dz) + edz >= ov.F16_EDGE).any(axis=0) & ~over
+    over = (np.abs(dz) - edz >= fp.F16_EDGE).any(axis=0)
+    doubt = (np.abs(dz) + edz >= fp.F16_EDGE).any(axis=0) & ~over
     assert over.any() == gelu
     fine = ~over & ~doubt
     for name in ("dw", "db"):
         g = got[name]
         if over.any() and not bad(g[over]).all():
             fails.append(f"{name}: an overflowed dZ did not reach it")
-        worst, at = lref.worst_ratio(g[fine], c["ref"][name][0][fine], c["ref"][name][1][fine])
+        worst, at = fp.worst_ratio(g[fine], c["ref"][name][0][fine], c["ref"][name][1][fine])
         print(f"B linear {name} worst |err| / bound {worst:.4f}")
         if not worst <= 1.0:
             fails.append(f"{name} outside the bound: {worst:.3f} at {at}")
@@ -320,7 +312,7 @@ def test_b_layernorm_dx16_leaves_fp16_as_inf_of_the_right_sign(M, rows, H, form)
     if not (err32 <= b).all():   # the fp32 copy of the same value does not overflow
         fails.append(f"dx32 outside the bound at {np.argwhere(~(err32 <= b))[0]}")
     for name in ("dg", "db"):
-        worst, at = nref.worst_ratio(got[name], *c["ref"][name])
+        worst, at = fp.worst_ratio(got[name], *c["ref"][name])
         if not worst <= 1.0:
             fails.append(f"{name} outside the bound: {worst:.3f} at {at}")
     assert not fails, fails
@@ -370,8 +362,8 @@ def test_b_every_gemm_epilogue_overflows_to_inf_bit_for_bit(kernel):
     that every fp32 partial sum in any order is an integer below 2^24 and exact. The fp16 output must EQUAL the one rounding of the exact
     value, +-Inf from 65520 on: no bound at all."""
     M, N, K = 300, 256, 256
-    x = (gemm_ref.grid((M, K), 61).astype(np.float32) * 64).astype(np.float16)
-    w = (gemm_ref.grid((N, K), 62).astype(np.float32) * 32).astype(np.float16)
+    x = fp.grid((M, K), 61, 64.0, np.float16)
+    w = fp.grid((N, K), 62, 32.0, np.float16)
     b = np.round(gemm_ref.grid_bias(N, 63).astype(np.float64) * 64).astype(np.float32)
     X, W = x.astype(np.float64), w.astype(np.float64)
     assert (X == np.round(X)).all() and (W == np.round(W)).all() and (np.abs(X) @ np.abs(W).T + np.abs(b)).max() <= 2.0 ** 24

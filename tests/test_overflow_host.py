@@ -8,8 +8,9 @@ import pytest
 
 import encoder_chain_ref as ch
 import overflow_ref as ov
+from oracle import fp
 
-E = ov.F16_EDGE
+E = fp.F16_EDGE
 
 
 def test_classify_on_hand_made_arrays():
@@ -69,7 +70,7 @@ def test_linear_case_meets_the_caps(M, rows, N, K, gelu):
         dz, edz = c["ref"]["dz"]
         over = np.abs(dz) - edz >= E
         assert over.any() and np.array_equal(over.any(axis=1), c["poisoned"][:, 0])
-        assert (np.abs(c["dy"][:rows].astype(np.float64)) <= ov.F16_MAX).all()   # dy itself stays inside: the overflow is dZ's own
+        assert (np.abs(c["dy"][:rows].astype(np.float64)) <= fp.F16_MAX).all()   # dy itself stays inside: the overflow is dZ's own
 
 
 @pytest.mark.parametrize("form", list(ov.LN_FORMS))
@@ -96,7 +97,7 @@ def test_attention_case_meets_the_caps(mode):
     assert c["poisoned"].any() and not c["poisoned"][:, 2 * hidden:].any() and (cls[~live] == ov.FINITE).all()
     assert np.isfinite(c["dctx"]).all() and np.isfinite(c["qkv"]).all()
     if mode == 3:  # p <= 1: no dV element can leave fp16
-        assert np.abs(c["ref"][0][:, 2 * hidden:]).max() <= np.abs(c["dctx"].astype(np.float64)).max() <= ov.F16_MAX
+        assert np.abs(c["ref"][0][:, 2 * hidden:]).max() <= np.abs(c["dctx"].astype(np.float64)).max() <= fp.F16_MAX
     with np.errstate(all="ignore"):
         emu = aref.emulate(c["qkv"], c["dctx"], c["cu"], c["heads"], mode)
     assert ov.verdicts(emu, *c["ref"], cls, "emulation") == []
@@ -125,7 +126,7 @@ def test_loss_case_meets_the_caps():
 def test_the_ladder():
     for G1 in (0.393, 1.0, 0.5, 0.49999, 3.0e-5, 7.7):
         safe, must, between = ov.ladder(G1)
-        assert safe * G1 <= ov.F16_MAX / 2 < 2 * safe * G1 and must * G1 >= 2 * E > must / 2 * G1
+        assert safe * G1 <= fp.F16_MAX / 2 < 2 * safe * G1 and must * G1 >= 2 * E > must / 2 * G1
         assert must / safe in (4.0, 8.0) and len(between) == (1 if must / safe == 4.0 else 2)
     assert ov.scale_class(2.0 ** 14, 1.0) == ov.SAFE and ov.scale_class(2.0 ** 15, 1.0) == ov.UNDECIDED and ov.scale_class(2.0 ** 16, 1.0) == ov.UNDECIDED
     assert ov.scale_class(2.0 ** 17, 1.0) == ov.MUST
@@ -161,7 +162,7 @@ def test_the_chain_run_holds_its_events_whatever_the_undecided_scales_do():
     # parts C: step 1 at a scale that must overflow, step 2 at a safe one
     assert ov.scale_class(must, G1) == ov.MUST and ov.scale_class(safe, G1) == ov.SAFE
     # the regime itself agrees with its own prediction: finite at the last safe scale, not at the first that must overflow
-    assert must * G1 >= 2 * E and safe * G1 <= ov.F16_MAX / 2
+    assert must * G1 >= 2 * E and safe * G1 <= fp.F16_MAX / 2
 
 
 def test_the_o1_loss_regime_at_b1_overflows_at_2_16_and_not_at_2_12():
@@ -174,4 +175,4 @@ def test_the_o1_loss_regime_at_b1_overflows_at_2_16_and_not_at_2_12():
     # and not by a hair: some unrounded term is a factor 1.5 outside, every term at 2^12 a factor 4 inside
     peak = max(np.abs(v).max() for v in mhop_loss_ref.loss_and_grads(inp, None, g0=1.0, o1=False)["grads"].values())
     print(f"LOSS B=1: largest |gradient| at g0 = 1: {peak:.4f}")
-    assert peak * 2.0 ** 16 >= 1.5 * E and peak * 2.0 ** 12 <= ov.F16_MAX / 4
+    assert peak * 2.0 ** 16 >= 1.5 * E and peak * 2.0 ** 12 <= fp.F16_MAX / 4

@@ -17,6 +17,7 @@ torch = pytest.importorskip("torch")
 transformers = pytest.importorskip("transformers")
 
 from multihop_dense_retrieval_amd import reader  # noqa: E402
+from oracle import fp  # noqa: E402
 
 DEV = "cuda"
 
@@ -386,7 +387,6 @@ def test_head_rounding_points(hidden):
     largest over [|d_j| - ulp, |d_j| + ulp] at the smaller end, so the kernel's tanh argument moves tanh by at most ulp16(d_j) sech^2(max(|d_j| - ulp16(d_j), 0));
     its fp16 rounding (and tanhf's last bits) can add one more spacing of t_j: |t'_j - t_j| <= tau_j = ulp16(d_j) sech^2(...) + ulp16(t_j). Through the dot:
     |got - r| <= ulp16 / 2 + H 2^-24 sum_j (|t_j| + tau_j) |w_j| + sum_j tau_j |w_j|."""
-    u32 = 2.0 ** -24
     worst = {"start": 0.0, "end": 0.0, "sp": 0.0, "rank": 0.0}
     for seed in range(12):
         cfg = _electra(hidden, 1, 256)
@@ -405,7 +405,7 @@ def test_head_rounding_points(hidden):
         def dot_check(got, w, b, terms, extra, label):
             r = (terms * w).sum() + b
             got = got.double().flatten()
-            bound = 0.5 * _ulp16(torch.maximum(got.abs(), r.abs())) + hidden * u32 * ((terms.abs() + extra) * w.abs()).sum() + (extra * w.abs()).sum()
+            bound = 0.5 * _ulp16(torch.maximum(got.abs(), r.abs())) + hidden * fp.U32 * ((terms.abs() + extra) * w.abs()).sum() + (extra * w.abs()).sum()
             err = (got - r).abs()
             worst[label] = max(worst[label], (err / bound).max().item())
             assert bool((err <= bound).all()), f"hidden {hidden} seed {seed} {label}: got {got[err.argmax()].item()!r} exact {r.item()!r} |err| {err.max().item():.3e} bound {bound.min().item():.3e}"

@@ -8,12 +8,13 @@ each wrong formula; no tolerance here was read off a device. Every output buffer
 own, and rows the call must not write (rows >= rows, tokens >= total, `order` above 1024 sequences) start as sentinels: all must keep their bits.
 Each check prints `SHARE kernel=... family=... share=...`, the largest part of the bound the device used (profiles/trunk_rows_bound_usage.md).
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
+import guarded
+from guarded import ISENTINEL, dev
+from multihop_dense_retrieval_amd._lib import ptr
 from oracle import trunk_rows_oracle as tr
 
 pytestmark = pytest.mark.gpu
@@ -27,34 +28,13 @@ def lib():
     return _lib, _lib.lib()
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-class Guarded:
+def guarded_rows(rows, width, dtype, init=None):
     """A device buffer of `rows` rows (of `width`) between GUARD sentinel rows; `init` (numpy, optional) fills the call's own rows."""
-
-    def __init__(self, rows, width, dtype, init=None):
-        self.rows, self.sent = rows, (tr.ISENTINEL if dtype == torch.int32 else tr.SENTINEL)
-        self.buf = torch.full((GUARD + rows + GUARD, width), self.sent, dtype=dtype, device="cuda")
-        self.own = self.buf[GUARD:GUARD + rows]
-        if init is not None:
-            self.own.copy_(dev(init).reshape(rows, width))
-
-    def get(self):
-        """The call's rows (numpy) after asserting that the guards kept their bits."""
-        got = self.buf.cpu().numpy()
-        edge = np.concatenate([got[:GUARD], got[GUARD + self.rows:]])
-        assert (edge == edge.dtype.type(self.sent)).all(), "rows outside the call were written"
-        return got[GUARD:GUARD + self.rows]
+    return guarded.Guarded(rows, (width,), dtype, GUARD, GUARD, init)
 
 
 def untouched(rows, what):
-    assert (rows == rows.dtype.type(tr.ISENTINEL if rows.dtype == np.int32 else tr.SENTINEL)).all(), f"{what} were written"
+    guarded.assert_untouched(rows, f"{what} were written")
 
 
 # ---- packing -------------------------------------------------------------------------------------------------------------------------------
@@ -62,12 +42,12 @@ def untouched(rows, what):
 def test_pack(B, L, kind, mask_kind, pad_id):
     _lib, L_ = lib()
     ids, mask = tr.make_pack_case(kind, B, L, pad_id, 1, mask_kind)
-    bufs = {k: Guarded(n, 1, torch.int32) for k, n in (("lens", B), ("cu", B + 1), ("total", 1), ("order", B), ("tok_src", B * L), ("tok_pid", B * L))}
+    bufs = {k: guarded_rows(n, 1, torch.int32) for k, n in (("lens", B), ("cu", B + 1), ("total", 1), ("order", B), ("tok_src", B * L), ("tok_pid", B * L))}
     t_ids, t_mask = dev(ids), dev(mask)  # named, so that both stay allocated across the call
     _lib.check(L_.mdr_test_pack(ptr(t_ids), ptr(t_mask), B, L, pad_id,*(ptr(bufs[k].own) for k in ("lens", "cu", "total", "order", "tok_src", "tok_pid")),
                                 0, _lib.current_stream_ptr()))
     torch.cuda.synchronize()
-    tr.assert_pack({k: v.get().reshape(-1) for k, v in bufs.items()}, ids, mask, pad_id, f"B={B} L={L} {kind} {mask_kind} pad_id={pad_id}")
+    tr.assert_pack({k: v.checked().reshape(-1) for k, v in bufs.items()}, ids, mask, pad_id, ISENTINEL, f"B={B} L={L} {kind} {mask_kind} pad_id={pad_id}")
 
 
 # ---- embeddings + LayerNorm ----------------------------------------------------------------------------------------------------------------
@@ -88,7 +68,7 @@ def run_embed(flavour, ids, mask, ty, pad_id, tables, eps, with32, L, label, tot
     total = int(p["total"][0]) if total_override is None else total_override
     src, pid = p["tok_src"][:total], p["tok_pid"][:total]
     fill = lambda a: np.concatenate([a, np.zeros(cap - len(a), np.int32)])  # noqa: E731  (entries behind total: valid indices, never to be read)
-    out16, out32 = Guarded(cap, H, torch.float16), (Guarded(cap, H, torch.float32) if with32 else None)
+    out16, out32 = guarded_rows(cap, H, torch.float16), (guarded_rows(cap, H, torch.float32) if with32 else None)
     t_ids, t_ty, t_src, t_pid, t_tot = dev(ids), (dev(ty) if ty is not None else None), dev(fill(p["tok_src"])), dev(fill(p["tok_pid"])), dev(np.asarray([total], np.int32))
     t_tab = [dev(a) for a in (word, pos, typ, g, b)]
     _lib.check(L_.mdr_test_embed_ln(flavour, ptr(t_ids), ptr(t_ty), ptr(t_src), ptr(t_pid), ptr(t_tot), cap, L, ptr(t_tab[0]), ptr(t_tab[1]), ptr(t_tab[2]),
@@ -98,11 +78,11 @@ def run_embed(flavour, ids, mask, ty, pad_id, tables, eps, with32, L, label, tot
     wid, prow, trow = tr.embed_rows(ids.reshape(-1), src, pid, word, pos, typ, ty, reader_L=L if flavour == 1 else None)
     x, dx = tr.embed_inputs(word, pos, typ, wid, prow, trow)
     ref, bnd = tr.layer_norm(x, g, b, eps), tr.bound(x, dx, g, b, eps)
-    got16 = out16.get()
+    got16 = out16.checked()
     untouched(got16[total:], "fp16 rows behind total")
     tr.assert_f16(got16[:total], ref, bnd, label)
     if with32:
-        got32 = out32.get()
+        got32 = out32.checked()
         untouched(got32[total:], "fp32 rows behind total")
         print(f"SHARE kernel={'reader_embed_ln' if flavour else 'embed_ln'} family={label.split()[0]} share={tr.assert_f32(got32[:total], ref, bnd, label):.4f}")
     return wid, prow, trow, p
@@ -165,8 +145,8 @@ def run_layernorm(family, in_type, residual, H, eps, rows_cap, outs, rows_dev, s
     t_rows = None if rows_dev == "null" else dev(np.asarray([rows if rows_dev == "below" else rows_cap + 7], np.int32))
     t_in, t_g, t_b = dev(case["inp"]), dev(case["g"]), dev(case["b"])
     t_res = dev(case["res"]) if case["res"] is not None else None
-    out16 = Guarded(rows_cap, H, torch.float16) if outs != "out32" else None
-    out32 = Guarded(rows_cap, H, torch.float32, init=case["res"] if outs == "alias" else None) if outs != "out16" else None
+    out16 = guarded_rows(rows_cap, H, torch.float16) if outs != "out32" else None
+    out32 = guarded_rows(rows_cap, H, torch.float32, init=case["res"] if outs == "alias" else None) if outs != "out16" else None
     res16 = t_res if residual == "res16" else None
     res32 = (out32.own if outs == "alias" else t_res) if residual == "res32" else None
     _lib.check(L_.mdr_test_layernorm(ptr(t_in), 1 if in_type == "f16" else 0, ptr(res16), ptr(res32), rows_cap, ptr(t_rows), H, ptr(t_g), ptr(t_b), eps,
@@ -176,13 +156,13 @@ def run_layernorm(family, in_type, residual, H, eps, rows_cap, outs, rows_dev, s
     x, dx = tr.ln_inputs(case["inp"], case["res"])
     ref, bnd = tr.layer_norm(x, case["g"], case["b"], eps)[:rows], tr.bound(x, dx, case["g"], case["b"], eps)[:rows]
     if out16:
-        got = out16.get()
+        got = out16.checked()
         untouched(got[rows:], "fp16 rows behind rows")
         tr.assert_f16(got[:rows], ref, bnd, label)
         if family == "const2":
             assert np.array_equal(tr.bits16(got[:rows]), tr.bits16(np.broadcast_to(case["b"].astype(np.float16), ref.shape))), label
     if out32:
-        got = out32.get()
+        got = out32.checked()
         if outs == "alias":
             assert np.array_equal(got[rows:].view(np.uint32), case["res"][rows:].view(np.uint32)), "the residual rows behind rows were written"
         else:
@@ -231,13 +211,13 @@ def test_gather_cls(B, H, with32):
     T = int(cu[-1])
     h16 = rng.standard_normal((T, H)).astype(np.float16)
     h32 = rng.standard_normal((T, H)).astype(f32)
-    out16, out32 = Guarded(B, H, torch.float16), (Guarded(B, H, torch.float32) if with32 else None)
+    out16, out32 = guarded_rows(B, H, torch.float16), (guarded_rows(B, H, torch.float32) if with32 else None)
     t16, t32, tcu = dev(h16), (dev(h32) if with32 else None), dev(cu)
     _lib.check(L_.mdr_test_row_copy(0, ptr(t16), ptr(t32), ptr(tcu), B, H, 0, ptr(out16.own), ptr(out32.own) if with32 else None, 0, _lib.current_stream_ptr()))
     torch.cuda.synchronize()
-    assert np.array_equal(tr.bits16(out16.get()), tr.bits16(h16[cu[:-1]]))
+    assert np.array_equal(tr.bits16(out16.checked()), tr.bits16(h16[cu[:-1]]))
     if with32:
-        assert np.array_equal(out32.get().view(np.uint32), h32[cu[:-1]].view(np.uint32))
+        assert np.array_equal(out32.checked().view(np.uint32), h32[cu[:-1]].view(np.uint32))
 
 
 @pytest.mark.parametrize("n", [1, 255, 256, 257, 2 ** 20 + 3])
@@ -250,20 +230,20 @@ def test_f32_to_f16(n):
     srcs = [np.resize(pool, n)] if n > 257 else [np.resize(np.roll(pool, -s), n) for s in range(0, len(pool), len(pool) // 48)] + [np.asarray([v], f32) for v in (65520.0, 65519.0, -0.0, np.nan) if n == 1]
     for src in srcs:
         src = np.ascontiguousarray(src, f32)
-        out = Guarded(1, len(src) + 0, torch.float16)  # one row of n elements between GUARD sentinel rows of the same width
+        out = guarded_rows(1, len(src) + 0, torch.float16)  # one row of n elements between GUARD sentinel rows of the same width
         t = dev(src)
         _lib.check(L_.mdr_test_row_copy(1, None, ptr(t), None, 0, 0, len(src), ptr(out.own), None, 0, _lib.current_stream_ptr()))
         torch.cuda.synchronize()
-        tr.assert_f16_conversion(out.get().reshape(-1), src, f"n={n}")
+        tr.assert_f16_conversion(out.checked().reshape(-1), src, f"n={n}")
 
 
 # ---- hook validation -----------------------------------------------------------------------------------------------------------------------
 def test_bad_arguments_are_errors_and_launch_nothing():
     _lib, L_ = lib()
     i64 = torch.zeros((4, 8), dtype=torch.int64, device="cuda")
-    ints = [Guarded(64, 1, torch.int32) for _ in range(6)]
+    ints = [guarded_rows(64, 1, torch.int32) for _ in range(6)]
     f = torch.zeros((64, 128), dtype=torch.float32, device="cuda")
-    o16, o32 = Guarded(32, 128, torch.float16), Guarded(32, 128, torch.float32)
+    o16, o32 = guarded_rows(32, 128, torch.float16), guarded_rows(32, 128, torch.float32)
     one = torch.ones(1, dtype=torch.int32, device="cuda")
     P = ptr
 
@@ -293,7 +273,7 @@ def test_bad_arguments_are_errors_and_launch_nothing():
         assert word in L_.mdr_last_error().decode(), (fn.__name__, kw, L_.mdr_last_error())
     torch.cuda.synchronize()
     for g_ in ints + [o16, o32]:  # none of the rejected calls launched anything: every output buffer is still all sentinels
-        untouched(g_.get(), "buffers of rejected calls")
+        untouched(g_.checked(), "buffers of rejected calls")
     with pytest.raises(_lib.MdrError):
         _lib.check(pack(B=0))
     assert pack() == 0 and ln() == 0  # and the same arguments without the defect are accepted

@@ -8,6 +8,7 @@
 import numpy as np
 import pytest
 
+from guarded import ISENTINEL
 from oracle import roberta_oracle
 from oracle import trunk_rows_oracle as tr
 
@@ -246,8 +247,8 @@ def wrong_pack(ids, mask, pad_id, defect):
 
 def as_buffers(p, B, L):
     """What the hook's buffers would hold: order untouched above 1024 rows, tok_* untouched beyond total."""
-    pad = lambda a: np.concatenate([a, np.full(B * L - len(a), tr.ISENTINEL, np.int32)])  # noqa: E731
-    return dict(lens=p["lens"], cu=p["cu"], total=p["total"], order=p["order"] if B <= 1024 else np.full(B, tr.ISENTINEL, np.int32),
+    pad = lambda a: np.concatenate([a, np.full(B * L - len(a), ISENTINEL, np.int32)])  # noqa: E731
+    return dict(lens=p["lens"], cu=p["cu"], total=p["total"], order=p["order"] if B <= 1024 else np.full(B, ISENTINEL, np.int32),
                 tok_src=pad(p["tok_src"]), tok_pid=pad(p["tok_pid"]))
 
 
@@ -261,7 +262,7 @@ def test_each_wrong_packing_is_rejected(defect):
         ids, mask = tr.make_pack_case(kind, B, L, pad_id, 1, mask_kind)
         p = tr.pack(ids, mask, pad_id) if defect is None else wrong_pack(ids, mask, pad_id, defect)
         try:
-            tr.assert_pack(as_buffers(p, B, L), ids, mask, pad_id, f"B={B} L={L} {kind} {mask_kind}")
+            tr.assert_pack(as_buffers(p, B, L), ids, mask, pad_id, ISENTINEL, f"B={B} L={L} {kind} {mask_kind}")
         except AssertionError:
             rejected += 1
     assert (rejected == 0) if defect is None else rejected > 0, (defect, rejected)
