@@ -29,8 +29,20 @@
 //   5. p is rounded to fp16 ONLY as the MFMA operand of dV; dS is rounded to fp16 ONLY as the operand of dQ and dK.
 //   6. dQ, dK, dV accumulate in fp32 (MFMA; mode 3: dQ as fma chains, dK and dV single products); dQ and dK are multiplied by 1/8 (exact)
 //      and every output is rounded to fp16 once.
+//
+// Dropout (include/mdr_dropout.h: mdr_attention_dropout_forward, mdr_attention_dropout_backward; the mask function is csrc/mdr_dropout.h's).
+// attn_drop_fwd_kernel is the training forward, ctx = (p o m) V: the row pass with other operands. attn_grad_kernel<*, true> and
+// attn_grad_cls_kernel<true> are its backward: dP is multiplied by m right after it is formed, in all three places S and dP are recomputed,
+// and the dV operand is p * m; the mask is drawn again from (seed, site), never stored. The <*, false> instantiations are the kernels above,
+// bit for bit. Rounding points of the dropout kernels (tests/dropout_ref.py derives its bound from 1 - 8):
+//   1 - 6 as above: the forward computes s and lse (3. without the sum of e dP) and p (4.) with the instructions of the backward's sweeps.
+//   7. m is 0 or fp32(256 / (256 - T)). dP * m and Pd = p * m are fp32 products (a multiplication, never a select: 0 * Inf = NaN). Pd is
+//      rounded to fp16 ONLY as the MFMA operand of ctx (forward) and of dV (backward); mode 3 rounds fp16(p * m) likewise.
+//   8. ctx accumulates in fp32 (MFMA; mode 3: fma chains, four strided partial sums added in wave order) and is rounded to fp16 once.
+#include "mdr_dropout.h"
 #include "mdr_grad_common.h"
 #include "../../include/mdr_attention_grad.h"
+#include "../../include/mdr_dropout.h"
 
 namespace mdr {
 namespace {
@@ -127,11 +139,26 @@ __device__ __forceinline__ void ag_store(ag_f32x4 (&acc)[4], float scale, _Float
     }
 }
 
-// stats: [heads][stat_stride] (lse, delta) pairs, indexed by the token's row in the packed batch
+// mk[t][r] = the dropout factor of swept row c0 + 16 t + 4 g + r and `owner` (csrc/mdr_dropout.h): a lane's four consecutive swept rows of one
+// tile lie in one 4 x 4 block, so each tile costs one generator call. Row pass: owner = query, swept = keys; column pass: the reverse.
 template <bool COLPASS>
+__device__ __forceinline__ void ag_mask(int owner, int c0, int g, uint32_t bh, const DropoutParams& dpar, ag_f32x4 (&mk)[kAgTiles]) {
+#pragma unroll
+    for (int t = 0; t < kAgTiles; ++t) {
+        const int blk = (c0 >> 2) + 4 * t + g;
+        const uint32_t w = COLPASS ? dropout_attn_word_queries(blk, owner, bh, dpar) : dropout_attn_word_keys(owner, blk, bh, dpar);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mk[t][r] = dropout_factor(w, r, dpar);
+    }
+}
+
+// stats: [heads][stat_stride] (lse, delta) pairs, indexed by the token's row in the packed batch
+// DROP: the backward of the training forward below. dp is multiplied by the mask factor right after ag_tiles, wherever S and dP are recomputed,
+// and the dV operand is p * m; nothing else changes.
+template <bool COLPASS, bool DROP>
 __global__ void __launch_bounds__(kAgThreads)
 attn_grad_kernel(const _Float16* __restrict__ qkv, const _Float16* __restrict__ dctx, const int* __restrict__ cu, int H, size_t stat_stride,
-                 float2* __restrict__ stats, _Float16* __restrict__ dqkv) {
+                 float2* __restrict__ stats, _Float16* __restrict__ dqkv, DropoutParams dpar) {
     __shared__ __attribute__((aligned(128))) char img1[kAgImage];  // row pass: K rows; column pass: Q rows
     __shared__ __attribute__((aligned(128))) char img2[kAgImage];  // row pass: V rows; column pass: dO rows
     __shared__ __attribute__((aligned(16))) float2 st_s[kAgChunk];  // column pass: (lse, delta) of the chunk's queries
@@ -182,6 +209,12 @@ attn_grad_kernel(const _Float16* __restrict__ qkv, const _Float16* __restrict__ 
             if (!wave_valid) continue;
             ag_f32x4 s[kAgTiles], dp[kAgTiles];
             ag_tiles(img1, img2, x1, x2, lane, s, dp);
+            ag_f32x4 mk[kAgTiles];  // DROP: the factor of swept row 16 t + 4 g + r and this owner
+            if (DROP) {
+                ag_mask<COLPASS>(owner, c0, g, (uint32_t)b * gridDim.x + h, dpar, mk);
+#pragma unroll
+                for (int t = 0; t < kAgTiles; ++t) dp[t] *= mk[t];
+            }
             if (sweep == 0) {
                 float cmax = -INFINITY;
 #pragma unroll
@@ -225,7 +258,7 @@ attn_grad_kernel(const _Float16* __restrict__ qkv, const _Float16* __restrict__ 
                     for (int r = 0; r < 4; ++r) {
                         const bool live = c0 + 16 * t + 4 * g + r < len;
                         const float e = __builtin_amdgcn_exp2f((s[t][r] - (COLPASS ? ls[r] : lse)) * kLog2e);
-                        p[t][r] = live ? e : 0.f;
+                        p[t][r] = live ? (DROP ? e * mk[t][r] : e) : 0.f;
                         dsv[t][r] = live ? e * (dp[t][r] - (COLPASS ? dl[r] : delta)) : 0.f;
                     }
                 }
@@ -249,12 +282,21 @@ attn_grad_kernel(const _Float16* __restrict__ qkv, const _Float16* __restrict__ 
     }
 }
 
-// Mode 3: dctx is [B, H], the gradient of each sequence's first query alone.
+// the dropout factor of the first query and key `key` (mode 3: the attention site at i = 0)
+__device__ __forceinline__ float ag_cls_factor(int key, uint32_t bh, const DropoutParams& dpar) {
+    return dropout_factor(philox4x32_10(0u, (uint32_t)key >> 2, bh, dpar.site, dpar.k0, dpar.k1).x, key & 3, dpar);
+}
+
+// Mode 3: dctx is [B, H], the gradient of each sequence's first query alone. DROP: dP is multiplied by the mask factor where it is formed and
+// the dV operand is fp16(p * m).
+template <bool DROP>
 __global__ void __launch_bounds__(kAgClsThreads)
-attn_grad_cls_kernel(const _Float16* __restrict__ qkv, const _Float16* __restrict__ dctx, const int* __restrict__ cu, int H, _Float16* __restrict__ dqkv) {
+attn_grad_cls_kernel(const _Float16* __restrict__ qkv, const _Float16* __restrict__ dctx, const int* __restrict__ cu, int H, _Float16* __restrict__ dqkv,
+                     DropoutParams dpar) {
     constexpr int W = kAgClsThreads / 64;
     __shared__ float q_s[64], do_s[64];
-    __shared__ float s_s[512], dp_s[512];  // scores, then fp16(p); dP, then fp16(dS)
+    __shared__ float s_s[512], dp_s[512];  // scores, then fp16(p) (DROP: fp16(p m)); dP (DROP: dP m), then fp16(dS)
+    __shared__ float m_s[DROP ? 512 : 1];  // DROP: the keys' factors
     __shared__ float red[3][W];
     __shared__ float part[W][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -282,6 +324,11 @@ attn_grad_cls_kernel(const _Float16* __restrict__ qkv, const _Float16* __restric
             }
         }
         s *= 0.125f;
+        if (DROP) {
+            const float m = ag_cls_factor(key, (uint32_t)b * gridDim.x + h, dpar);
+            m_s[key] = m;
+            dp *= m;
+        }
         s_s[key] = s;
         dp_s[key] = dp;
         mx = fmaxf(mx, s);
@@ -311,7 +358,7 @@ attn_grad_cls_kernel(const _Float16* __restrict__ qkv, const _Float16* __restric
     const float delta = dsum * inv;
     for (int key = tid; key < len; key += kAgClsThreads) {  // (each thread revisits the keys it wrote)
         const float p = s_s[key] * inv;
-        s_s[key] = (float)(_Float16)p;
+        s_s[key] = (float)(_Float16)(DROP ? p * m_s[key] : p);
         dp_s[key] = (float)(_Float16)(p * (dp_s[key] - delta));
     }
     __syncthreads();
@@ -341,9 +388,208 @@ attn_grad_cls_kernel(const _Float16* __restrict__ qkv, const _Float16* __restric
     if (tid < 64) out[tid] = (_Float16)((((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid]) * 0.125f);
 }
 
+// a[t][r] = X . I / 8 for swept row 16 t + 4 g + r of the chunk and owner lr: the score half of ag_tiles
+__device__ __forceinline__ void ag_scores(const char* img, const ag_half8 (&x)[2], int lane, ag_f32x4 (&a)[kAgTiles]) {
+    const int g = lane >> 4, lr = lane & 15;
+    const int rd = lr * 128, sw0 = (g ^ (lr & 7)) << 4, sw1 = ((4 + g) ^ (lr & 7)) << 4;
+#pragma unroll
+    for (int t = 0; t < kAgTiles; ++t) {
+        const ag_half8 i0 = *(const ag_half8*)(img + t * 2048 + rd + sw0), i1 = *(const ag_half8*)(img + t * 2048 + rd + sw1);
+        ag_f32x4 s = {0.f, 0.f, 0.f, 0.f};
+        s = __builtin_amdgcn_mfma_f32_16x16x32_f16(i0, x[0], s, 0, 0, 0);
+        s = __builtin_amdgcn_mfma_f32_16x16x32_f16(i1, x[1], s, 0, 0, 0);
+        a[t] = s * 0.125f;
+    }
+    asm volatile("s_nop 7\n\ts_nop 7" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]));  // (see ag_tiles)
+}
+
+// The training forward (mdr_attention_dropout_forward, mode 0): the row pass with other operands. A workgroup owns 64 queries (Q rows in
+// registers) and sweeps the keys in chunks of 64 (K and V rows staged as in attn_grad_kernel). Sweep 0 folds the chunks into a running (max, sum)
+// per query: lse. Sweep 1 forms p = exp(s - lse) and Pd = p * m and accumulates ctx^T = V^T Pd^T on the staged V image. No probability goes
+// to memory, and the backward recomputes lse with the same instructions. Rounding points: the list at the top of the file.
+__global__ void __launch_bounds__(kAgThreads)
+attn_drop_fwd_kernel(const _Float16* __restrict__ qkv, const int* __restrict__ cu, int H, DropoutParams dpar, _Float16* __restrict__ ctx) {
+    __shared__ __attribute__((aligned(128))) char img1[kAgImage];  // K rows
+    __shared__ __attribute__((aligned(128))) char img2[kAgImage];  // V rows
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, lr = lane & 15;
+    const int h = blockIdx.x, b = blockIdx.y, o0 = blockIdx.z * kAgOwn;
+    const int start = cu[b], len = cu[b + 1] - start;
+    if (o0 >= len) return;
+    const size_t H3 = (size_t)3 * H;
+    const _Float16* seq = qkv + (size_t)start * H3 + h * 64;
+    const int owner = o0 + wave * 16 + lr;
+    const bool ovalid = owner < len;
+    const int orow = ovalid ? owner : len - 1;
+    const bool wave_valid = o0 + wave * 16 < len;
+    ag_half8 x[2];
+#pragma unroll
+    for (int ds = 0; ds < 2; ++ds) x[ds] = *(const ag_half8*)(seq + (size_t)orow * H3 + ds * 32 + g * 8);
+
+    ag_f32x4 acc[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) acc[dt] = (ag_f32x4){0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f, lse = 0.f;
+    const bool one_chunk = len <= kAgChunk;  // sweep 1 finds the only chunk staged
+
+    for (int sweep = 0; sweep < 2; ++sweep) {
+        for (int c0 = 0; c0 < len; c0 += kAgChunk) {
+            if (sweep == 0 || !one_chunk) {
+                __syncthreads();
+                ag_stage(seq + H, H3, c0, len, img1, tid);
+                if (sweep == 1 || one_chunk) ag_stage(seq + 2 * H, H3, c0, len, img2, tid);
+                __syncthreads();
+            }
+            if (!wave_valid) continue;
+            ag_f32x4 s[kAgTiles];
+            ag_scores(img1, x, lane, s);
+            if (sweep == 0) {
+                float cmax = -INFINITY;
+#pragma unroll
+                for (int t = 0; t < kAgTiles; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if (c0 + 16 * t + 4 * g + r >= len) s[t][r] = -INFINITY;
+                        cmax = fmaxf(cmax, s[t][r]);
+                    }
+                cmax = fmaxf(cmax, __shfl_xor(cmax, 16));
+                cmax = fmaxf(cmax, __shfl_xor(cmax, 32));
+                const float m_new = fmaxf(m_run, cmax);
+                const float alpha = exp2f((m_run - m_new) * kLog2e);
+                const float mb = -m_new * kLog2e;
+                float csum = 0.f;
+#pragma unroll
+                for (int t = 0; t < kAgTiles; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) csum += __builtin_amdgcn_exp2f(fmaf(s[t][r], kLog2e, mb));
+                csum += __shfl_xor(csum, 16);
+                csum += __shfl_xor(csum, 32);
+                l_run = l_run * alpha + csum;
+                m_run = m_new;
+            } else {
+                ag_f32x4 mk[kAgTiles], pd[kAgTiles];
+                ag_mask<false>(owner, c0, g, (uint32_t)b * gridDim.x + h, dpar, mk);
+#pragma unroll
+                for (int t = 0; t < kAgTiles; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const bool live = c0 + 16 * t + 4 * g + r < len;
+                        const float e = __builtin_amdgcn_exp2f((s[t][r] - lse) * kLog2e);
+                        pd[t][r] = live ? e * mk[t][r] : 0.f;
+                    }
+                ag_accumulate(img2, pd, lane, acc);
+            }
+        }
+        if (sweep == 0) lse = m_run + logf(l_run);
+    }
+    if (!ovalid) return;
+    ag_store(acc, 1.f, ctx + (size_t)(start + owner) * H + h * 64, g);
+}
+
+// The training forward, mode 3: ctx is [B, H], the first query of each sequence. One workgroup per (sequence, head), shaped like
+// attn_grad_cls_kernel: scores of the one query, softmax against the true maximum, fp16(p * m), then the context as four strided partial sums
+// added in wave order.
+__global__ void __launch_bounds__(kAgClsThreads)
+attn_drop_fwd_cls_kernel(const _Float16* __restrict__ qkv, const int* __restrict__ cu, int H, DropoutParams dpar, _Float16* __restrict__ ctx) {
+    constexpr int W = kAgClsThreads / 64;
+    __shared__ float q_s[64];
+    __shared__ float s_s[512];  // scores, then e, then fp16(p m)
+    __shared__ float red[2][W];
+    __shared__ float part[W][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = blockIdx.x, b = blockIdx.y;
+    const int start = cu[b], len = cu[b + 1] - start;
+    if (len <= 0) return;
+    const size_t H3 = (size_t)3 * H;
+    const _Float16* seq = qkv + (size_t)start * H3 + h * 64;
+    if (tid < 64) q_s[tid] = (float)seq[tid];
+    __syncthreads();
+    float mx = -INFINITY;
+    for (int key = tid; key < len; key += kAgClsThreads) {
+        const _Float16* kp = seq + (size_t)key * H3 + H;
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const ag_half8 kv = *(const ag_half8*)(kp + c * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s = fmaf((float)kv[j], q_s[c * 8 + j], s);
+        }
+        s *= 0.125f;
+        s_s[key] = s;
+        mx = fmaxf(mx, s);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if (lane == 0) red[0][wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+    float sum = 0.f;
+    for (int key = tid; key < len; key += kAgClsThreads) {
+        const float e = exp2f((s_s[key] - mx) * kLog2e);
+        s_s[key] = e;
+        sum += e;
+    }
+    sum = grad_wave_sum(sum);
+    if (lane == 0) red[1][wave] = sum;
+    __syncthreads();
+    sum = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+    const float inv = 1.f / sum;
+    for (int key = tid; key < len; key += kAgClsThreads)  // (each thread revisits the keys it wrote)
+        s_s[key] = (float)(_Float16)(s_s[key] * inv * ag_cls_factor(key, (uint32_t)b * gridDim.x + h, dpar));
+    __syncthreads();
+    // wave w adds keys w, w + 4, ... in key order, then the four partial sums are added in wave order
+    float acc = 0.f;
+    const _Float16* vcol = seq + 2 * H + lane;
+    for (int j = wave; j < len; j += W) acc = fmaf(s_s[j], (float)vcol[(size_t)j * H3], acc);
+    part[wave][lane] = acc;
+    __syncthreads();
+    if (tid < 64) ctx[(size_t)b * H + h * 64 + tid] = (_Float16)(((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid]);
+}
+
 bool ag_shape_ok(int B, int L, int heads, int mode) { return B >= 1 && L >= 1 && L <= 512 && heads >= 1 && heads <= 65535 && (mode == 0 || mode == 3); }
 
 size_t ag_need(int B, int L, int heads, int mode) { return mode == 0 ? (size_t)B * L * heads * sizeof(float2) : 0; }
+
+// what mdr_attention_backward, mdr_attention_dropout_forward and mdr_attention_dropout_backward refuse alike
+int ag_check_shape(const char* fn, int B, int L, int hidden, int heads, int mode) {
+    MDR_REQUIRE(B >= 1 && B <= 65535, "%s: B=%d out of range (1..65535)", fn, B);
+    MDR_REQUIRE(L >= 1 && L <= 512, "%s: L=%d out of range (1..512)", fn, L);
+    MDR_REQUIRE(heads >= 1 && heads <= 65535 && hidden == 64 * heads, "%s: head dim must be 64 (hidden=%d heads=%d)", fn, hidden, heads);
+    MDR_REQUIRE(mode == 0 || mode == 3, "%s: mode must be 0 (every query) or 3 (first query of each sequence), got %d", fn, mode);
+    return MDR_OK;
+}
+
+// the backward's validation and launches; DROP: with the mask of `dpar` replayed
+template <bool DROP>
+int ag_backward(const char* fn, const void* qkv_dev, const void* dctx_dev, const int* cu_dev, int B, int L, int hidden, int heads, int mode,
+                const DropoutParams& dpar, void* dqkv_dev, void* workspace_dev, size_t workspace_bytes, int device, void* stream) {
+    MDR_REQUIRE(qkv_dev && dctx_dev && cu_dev && dqkv_dev, "%s: NULL pointer (qkv, dctx, cu and dqkv are required)", fn);
+    if (const int rc = ag_check_shape(fn, B, L, hidden, heads, mode)) return rc;
+    MDR_REQUIRE(aligned16({qkv_dev, dctx_dev, dqkv_dev, workspace_dev}), "%s: qkv, dctx, dqkv and the workspace must be 16-byte aligned", fn);
+    const size_t need = ag_need(B, L, heads, mode);
+    MDR_REQUIRE_WORKSPACE(fn, workspace_dev, workspace_bytes, need, "mdr_attention_backward_workspace_bytes");
+    MDR_ENTER_DEVICE(device);
+    const _Float16* qkv = (const _Float16*)qkv_dev;
+    const _Float16* dctx = (const _Float16*)dctx_dev;
+    _Float16* dqkv = (_Float16*)dqkv_dev;
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == 3) {
+        hipLaunchKernelGGL(attn_grad_cls_kernel<DROP>, dim3(heads, B), dim3(kAgClsThreads), 0, st, qkv, dctx, cu_dev, hidden, dqkv, dpar);
+        MDR_HIP_TRY(hipGetLastError());
+        return MDR_OK;
+    }
+    // the row pass writes (lse, delta), the column pass reads them: stream order
+    const dim3 grid(heads, B, (L + kAgOwn - 1) / kAgOwn);
+    const size_t stat_stride = (size_t)B * L;
+    hipLaunchKernelGGL((attn_grad_kernel<false, DROP>), grid, dim3(kAgThreads), 0, st, qkv, dctx, cu_dev, hidden, stat_stride, (float2*)workspace_dev, dqkv,
+                       dpar);
+    MDR_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((attn_grad_kernel<true, DROP>), grid, dim3(kAgThreads), 0, st, qkv, dctx, cu_dev, hidden, stat_stride, (float2*)workspace_dev, dqkv,
+                       dpar);
+    MDR_HIP_TRY(hipGetLastError());
+    return MDR_OK;
+}
 
 }  // namespace
 }  // namespace mdr
@@ -358,32 +604,36 @@ size_t mdr_attention_backward_workspace_bytes(int B, int L, int heads, int mode)
 
 int mdr_attention_backward(const void* qkv_dev, const void* dctx_dev, const int* cu_dev, int B, int L, int hidden, int heads, int mode, void* dqkv_dev,
                            void* workspace_dev, size_t workspace_bytes, int device, void* stream) {
+    return mdr::ag_backward<false>("mdr_attention_backward", qkv_dev, dctx_dev, cu_dev, B, L, hidden, heads, mode, mdr::DropoutParams{}, dqkv_dev, workspace_dev,
+                                   workspace_bytes, device, stream);
+}
+
+int mdr_attention_dropout_backward(const void* qkv_dev, const void* dctx_dev, const int* cu_dev, int B, int L, int hidden, int heads, int mode, int T,
+                                   uint64_t seed, uint32_t site, void* dqkv_dev, void* workspace_dev, size_t workspace_bytes, int device, void* stream) {
     using namespace mdr;
-    const char* fn = "mdr_attention_backward";
-    MDR_REQUIRE(qkv_dev && dctx_dev && cu_dev && dqkv_dev, "%s: NULL pointer (qkv, dctx, cu and dqkv are required)", fn);
-    MDR_REQUIRE(B >= 1 && B <= 65535, "%s: B=%d out of range (1..65535)", fn, B);
-    MDR_REQUIRE(L >= 1 && L <= 512, "%s: L=%d out of range (1..512)", fn, L);
-    MDR_REQUIRE(heads >= 1 && heads <= 65535 && hidden == 64 * heads, "%s: head dim must be 64 (hidden=%d heads=%d)", fn, hidden, heads);
-    MDR_REQUIRE(mode == 0 || mode == 3, "%s: mode must be 0 (every query) or 3 (first query of each sequence), got %d", fn, mode);
-    MDR_REQUIRE(aligned16({qkv_dev, dctx_dev, dqkv_dev, workspace_dev}), "%s: qkv, dctx, dqkv and the workspace must be 16-byte aligned", fn);
-    const size_t need = ag_need(B, L, heads, mode);
-    MDR_REQUIRE_WORKSPACE(fn, workspace_dev, workspace_bytes, need, "mdr_attention_backward_workspace_bytes");
+    const char* fn = "mdr_attention_dropout_backward";
+    MDR_REQUIRE(T >= 1 && T <= 255, "%s: T=%d out of range (1..255; without dropout the call is mdr_attention_backward)", fn, T);
+    return ag_backward<true>(fn, qkv_dev, dctx_dev, cu_dev, B, L, hidden, heads, mode, dropout_params((unsigned)T, seed, site), dqkv_dev, workspace_dev,
+                             workspace_bytes, device, stream);
+}
+
+int mdr_attention_dropout_forward(const void* qkv_dev, const int* cu_dev, int B, int L, int hidden, int heads, int mode, int T, uint64_t seed,
+                                  uint32_t site, void* ctx_dev, int device, void* stream) {
+    using namespace mdr;
+    const char* fn = "mdr_attention_dropout_forward";
+    MDR_REQUIRE(qkv_dev && cu_dev && ctx_dev, "%s: NULL pointer (qkv, cu and ctx are required)", fn);
+    if (const int rc = ag_check_shape(fn, B, L, hidden, heads, mode)) return rc;
+    MDR_REQUIRE(T >= 1 && T <= 255, "%s: T=%d out of range (1..255; without dropout the forward is the encoder's own)", fn, T);
+    MDR_REQUIRE(aligned16({qkv_dev, ctx_dev}), "%s: qkv and ctx must be 16-byte aligned", fn);
     MDR_ENTER_DEVICE(device);
-    const _Float16* qkv = (const _Float16*)qkv_dev;
-    const _Float16* dctx = (const _Float16*)dctx_dev;
-    _Float16* dqkv = (_Float16*)dqkv_dev;
+    const DropoutParams dpar = dropout_params((unsigned)T, seed, site);
     hipStream_t st = (hipStream_t)stream;
-    if (mode == 3) {
-        hipLaunchKernelGGL(attn_grad_cls_kernel, dim3(heads, B), dim3(kAgClsThreads), 0, st, qkv, dctx, cu_dev, hidden, dqkv);
-        MDR_HIP_TRY(hipGetLastError());
-        return MDR_OK;
-    }
-    // the row pass writes (lse, delta), the column pass reads them: stream order
-    const dim3 grid(heads, B, (L + kAgOwn - 1) / kAgOwn);
-    const size_t stat_stride = (size_t)B * L;
-    hipLaunchKernelGGL(attn_grad_kernel<false>, grid, dim3(kAgThreads), 0, st, qkv, dctx, cu_dev, hidden, stat_stride, (float2*)workspace_dev, dqkv);
-    MDR_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(attn_grad_kernel<true>, grid, dim3(kAgThreads), 0, st, qkv, dctx, cu_dev, hidden, stat_stride, (float2*)workspace_dev, dqkv);
+    if (mode == 3)
+        hipLaunchKernelGGL(attn_drop_fwd_cls_kernel, dim3(heads, B), dim3(kAgClsThreads), 0, st, (const _Float16*)qkv_dev, cu_dev, hidden, dpar,
+                           (_Float16*)ctx_dev);
+    else
+        hipLaunchKernelGGL(attn_drop_fwd_kernel, dim3(heads, B, (L + kAgOwn - 1) / kAgOwn), dim3(kAgThreads), 0, st, (const _Float16*)qkv_dev, cu_dev, hidden,
+                           dpar, (_Float16*)ctx_dev);
     MDR_HIP_TRY(hipGetLastError());
     return MDR_OK;
 }

@@ -9,8 +9,8 @@ H a multiple of 64, at most 1024. The forward is the encoder's own kernel (flavo
 are the encoder's; rows at or behind total stay zero. The backward is mdr_embedding_backward (include/mdr_embedding_grad.h;
 csrc/mdr_embedding_grad.hip lists its rounding points) on a plan built at forward time (mdr_embedding_plan): dense fp32 gradients for word,
 pos, type0, weight and bias, no floating-point atomics, two runs give the same bits. pad_row is Hugging Face's padding_idx: that row of both
-tables gets no gradient (-1: no such row). Everything is enqueued on the current stream and never synchronises. There is no dropout and no
-CPU fallback.
+tables gets no gradient (-1: no such row). Everything is enqueued on the current stream and never synchronises. The hidden dropout behind
+this LayerNorm is a call of its own, dropout.packed_dropout(y32, p, seed, site, rows=total, also16=True). There is no CPU fallback.
 """
 import ctypes
 

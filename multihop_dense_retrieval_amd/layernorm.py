@@ -9,7 +9,8 @@ encoder's. y16 is the fp16 operand of the next Linear, y32 the same value unroun
 mdr_layernorm_backward (include/mdr_layernorm_grad.h; csrc/mdr_layernorm_grad.hip lists its rounding points): the gradient of y16 goes in as
 dy16 and that of y32 as the fp32 dy2, x and residual each get dx in their own dtype, weight and bias get dg and db in fp32; no atomics, two
 runs give the same bits. Nothing is saved but the inputs: the backward recomputes the statistics. Both directions are enqueued on the
-current stream and never synchronise. There is no dropout and no CPU fallback.
+current stream and never synchronise. The hidden dropout in front of a residual LayerNorm is a call of its own (dropout.packed_dropout on the
+Linear's output). There is no CPU fallback.
 """
 import ctypes
 
