@@ -12,7 +12,9 @@ exact in expectation for the rate drawn. The factor is applied as a multiplicati
 torch's x * mask does.
 
 Nothing is saved for the backward but (T, seed, site) and rows: the backward is the same call on the gradient and draws the same mask. With
-also16 the input's gradient is the mask times (g32 + fp32(g16)). A p with T = 0 returns x itself without a launch (also16: one launch, for y16).
+also16 the input's gradient is the mask times (g32 + fp32(g16)). A p with T = 0 returns x itself without a launch (also16: one launch, for y16). That
+y16 is fp16(y32), a second rounding: embedding.packed_embedding_layer_norm's own fp16 copy is one rounding of the unrounded value and differs from it
+by an fp16 ulp where y32 sits exactly between two fp16 values, so a caller whose T is 0 keeps the embedding's pair and makes no call.
 
 Uniqueness is the CALLER's duty: every use -- every step, encode, layer and place -- needs its own site or seed; two uses that share
 (seed, site) share their mask. The attention probabilities' dropout is attention.packed_self_attention(..., dropout=(p, seed, site)).

@@ -142,6 +142,19 @@ def child(root):
     for mode in (0, 3):
         put(f"overflow_ref attention mode={mode}", overflow_ref.attention_case(mode))
     put("overflow_ref loss", overflow_ref.loss_case())
+
+    # the whole-encoder references WITHOUT dropout (their fp64 arithmetic repeats its bits; regime_b's fp32 index backward does not)
+    import encoder_chain_ref as ch
+    from oracle import seeded
+    for gn, geom in (("TINY", seeded.TINY), ("DEEP", seeded.DEEP)):
+        sd = ch.state_dict(geom)
+        ids, mask = ch.batch("L48", geom)
+        G = ch.cotangent(len(ids), geom)
+        put(f"encoder_chain_ref {gn} L48 model64", ch.grads_cotangent("model64", sd, geom, ids, mask, G))
+        for scale in (1.0, 256.0):
+            put(f"encoder_chain_ref {gn} L48 regime scale={scale:g}", ch.grads_cotangent("regime", sd, geom, ids, mask, G, scale))
+    for kind in ("model64", "regime"):
+        put(f"encoder_chain_ref TINY loss {kind}", ch.grads_loss(kind, ch.state_dict(seeded.TINY), seeded.TINY, ch.loss_batches(seeded.TINY)))
     print(json.dumps(out, sort_keys=True))
 
 

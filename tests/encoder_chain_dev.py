@@ -1,4 +1,4 @@
-"""The device side that tests/test_encoder_chain_gpu.py and tests/test_overflow_chain_gpu.py share: the retriever encoder as ONE chain of the
+"""The device side that tests/test_encoder_chain_gpu.py, tests/test_encoder_chain_dropout_gpu.py and tests/test_overflow_chain_gpu.py share: the retriever encoder as ONE chain of the
 package's differentiable functions (Chain, with a tape of every call and a hook on every output), its leaves (params), the NaN seeding of the
 caching allocator (poison), the bit comparisons, and criterion E's assertion (check_e). The host side is tests/encoder_chain_ref.py.
 Chain, params, poison and check_e take the geometry (oracle.seeded.TINY or DEEP); the default is TINY."""
@@ -36,7 +36,10 @@ def poison(mib=64, geom=GEOM):
     """allocate, fill with NaN bit patterns and free blocks of the sizes the chain's torch.empty calls ask for (and many more): the caching
     allocator hands them out again, so a read of an unwritten row shows as a NaN. Then every block the allocator still holds free -- what
     earlier tests freed, the splinters between live tensors, the rest of the segments opened here -- is asked for by its exact size and
-    filled too, so that no unseeded block is left for the allocator to prefer, however much ran before. Nothing here can fault."""
+    filled too, so that no unseeded block is left for the allocator to prefer, however much ran before. The first lot is FREED before that
+    second step: a request above 1 MiB that meets a free block up to 1 MiB larger is handed the whole block unsplit, and the fill writes only
+    what was asked for -- held, such a block hides its unwritten rest; freed, it is one of the blocks asked for by their exact size.
+    Nothing here can fault."""
     torch.cuda.synchronize()
     torch.cuda.empty_cache()  # whole free segments go back to the driver: what remains free lies inside segments with live tensors
     held, total = [], 0
@@ -51,6 +54,8 @@ def poison(mib=64, geom=GEOM):
         for n in (512, 4096, 65536, 1 << 20, 4 << 20):
             held.append(torch.full((n,), 0xFF, dtype=torch.uint8, device="cuda"))
             total += n
+    torch.cuda.synchronize()
+    held = []
     for _ in range(8):  # a block of a small segment above 1 MiB takes two requests, a new segment's rest another pass
         free = sorted((b["size"], seg["segment_type"]) for seg in torch.cuda.memory_snapshot() for b in seg["blocks"] if b["state"] == "inactive")
         if not free:
@@ -63,15 +68,24 @@ def poison(mib=64, geom=GEOM):
 
 class Chain:
     """one encode through the public functions, with a tape of every call and hooks on every output. half: None, or a function from a weight
-    leaf to the fp16 copy that every Linear is handed as weight16 (optim.FusedAdam.half). geom: the geometry P was made for"""
+    leaf to the fp16 copy that every Linear is handed as weight16 (optim.FusedAdam.half). geom: the geometry P was made for.
+    dropout: None (the graph is the one without any dropout call), or (p, seed, encode): the reference's training dropout, every call at the
+    site ch.site_of(encode, layer, place) -- packed_dropout(y32, ..., rows=total, also16=True) behind the embedding (the embedding's own fp16
+    copy then has no consumer), dropout=(p, seed, site) on both attention forms, packed_dropout on a Linear's output in front of both
+    residual LayerNorms (rows = None in the CLS tail: the mask's row index is the sequence index). Each call is on the tape as kind "drop"
+    (a call whose threshold is 0 hands its input back and is not taped: there is nothing between the two stages). With a threshold of 0 the
+    embedding's call is NOT made and the embedding's own fp16 copy is used: that copy is the kernel's single rounding of the unrounded value,
+    fp16(y32) is a second rounding of the fp32 one, and the two differ by an fp16 ulp where y32 sits exactly between two fp16 values (a
+    handful of elements per batch; tests/test_encoder_chain_dropout_gpu.py holds both facts)."""
 
-    def __init__(self, P, ids, mask, half=None, geom=GEOM):
+    def __init__(self, P, ids, mask, half=None, geom=GEOM, dropout=None):
         from multihop_dense_retrieval_amd import _lib
+        from multihop_dense_retrieval_amd import dropout as _dropout
         from multihop_dense_retrieval_amd.attention import packed_self_attention
         from multihop_dense_retrieval_amd.embedding import packed_embedding_layer_norm
         from multihop_dense_retrieval_amd.layernorm import packed_layer_norm
         from multihop_dense_retrieval_amd.linear import packed_linear
-        self.tape, self.P, self.geom = [], P, geom
+        self.tape, self.P, self.geom, self.dropout = [], P, geom, dropout
         NH, EPS, PAD = geom["heads"], geom["ln_eps"], geom["pad_id"]
         self.ids_np, self.mask_np = ids, mask
         B, L = ids.shape
@@ -100,30 +114,51 @@ class Chain:
             self._rec("ln", label, {"x": x, "res": res}, {"y16": y16, "y32": y32}, rows=rows, name_=name)
             return y16, y32
 
-        def attn(qkv, cls_only, label):
-            ctx = packed_self_attention(qkv, cu, NH, L, cls_only)
-            self._rec("attn", label, {"qkv": qkv}, {"ctx": ctx}, mode=3 if cls_only else 0)
+        def attn(qkv, cls_only, label, i):
+            if dropout is None:
+                ctx = packed_self_attention(qkv, cu, NH, L, cls_only)
+                self._rec("attn", label, {"qkv": qkv}, {"ctx": ctx}, mode=3 if cls_only else 0)
+                return ctx
+            p_, seed, enc = dropout
+            site = ch.site_of(enc, i, "attn")
+            ctx = packed_self_attention(qkv, cu, NH, L, cls_only, dropout=(p_, seed, site))
+            T = _dropout.threshold(p_)
+            self._rec("attn", label, {"qkv": qkv}, {"ctx": ctx}, mode=3 if cls_only else 0, drop=(T, seed, site) if T else None)
             return ctx
 
-        def tail(p, ctx, res32, rows, lab):
-            a16, a32 = ln(linear(ctx, [p + "attention.output.dense"], False, rows, lab + ".ao"), res32, p + "attention.output.LayerNorm", rows, lab + ".ln1")
+        def drop(x, i, place, rows, label, also16=False):
+            """x, or with also16 (y32, y16), through the hidden dropout of site_of(encode, i, place)"""
+            if dropout is None:
+                return x
+            p_, seed, enc = dropout
+            site = ch.site_of(enc, i, place)
+            y = _dropout.packed_dropout(x, p_, seed, site, rows, also16)
+            if y is not x:
+                self._rec("drop", label, {"x": x}, {"y32": y[0], "y16": y[1]} if also16 else {"y": y}, rows=rows, drop=(_dropout.threshold(p_), seed, site))
+            return y
+
+        def tail(p, ctx, res32, rows, lab, i):
+            ao = drop(linear(ctx, [p + "attention.output.dense"], False, rows, lab + ".ao"), i, "ao", rows, lab + ".ao.drop")
+            a16, a32 = ln(ao, res32, p + "attention.output.LayerNorm", rows, lab + ".ln1")
             f2 = linear(linear(a16, [p + "intermediate.dense"], True, rows, lab + ".ff1"), [p + "output.dense"], False, rows, lab + ".ff2")
-            return ln(f2, a32, p + "output.LayerNorm", rows, lab + ".ln2")
+            return ln(drop(f2, i, "ff2", rows, lab + ".ff2.drop"), a32, p + "output.LayerNorm", rows, lab + ".ln2")
 
         h16, h32 = packed_embedding_layer_norm(tids, src, pid, total, P[E_ + "word_embeddings.weight"], P[E_ + "position_embeddings.weight"],
                                                P[E_ + "token_type_embeddings.weight"][0], P[E_ + "LayerNorm.weight"], P[E_ + "LayerNorm.bias"], EPS,
                                                self.cap, PAD, True)
         self._rec("emb", "emb", {}, {"y16": h16, "y32": h32})
+        if dropout is not None and _dropout.threshold(dropout[0]):
+            h32, h16 = drop(h32, 0, "emb", total, "emb.drop", also16=True)
         nl = geom["layers"]
         for i in range(nl):
             p, lab = f"encoder.encoder.layer.{i}.", f"L{i}"
             qkv = linear(h16, [p + "attention.self." + n for n in ("query", "key", "value")], False, total, lab + ".qkv")
             if i < nl - 1:
-                h16, h32 = tail(p, attn(qkv, False, lab + ".attn"), h32, total, lab)
+                h16, h32 = tail(p, attn(qkv, False, lab + ".attn", i), h32, total, lab, i)
             else:  # the CLS rows alone; their fp16 copy (h16[starts]) has no consumer in this mode
                 cls32 = h32[self.starts]
                 self._rec("gather", lab + ".cls", {"src32": h32}, {"cls32": cls32})
-                h16, h32 = tail(p, attn(qkv, True, lab + ".attn"), cls32, None, lab)
+                h16, h32 = tail(p, attn(qkv, True, lab + ".attn", i), cls32, None, lab, i)
         y = linear(h16, ["project.0"], False, None, "project.0")
         out16, out = packed_layer_norm(y, None, P["project.1.weight"], P["project.1.bias"], EPS, None, True)
         self._rec("ln", "project.1", {"x": y, "res": None}, {"y16": out16, "y32": out}, rows=None, name_="project.1")

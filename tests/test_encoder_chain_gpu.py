@@ -36,6 +36,7 @@ import pytest
 import torch
 
 import attention_grad_ref as aref
+import dropout_ref as dref
 import embedding_grad_ref as eref
 import encoder_chain_ref as ch
 import layernorm_grad_ref as nref
@@ -68,7 +69,7 @@ def _f32(shape):
 
 def rerun(c, rec):
     """-> (device results, {input key: dx}, {param name: gradient}, {output: share of the bound}); asserts the bound"""
-    from multihop_dense_retrieval_amd import attention, embedding, layernorm, linear
+    from multihop_dense_retrieval_amd import attention, dropout, embedding, layernorm, linear
     kind, lab, g = rec["kind"], rec["label"], rec["g"]
     P, geom = c.P, c.geom
     H, NH, EPS, PAD = geom["hidden"], geom["heads"], geom["ln_eps"], geom["pad_id"]
@@ -117,15 +118,54 @@ def rerun(c, rec):
     elif kind == "attn":
         qkv, mode = rec["ins"]["qkv"].detach(), rec["mode"]
         dctx = g["ctx"].to(torch.float16).contiguous()
-        dq = attention.attention_backward(qkv, dctx, c.cu, NH, c.L, mode)
         cu = _np(c.cu)
         d_np = _np(dctx) if mode == 3 else _np(dctx)[:c.T]
-        ratio("dqkv", _np(dq)[:c.T], *aref.reference_and_bound(_np(qkv)[:c.T], d_np, cu, NH, mode))
+        if rec.get("drop") is None:
+            dq = attention.attention_backward(qkv, dctx, c.cu, NH, c.L, mode)
+            ratio("dqkv", _np(dq)[:c.T], *aref.reference_and_bound(_np(qkv)[:c.T], d_np, cu, NH, mode))
+        else:  # the training forward too: the chain is the first place it runs at these shapes
+            dq = attention.attention_dropout_backward(qkv, dctx, c.cu, NH, c.L, mode, *rec["drop"])
+            ctx_r, ctx_b, dq_r, dq_b = dref.reference_and_bound(_np(qkv)[:c.T], d_np, cu, NH, mode, dref.attn_masks(cu, NH, mode, *rec["drop"]))
+            ctx = _np(rec["outs"]["ctx"])
+            ratio("ctx", ctx if mode == 3 else ctx[:c.T], ctx_r, ctx_b)
+            ratio("dqkv", _np(dq)[:c.T], dq_r, dq_b)
         res = ({"dqkv": dq}, {"qkv": dq}, {})
+    elif kind == "drop":  # bits, both directions: x * m in numpy from the replica's mask; nothing written at or behind the valid count
+        x, rows, (T, seed, site) = rec["ins"]["x"].detach(), rec["rows"], rec["drop"]
+        M, N = x.shape
+        valid = c.T if rows is not None else M
+        m = np.where(dref.hidden_keep(M, N, T, seed, site), dref.scale(T), np.float32(0))
+        also16 = "y32" in rec["outs"]
+        y = _np(rec["outs"]["y32" if also16 else "y"])
+        want = (_np(x).astype(np.float32) * m).astype(y.dtype)
+        same = [np.array_equal(fp.bits(y[:valid]), fp.bits(want[:valid])), not fp.bits(y[valid:]).any()]
+        g32 = g.get("y32" if also16 else "y")
+        g16 = g.get("y16")
+        assert g32 is not None or g16 is not None, (lab, "no gradient reached a dropout's output")
+        if also16:
+            y16 = _np(rec["outs"]["y16"])
+            same += [np.array_equal(fp.bits(y16[:valid]), fp.bits(want[:valid].astype(np.float16))), not fp.bits(y16[valid:]).any()]
+            gz = torch.zeros(x.shape, dtype=torch.float32, device="cuda") if g32 is None else g32.contiguous()
+            a16 = None if g16 is None else g16.to(torch.float16).contiguous()
+            dx = dropout.dropout_rows(gz, T, seed, site, rows, a16, False)
+            want_dx = (_np(gz) + (0 if a16 is None else _np(a16).astype(np.float32))) * m
+        else:
+            gz = g32.to(x.dtype).contiguous()
+            dx = dropout.dropout_rows(gz, T, seed, site, rows, None, False)
+            want_dx = (_np(gz).astype(np.float32) * m).astype(_np(gz).dtype)
+        same += [np.array_equal(fp.bits(_np(dx)[:valid]), fp.bits(want_dx[:valid])), not fp.bits(_np(dx)[valid:]).any()]
+        dropped = float((m[:valid] == 0).mean())
+        shares.update(dropped=dropped, bits_equal=all(same))
+        if not all(same):
+            fails.append(f"y, rows behind the count of y, (y16, its rows,) dx, rows behind the count of dx -- bit-equal: {same}")
+        if T and not 0.0 < dropped < 1.0:
+            fails.append("the mask keeps or drops everything")
+        res = ({"dx": dx}, {"x": dx}, {})
     elif kind == "emb":
         names = [E_ + n for n in ("word_embeddings.weight", "position_embeddings.weight", "token_type_embeddings.weight", "LayerNorm.weight", "LayerNorm.bias")]
         word, pos, typ, wt = (P[n].detach() for n in names[:4])
-        dy16, dy2 = g["y16"].to(torch.float16).contiguous(), g["y32"].to(torch.float32).contiguous()
+        # (with dropout behind it the embedding's own fp16 copy has no consumer: dy16 is None, the other branch of the backward)
+        dy16, dy2 = None if "y16" not in g else g["y16"].to(torch.float16).contiguous(), g["y32"].to(torch.float32).contiguous()
         plan = embedding.embedding_plan(c.ids, c.src, c.pid, c.total, c.cap, geom["vocab"], geom["max_pos"], PAD)
         outs = [_f32(word.shape), _f32(pos.shape), _f32((H,)), _f32((H,)), _f32((H,)), torch.zeros((c.cap, H), dtype=torch.float32, device="cuda")]
         embedding.embedding_backward(c.ids, c.src, c.pid, c.total, c.cap, word, pos, typ[0], wt, EPS, dy16, dy2, plan, *outs)
@@ -173,8 +213,11 @@ def check_wiring(c, st, param_grads_used_once=True):
             assert same_bits(hooked[:m], dx[:m]), (rec["label"], k, "<-", r2["label"], k2)
             n += 1
     # every output but the last LayerNorm's fp32 one and the head's has one consumer: 2 of the embedding, 9 of a full layer, 10 of the last
-    # layer with the gather and project.0 (21 on two layers)
-    assert n == 9 * c.geom["layers"] + 3, n
+    # layer with the gather and project.0 (21 on two layers). With dropout: two more outputs per layer (the dropped copies of both Linears'
+    # outputs) and one more of the embedding (its y32 and the dropout's pair, its own y16 having lost its consumer)
+    taped_drops = sum(r["kind"] == "drop" for r in c.tape)
+    assert taped_drops == (0 if c.dropout is None else 2 * c.geom["layers"] + 1), taped_drops
+    assert n == 9 * c.geom["layers"] + 3 + taped_drops, n
     if param_grads_used_once:
         seen = set()
         for lab, (_, _, pg, _) in st.items():
