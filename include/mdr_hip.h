@@ -238,6 +238,16 @@ int mdr_test_gemm_f16(const void* A_dev, const void* W_dev, const float* bias_de
 int mdr_test_gemm_ex(const void* A_dev, const void* W_dev, const float* bias_dev, const void* res16_dev, int M, int M_est, const int* m_dev,
                      int N, int K, void* out_dev, int epilogue, int kernel, int* res_added_host, int device, void* stream);
 /* ------------------------------------------------------------------------------------------------
+ * Test hook: the kernel mdr_test_gemm_ex(kernel, M, M_est, N, K, epilogue) runs on a device of num_cus (>= 8) compute units -- the answer of the one
+ * function the encoder's GEMM launcher switches on, so a test that has to know the kernel asks instead of restating the choice. Host integers only:
+ * no device, no stream, no global state, the same answers on a machine without a GPU. Arguments are checked as by mdr_test_gemm_ex (MDR_E_INVALID).
+ * kernel_out: 1 = 64x64, 2 = 128x128, 4 = persistent 256x128, 6 / 7 = persistent 256x256 on eight / four waves. res_added_out: 1 for 1 and 2, else 0.
+ * walk_row_tiles_out: the row tiles of 256 the persistent walk covers when M_est rows are valid -- all ceil(M_est / 256) of them for 4; for 6 and 7 those
+ * that fill complete rounds of the num_cus / 8 * 8 workgroups (the rows behind them go to 128x128 tail tiles); 0 for 1 and 2. Any out pointer may be NULL.
+ * ---------------------------------------------------------------------------------------------- */
+int mdr_test_gemm_choice(int kernel, int M, int M_est, int N, int K, int epilogue, int num_cus, int* kernel_out, int* res_added_out,
+                         int* walk_row_tiles_out);
+/* ------------------------------------------------------------------------------------------------
  * Test hook: one attention call in isolation, ctx = softmax(Q K^T / 8) V per (sequence, head) -- the self-attention inside
  * HF RobertaModel / ElectraModel layers, on packed rows. qkv: f16 device [T, 3*hidden], each token's row is Q | K | V;
  * cu: int32 device [B + 1], cu[0] = 0, cu[B] = T (sequence b owns rows cu[b] .. cu[b+1]-1); order: int32 device [B], a

@@ -68,6 +68,7 @@ _SIGNATURES = {
                                      _c.c_int, _c.c_int, _c.c_void_p]),
     "mdr_test_gemm_ex": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int,
                                     _c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.c_int, _c.c_void_p]),
+    "mdr_test_gemm_choice": (_c.c_int, [_c.c_int] * 7 + [_c.POINTER(_c.c_int)] * 3),
     "mdr_test_attention": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
                                       _c.c_int, _c.c_void_p]),
     "mdr_test_pack": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,

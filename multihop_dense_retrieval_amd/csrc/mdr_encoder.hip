@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "mdr_common.h"
+#include "mdr_gemm_choice.h"
 #include "../../include/mdr_reader.h"
 
 namespace mdr {
@@ -73,16 +74,9 @@ int launch_gemm_cfg(const _Float16* A, int lda, const _Float16* W, const float* 
     return MDR_OK;
 }
 
-// Rounds of tiles the busiest workgroup walks (tiles split evenly over 8 XCDs, then round-robin over an XCD's workgroups).
-inline int persistent_rounds(int M_est, int bm, int N, int bn, int wgs_per_xcd) {
-    const long long T = (long long)((M_est + bm - 1) / bm) * (N / bn);
-    const long long per_xcd = (T + 7) / 8;
-    return (int)((per_xcd + wgs_per_xcd - 1) / wgs_per_xcd);
-}
-
 template <int EPI, typename C>
 int launch_gemm_persist(const _Float16* A, int lda, const _Float16* W, const float* bias, int M_cap, const int* M_dev, int N, int K, void* out, int ldo,
-                        int M_est, int num_cus, hipStream_t st) {
+                        int num_cus, hipStream_t st) {
     constexpr int lds = C::LDS_BYTES + kPersistBiasMax * 4;
     { int rc_ = ensure_dynamic_lds((const void*)gemm_persist_kernel<EPI, C>, lds); if (rc_) return rc_; }
     const int grid = num_cus / 8 * 8;
@@ -95,7 +89,7 @@ int launch_gemm_persist(const _Float16* A, int lda, const _Float16* W, const flo
 
 template <int EPI>
 int launch_gemm_big(const _Float16* A, int lda, const _Float16* W, const float* bias, int M_cap, const int* M_dev, int N, int K, void* out, int ldo,
-                    int M_est, int num_cus, hipStream_t st) {
+                    int num_cus, hipStream_t st) {
     constexpr int lds = GemmB2::LDS_BYTES + kPersistBiasMax * 4 + 8 * 2048;  // slots + bias + per-wave epilogue scratch
     const int grid = num_cus / 8 * 8;
     { int rc_ = ensure_dynamic_lds((const void*)gemm_big_kernel<EPI>, lds); if (rc_) return rc_; }
@@ -106,7 +100,7 @@ int launch_gemm_big(const _Float16* A, int lda, const _Float16* W, const float* 
 
 template <int EPI>
 int launch_gemm_quad(const _Float16* A, int lda, const _Float16* W, const float* bias, int M_cap, const int* M_dev, int N, int K, void* out, int ldo,
-                     int M_est, int num_cus, hipStream_t st) {
+                     int num_cus, hipStream_t st) {
     constexpr int lds = GemmB2::LDS_BYTES + kPersistBiasMax * 4 + 4 * 4096;  // slots + bias + per-wave epilogue scratch
     const int grid = num_cus / 8 * 8;
     { int rc_ = ensure_dynamic_lds((const void*)gemm_quad_kernel<EPI>, lds); if (rc_) return rc_; }
@@ -115,7 +109,7 @@ int launch_gemm_quad(const _Float16* A, int lda, const _Float16* W, const float*
     return MDR_OK;
 }
 
-// M_est: expected number of valid rows (the packed token count is only known on the device).
+// The kernel is gemm_choose's (csrc/mdr_gemm_choice.h); M_est: expected number of valid rows (the packed token count is only known on the device).
 // *res_added tells the caller whether the residual went into the output (else the following LayerNorm adds it).
 template <int EPI>
 int launch_gemm(const _Float16* A, int lda, const _Float16* W, const float* bias, int M_cap, const int* M_dev, int N, int K, void* out, int ldo,
@@ -123,71 +117,29 @@ int launch_gemm(const _Float16* A, int lda, const _Float16* W, const float* bias
     // K: any multiple of 64 from 64 on for the one-tile kernel (2 to 4 stages), gemm_tail_tile, gemm_persist_kernel and gemm_big_kernel -- their prologues
     // skip the stages past K / 64, their counted waits never allow more batches in flight than were issued (the persistent kernels issue surplus batches so
     // that the count is constant) and a tile's pending stores are flushed when the next tile has fewer K-steps than pairs of fragments; the four-wave kernel
-    // needs an even K / 64 >= 4 and is routed around below.
-    // experiment knob: 1 small, 2 mid, 3 big tiles; 4 persistent 256x128 / 6 persistent 256x256 for the large-M calls (the others keep the heuristic)
-    static int env_sel = getenv("MDR_GEMM_CFG") ? atoi(getenv("MDR_GEMM_CFG")) : 0;
-    int sel = force >= 0 ? force : env_sel;
-    if (force < 0 && (sel == 4 || sel == 6 || sel == 7) && (long long)(N / 128) * ((M_est + 255) / 256) < (long long)num_cus * 3 / 2) sel = 0;
-    if (res_added) *res_added = true;
-    const long long p_tiles = (long long)(N / 128) * ((M_est + 255) / 256);
-    if ((sel == 4 || sel == 6 || sel == 7 || (sel == 0 && p_tiles >= (long long)num_cus * 3 / 2)) && N % 128 == 0 && N <= kPersistBiasMax) {
-        if (res_added) *res_added = false;
-        else if (EPI == EPI_BIAS_RES_F32) return set_error(MDR_E_STATE, "large-M GEMM with a residual needs the caller to take the residual (res_added)");
-        constexpr int E = EPI == EPI_BIAS_RES_F32 ? EPI_BIAS_F32 : EPI;
-        // Both kernels are bound by the bytes a CU moves over its L2 path, loads AND stores (~20 B/clk/CU measured; skipping
-        // the stores made the K = 768 GEMMs 25-30 % faster, deferring them did not): cost = rounds x (tile inputs + outputs).
-        // the 256x256 kernels store through a buffer descriptor with 32-bit byte offsets: outputs of 4 GiB and more go to the 256x128 kernel
-        // (the offsets of the LAST row tile reach row M + 254: the guard covers M_cap + 255 rows, so that they cannot wrap into valid low rows -- ADVICE r3)
-        const bool out32 = ((unsigned long long)M_cap + 255ull) * (unsigned long long)ldo * (E == EPI_BIAS_F32 ? 4ull : 2ull) < (1ull << 32);
-        const bool a32 = ((unsigned long long)M_cap + 255ull) * (unsigned long long)lda * 2ull < (1ull << 32);  // the four-wave kernel also LOADS A through a descriptor
-        if (sel == 7 && out32 && a32 && N % 256 == 0 && K % 128 == 0 && K >= 256) return launch_gemm_quad<E>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, M_est, num_cus, st);
-        if ((sel == 6 || sel == 0) && N % 256 == 0 && out32) {
-            const double osz = (E == EPI_BIAS_F32) ? 4.0 : 2.0;
-            // the 256x256 kernels walk only the row tiles that fill complete rounds and finish the rest on 128x128 tiles (gemm_head_row_tiles): cost =
-            // complete rounds x big tile + passes x small tile (latency-bound: counted 1.5 x its bytes)
-            const int grid = num_cus / 8 * 8, ntm_all = (M_est + 255) / 256;
-            auto cost256 = [&](int max_rem, int tiles_per_pass, int* rounds_out) {
-                const int head = gemm_head_row_tiles(ntm_all, N / 256, grid, max_rem);
-                const int rounds = persistent_rounds(std::min(M_est, head * 256), 256, N, 256, num_cus / 8);
-                const long long tail_tiles = (long long)((std::max(0, M_est - head * 256) + 127) / 128) * (N / 128);
-                const long long passes = (tail_tiles + (long long)grid * tiles_per_pass - 1) / ((long long)grid * tiles_per_pass);
-                if (rounds_out) *rounds_out = rounds;
-                return rounds * ((256.0 + 256.0) * K * 2 + 256.0 * 256.0 * osz) + passes * 1.2 * ((128.0 + 128.0) * K * 2 + 128.0 * 128.0 * osz);
-            };
-            int rounds_q = 0;
-            const double c_quad = cost256(grid / 4, 1, &rounds_q), c_big = cost256(grid / 2, 1, nullptr);
-            const double c_p = persistent_rounds(M_est, 256, N, 128, num_cus / 8) * ((256.0 + 128.0) * K * 2 + 256.0 * 128.0 * osz);
-            if (sel == 6 || std::min(c_big, c_quad) < c_p) {
-                // four waves of 128x128 (gemm_quad_kernel): a faster K-loop (fewer LDS reads, one barrier per K-tile) behind a slower epilogue (one
-                // wave per SIMD has nobody to hide its latencies). Measured at 20.3 k rows: FFN2 77 vs 83-86 us, out-projection 30-33 vs 31-37,
-                // but QKV 84-89 vs 70-72 and FFN1 113-123 vs 106-117 (three / four tiles per workgroup, K = 768): taken where the K-loop dominates.
-                if (sel == 0 && a32 && K % 128 == 0 && K >= 256 && (rounds_q == 1 || K >= 2048) && c_quad <= 1.15 * c_big)
-                    return launch_gemm_quad<E>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, M_est, num_cus, st);
-                return launch_gemm_big<E>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, M_est, num_cus, st);
-            }
-        }
-        return launch_gemm_persist<E, GemmP>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, M_est, num_cus, st);
-    }
-    const long long big_blocks = (N % 256 == 0) ? (long long)(N / 256) * ((M_est + 255) / 256) : 0;
-    const long long mid_blocks = (long long)(N / 128) * ((M_est + 127) / 128);
-    const long long small_blocks = (long long)(N / 64) * ((M_est + 63) / 64);
-    if (sel == 3 && big_blocks > 0) return launch_gemm_cfg<EPI, GemmBig>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
-#ifdef MDR_GEMM_EXTRA_CFGS  // measurement builds: more tile shapes behind the test hook's kernel ids 8-11
-    if (sel == 8) return launch_gemm_cfg<EPI, GemmCfg<128, 64, 2, 2, 3>>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
-    if (sel == 9) return launch_gemm_cfg<EPI, GemmCfg<64, 128, 2, 2, 3>>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
-    if (sel == 10) return launch_gemm_cfg<EPI, GemmCfg<128, 128, 2, 2, 3>>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
-    if (sel == 11) return launch_gemm_cfg<EPI, GemmCfg<64, 64, 2, 2, 4>>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
-    if (sel == 12) return launch_gemm_cfg<EPI, GemmCfg<128, 64, 4, 2, 3>>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
-    if (sel == 13) return launch_gemm_cfg<EPI, GemmCfg<64, 64, 4, 2, 3>>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
+    // needs an even K / 64 >= 4 and gemm_choose routes around it.
+    static int env_sel = getenv("MDR_GEMM_CFG") ? atoi(getenv("MDR_GEMM_CFG")) : 0;  // experiment knob: gemm_choose's sel
+    constexpr int E = EPI == EPI_BIAS_RES_F32 ? EPI_BIAS_F32 : EPI;  // what a persistent kernel runs: it leaves the residual to the caller
+    const GemmChoice choice = gemm_choose(force >= 0 ? force : env_sel, force >= 0, M_cap, M_est, N, K, lda, ldo, E == EPI_BIAS_F32 ? 4 : 2, num_cus);
+    if (res_added) *res_added = choice.res_added;
+    else if (EPI == EPI_BIAS_RES_F32 && !choice.res_added)
+        return set_error(MDR_E_STATE, "large-M GEMM with a residual needs the caller to take the residual (res_added)");
+    switch (choice.kernel) {
+    case 7: return launch_gemm_quad<E>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, num_cus, st);
+    case 6: return launch_gemm_big<E>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, num_cus, st);
+    case 4: return launch_gemm_persist<E, GemmP>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, num_cus, st);
+    case 3: return launch_gemm_cfg<EPI, GemmBig>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
+#ifdef MDR_GEMM_EXTRA_CFGS  // measurement builds: more tile shapes behind the test hook's kernel ids 8-13
+    case 8: return launch_gemm_cfg<EPI, GemmCfg<128, 64, 2, 2, 3>>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
+    case 9: return launch_gemm_cfg<EPI, GemmCfg<64, 128, 2, 2, 3>>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
+    case 10: return launch_gemm_cfg<EPI, GemmCfg<128, 128, 2, 2, 3>>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
+    case 11: return launch_gemm_cfg<EPI, GemmCfg<64, 64, 2, 2, 4>>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
+    case 12: return launch_gemm_cfg<EPI, GemmCfg<128, 64, 4, 2, 3>>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
+    case 13: return launch_gemm_cfg<EPI, GemmCfg<64, 64, 4, 2, 3>>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
 #endif
-    // bytes the busiest CU pulls through its L2 path: rounds of blocks x (BM + BN) rows of K; ties go to the small tile
-    // (measured at 2.4 k rows: QKV / FFN1 faster on 128x128, out-projection / FFN2 on 64x64)
-    const long long c_mid = (mid_blocks + num_cus - 1) / num_cus * 256, c_small = (small_blocks + num_cus - 1) / num_cus * 128;
-    // (a forced 128x128 selection whose N is no multiple of 128 takes the 64x64 kernel, as the forced persistent selections do: the grid of the
-    // 128x128 kernel would leave the last 64 columns unwritten)
-    if (N % 128 == 0 && (sel == 2 || (sel == 0 && c_mid < c_small)))
-        return launch_gemm_cfg<EPI, GemmMid>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
-    return launch_gemm_cfg<EPI, GemmSmall>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
+    case 2: return launch_gemm_cfg<EPI, GemmMid>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
+    default: return launch_gemm_cfg<EPI, GemmSmall>(A, lda, W, bias, M_cap, M_dev, N, K, out, ldo, res, ldr, st);
+    }
 }
 
 template <int NT>
@@ -253,6 +205,45 @@ void launch_embed_ln(const long long* ids, const int* tok_src, const int* tok_pi
                        out16, out32);
 }
 
+// What the GEMM test hooks ask of their integers. mdr_test_gemm_f16 has no epilogue 2 and, in MDR_GEMM_EXTRA_CFGS builds, the kernels 8-13.
+int check_gemm_hook_args(int M, int M_est, int N, int K, int epilogue, int kernel, bool f16_hook) {
+    MDR_REQUIRE(M > 0 && N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0, "bad GEMM shape M=%d N=%d K=%d (N, K multiples of 64)", M, N, K);
+    MDR_REQUIRE(M_est >= 1, "M_est=%d must be at least 1", M_est);
+    if (f16_hook) MDR_REQUIRE(epilogue == EPI_BIAS_F16 || epilogue == EPI_BIAS_GELU_F16 || epilogue == EPI_BIAS_F32, "epilogue must be 0, 1 or 3");
+    MDR_REQUIRE(epilogue >= EPI_BIAS_F16 && epilogue <= EPI_BIAS_F32, "epilogue must be 0, 1, 2 or 3");
+    const bool product_kernel = kernel == 0 || kernel == 1 || kernel == 2 || kernel == 4 || kernel == 6 || kernel == 7;
+#ifdef MDR_GEMM_EXTRA_CFGS
+    if (f16_hook) MDR_REQUIRE(product_kernel || (kernel >= 8 && kernel <= 13), "kernel must be 0, 1, 2, 4, 6, 7 or 8-13");
+    else
+#endif
+    MDR_REQUIRE(product_kernel, "kernel must be 0, 1, 2, 4, 6 or 7");
+    return MDR_OK;
+}
+
+// mdr_test_gemm_ex; mdr_test_gemm_f16 is this call with M_est = M, no residual and nobody to tell about it (f16_hook)
+int test_gemm(const void* A_dev, const void* W_dev, const float* bias_dev, const void* res16_dev, int M, int M_est, const int* m_dev, int N, int K,
+              void* out_dev, int epilogue, int kernel, int* res_added_host, bool f16_hook, int device, void* stream) {
+    MDR_REQUIRE(A_dev && W_dev && bias_dev && out_dev, "NULL pointer");
+    if (int rc = check_gemm_hook_args(M, M_est, N, K, epilogue, kernel, f16_hook)) return rc;
+    MDR_REQUIRE((epilogue == EPI_BIAS_RES_F32) == (res16_dev != nullptr), "res16_dev goes with epilogue 2 and with no other");
+    DeviceGuard guard(device);
+    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
+    const int ncu = device_cu_count(device);
+    const _Float16* A = (const _Float16*)A_dev;
+    const _Float16* W = (const _Float16*)W_dev;
+    const _Float16* res = (const _Float16*)res16_dev;
+    hipStream_t st = (hipStream_t)stream;
+    bool added = true;
+    bool* ra = res_added_host ? &added : nullptr;
+    int rc;
+    if (epilogue == EPI_BIAS_F16) rc = launch_gemm<EPI_BIAS_F16>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M_est, ncu, st, ra, kernel);
+    else if (epilogue == EPI_BIAS_GELU_F16) rc = launch_gemm<EPI_BIAS_GELU_F16>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M_est, ncu, st, ra, kernel);
+    else if (epilogue == EPI_BIAS_RES_F32) rc = launch_gemm<EPI_BIAS_RES_F32>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, res, N, M_est, ncu, st, ra, kernel);
+    else rc = launch_gemm<EPI_BIAS_F32>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M_est, ncu, st, ra, kernel);
+    if (res_added_host) *res_added_host = added ? 1 : 0;
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -282,49 +273,29 @@ int mdr_encoder_create(const mdr_encoder_config* cfg, const mdr_tensor* tensors,
 
 int mdr_test_gemm_f16(const void* A_dev, const void* W_dev, const float* bias_dev, int M, const int* m_dev, int N, int K, void* out_dev, int epilogue,
                       int kernel, int device, void* stream) {
-    MDR_REQUIRE(A_dev && W_dev && bias_dev && out_dev, "NULL pointer");
-    MDR_REQUIRE(M > 0 && N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0, "bad GEMM shape M=%d N=%d K=%d (N, K multiples of 64)", M, N, K);
-    MDR_REQUIRE(epilogue == EPI_BIAS_F16 || epilogue == EPI_BIAS_GELU_F16 || epilogue == EPI_BIAS_F32, "epilogue must be 0, 1 or 3");
-#ifdef MDR_GEMM_EXTRA_CFGS
-    MDR_REQUIRE(kernel == 0 || kernel == 1 || kernel == 2 || kernel == 4 || kernel == 6 || kernel == 7 || (kernel >= 8 && kernel <= 13), "kernel must be 0, 1, 2, 4, 6, 7 or 8-13");
-#else
-    MDR_REQUIRE(kernel == 0 || kernel == 1 || kernel == 2 || kernel == 4 || kernel == 6 || kernel == 7, "kernel must be 0, 1, 2, 4, 6 or 7");
-#endif
-    DeviceGuard guard(device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
-    const int ncu = device_cu_count(device);
-    const _Float16* A = (const _Float16*)A_dev;
-    const _Float16* W = (const _Float16*)W_dev;
-    hipStream_t st = (hipStream_t)stream;
-    if (epilogue == EPI_BIAS_F16) return launch_gemm<EPI_BIAS_F16>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M, ncu, st, nullptr, kernel);
-    if (epilogue == EPI_BIAS_GELU_F16) return launch_gemm<EPI_BIAS_GELU_F16>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M, ncu, st, nullptr, kernel);
-    return launch_gemm<EPI_BIAS_F32>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M, ncu, st, nullptr, kernel);
+    return test_gemm(A_dev, W_dev, bias_dev, nullptr, M, M, m_dev, N, K, out_dev, epilogue, kernel, nullptr, true, device, stream);
 }
 
 int mdr_test_gemm_ex(const void* A_dev, const void* W_dev, const float* bias_dev, const void* res16_dev, int M, int M_est, const int* m_dev, int N, int K,
                      void* out_dev, int epilogue, int kernel, int* res_added_host, int device, void* stream) {
-    MDR_REQUIRE(A_dev && W_dev && bias_dev && out_dev, "NULL pointer");
-    MDR_REQUIRE(M > 0 && N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0, "bad GEMM shape M=%d N=%d K=%d (N, K multiples of 64)", M, N, K);
-    MDR_REQUIRE(M_est >= 1, "M_est=%d must be at least 1", M_est);
-    MDR_REQUIRE(epilogue >= EPI_BIAS_F16 && epilogue <= EPI_BIAS_F32, "epilogue must be 0, 1, 2 or 3");
-    MDR_REQUIRE((epilogue == EPI_BIAS_RES_F32) == (res16_dev != nullptr), "res16_dev goes with epilogue 2 and with no other");
-    MDR_REQUIRE(kernel == 0 || kernel == 1 || kernel == 2 || kernel == 4 || kernel == 6 || kernel == 7, "kernel must be 0, 1, 2, 4, 6 or 7");
-    DeviceGuard guard(device);
-    if (!guard.ok) return set_error(MDR_E_HIP, "hipSetDevice(%d) failed", device);
-    const int ncu = device_cu_count(device);
-    const _Float16* A = (const _Float16*)A_dev;
-    const _Float16* W = (const _Float16*)W_dev;
-    const _Float16* res = (const _Float16*)res16_dev;
-    hipStream_t st = (hipStream_t)stream;
-    bool added = true;
-    bool* ra = res_added_host ? &added : nullptr;
-    int rc;
-    if (epilogue == EPI_BIAS_F16) rc = launch_gemm<EPI_BIAS_F16>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M_est, ncu, st, ra, kernel);
-    else if (epilogue == EPI_BIAS_GELU_F16) rc = launch_gemm<EPI_BIAS_GELU_F16>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M_est, ncu, st, ra, kernel);
-    else if (epilogue == EPI_BIAS_RES_F32) rc = launch_gemm<EPI_BIAS_RES_F32>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, res, N, M_est, ncu, st, ra, kernel);
-    else rc = launch_gemm<EPI_BIAS_F32>(A, K, W, bias_dev, M, m_dev, N, K, out_dev, N, nullptr, 0, M_est, ncu, st, ra, kernel);
-    if (res_added_host) *res_added_host = added ? 1 : 0;
-    return rc;
+    return test_gemm(A_dev, W_dev, bias_dev, res16_dev, M, M_est, m_dev, N, K, out_dev, epilogue, kernel, res_added_host, false, device, stream);
+}
+
+int mdr_test_gemm_choice(int kernel, int M, int M_est, int N, int K, int epilogue, int num_cus, int* kernel_out, int* res_added_out,
+                         int* walk_row_tiles_out) {
+    if (int rc = check_gemm_hook_args(M, M_est, N, K, epilogue, kernel, false)) return rc;
+    MDR_REQUIRE(num_cus >= 8, "num_cus=%d must be at least 8", num_cus);
+    const GemmChoice c = gemm_choose(kernel, kernel != 0, M, M_est, N, K, K, N, epilogue == EPI_BIAS_RES_F32 || epilogue == EPI_BIAS_F32 ? 4 : 2, num_cus);
+    if (kernel_out) *kernel_out = c.kernel;
+    if (res_added_out) *res_added_out = c.res_added ? 1 : 0;
+    if (walk_row_tiles_out) {
+        const int grid = num_cus / 8 * 8, ntm_all = (M_est + 255) / 256;
+        *walk_row_tiles_out = c.kernel == 6   ? gemm_head_row_tiles(ntm_all, N / 256, grid, grid / 2)  // (gemm_big_kernel's call,
+                              : c.kernel == 7 ? gemm_head_row_tiles(ntm_all, N / 256, grid, grid / 4)  //  gemm_quad_kernel's)
+                              : c.kernel == 4 ? ntm_all
+                                              : 0;
+    }
+    return MDR_OK;
 }
 
 int mdr_test_attention(const void* qkv_dev, const int* cu_dev, const int* order_dev, int B, int L, int hidden, int heads, int kernel, void* ctx_dev,

@@ -207,17 +207,7 @@ gemm_f16_kernel(const _Float16* __restrict__ A, int lda, const _Float16* __restr
 }
 
 // ---- tail of the persistent 256x256 kernels: the last, partial round on 128x128 tiles ------------------------------------------
-// T = ntm x ntn tiles of 256x256 over G persistent workgroups take ceil(T / G) rounds; when T is a little over a multiple of G the last round
-// keeps a few workgroups busy for a whole tile time while the rest of the chip idles (86 row tiles of 256 x N = 768: 258 tiles = TWO rounds on 256
-// CUs for one round of work -- the +37 % step at 21.8 k tokens of DESIGN.md section 4). gemm_head_row_tiles() gives the 256x256 walk only the row
-// tiles that fill COMPLETE rounds; the remaining rows (fewer than max_rem + ntn tiles' worth) are computed by the same workgroups afterwards on
-// 128x128 tiles (gemm_tail_tile: the one-tile-per-block kernel's K-loop on a four-slot ring over the whole 128 KiB), which spreads them over 4x as many units. Same K order and MFMA per output element as every other flavour: bit-identical results.
-__host__ __device__ inline int gemm_head_row_tiles(int ntm, int ntn, int G, int max_rem) {
-    const long long T = (long long)ntm * ntn;
-    const long long full = T / G, rem = T % G;
-    if (full < 1 || rem == 0 || rem > max_rem) return ntm;
-    return (int)(full * G / ntn);
-}
+// (which rows the tail gets, and why: gemm_head_row_tiles, csrc/mdr_gemm_choice.h)
 
 // The tail's MFMAs are spelled as asm with VGPR accumulators: gemm_quad_kernel keeps a[0:255] live ACROSS its asm statements, so the compiler must not
 // be given a reason to touch an AGPR anywhere in that kernel (its own MFMA form put these 64 accumulators there: scripts/check_quad_agprs.py). Hazards
@@ -348,8 +338,7 @@ using GemmP = GemmCfg<256, 128, 4, 2, 3>;   // 3 slots of 48 KiB: two batches in
 #endif
 // K: any multiple of 64 from 64 on. Every K-step issues exactly one batch (surplus ones past the end of the stream), so the counted wait is exact for any KT; with fewer
 // than eight K-steps a tile the fragments the next tile's steps did not carry out are flushed behind its K-loop (tests/test_gemm_exact_gpu.py runs K = 64 .. 448 with
-// two tiles per workgroup).
-constexpr int kPersistBiasMax = 3072;  // floats of bias kept in LDS behind the ring (12 KiB)
+// two tiles per workgroup). The bias vector behind the ring: kPersistBiasMax floats (csrc/mdr_gemm_choice.h).
 
 template <int EPI, typename C>
 __global__ void __launch_bounds__(C::THREADS)

@@ -1,7 +1,7 @@
 """Host restatement of ONE forward GEMM call of the encoder (mdr_test_gemm_ex, include/mdr_hip.h): the exact result on a grid of inputs, the
 erf-GELU in fp64 and as the fp32 chain of gelu_erf2 (csrc/mdr_encoder_gemm.inl) with switchable mutations, derived error bounds, a second
-implementation of the GEMM's dataflow with switchable defects, and a mirror of the host's kernel choice. numpy (erfc in float64 through
-torch's CPU kernel); nothing here is measured from a kernel. Test helper (tests/test_gemm_host.py, tests/test_gemm_exact_gpu.py).
+implementation of the GEMM's dataflow with switchable defects, and the host's kernel choice as the library reports it (mdr_test_gemm_choice: the
+function the launcher switches on, not a copy of it). numpy (erfc in float64 through torch's CPU kernel); nothing here is measured from a kernel. Test helper (tests/test_gemm_host.py, tests/test_gemm_exact_gpu.py).
 
 Layout: x float16 [M, K], w float16 [N, K], b float32 [N], res None or float16 [M, N].
 Epilogues: 0 = fp16(z), 1 = fp16(gelu(z)), 2 = z + res in fp32 (the persistent kernels leave the residual out and say so), 3 = z in fp32,
@@ -36,6 +36,8 @@ backward's dX uses (the same GEMM); then the fp32 add of the bias and, for epilo
       ez = K X1ULP (|x| |w|^T) + U32 (|z| + ez) [+ U32 (|z + res| + ez)]
 fp32 outputs: ez. Epilogue 0: ez + r(|z| + ez). Epilogue 1: as above with du = ez.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -51,7 +53,6 @@ CLAMP = 16.0
 KERNELS = (0, 1, 2, 4, 6, 7)
 SMALL_NK = [(64, 64), (192, 64), (128, 128), (256, 64), (256, 128), (256, 192), (256, 256), (256, 384), (512, 256)]
 M_SWEEP = [1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 255, 256, 257, 300]   # -1, 0, +1 around an MFMA tile and the 64-, 128- and 256-row tiles
-PERSIST_BIAS_MAX = 3072
 
 
 # ---- makers --------------------------------------------------------------------------------------------------------------------------------
@@ -208,72 +209,34 @@ def emulate(x, w, b, epilogue, res=None, res_added=True, mutation=None):
     return v.astype(np.float16)
 
 
-# ---- the host's kernel choice (launch_gemm of csrc/mdr_encoder.hip) -----------------------------------------------------------------------
-def head_row_tiles(ntm, ntn, G, max_rem):
-    """gemm_head_row_tiles: the row tiles of 256 the 256x256 walk takes; the rows behind them go to 128x128 tail tiles."""
-    T = ntm * ntn
-    full, rem = T // G, T % G
-    if full < 1 or rem == 0 or rem > max_rem:
-        return ntm
-    return full * G // ntn
+# ---- the host's kernel choice: asked of the library (mdr_test_gemm_choice, include/mdr_hip.h), which answers without a device ---------------
+NOMINAL = {1: "small", 2: "mid", 4: "persist", 6: "big", 7: "quad"}
 
 
-def persistent_rounds(M_est, bm, N, bn, wgs_per_xcd):
-    T = ((M_est + bm - 1) // bm) * (N // bn)
-    per_xcd = (T + 7) // 8
-    return (per_xcd + wgs_per_xcd - 1) // wgs_per_xcd
+def choice(kernel, M_cap, M_est, N, K, epilogue, num_cus):
+    """(kernel id, res_added, row tiles of 256 of the persistent walk at M_est valid rows) of gemm_choose (csrc/mdr_gemm_choice.h), the function
+    launch_gemm switches on, for the call mdr_test_gemm_ex(kernel, M = M_cap, M_est, N, K, epilogue) on num_cus compute units."""
+    from multihop_dense_retrieval_amd import _lib
+    out = [ctypes.c_int(-1) for _ in range(3)]
+    _lib.check(_lib.lib().mdr_test_gemm_choice(kernel, M_cap, M_est, N, K, epilogue, num_cus, *[ctypes.byref(o) for o in out]))
+    return out[0].value, bool(out[1].value), out[2].value
 
 
 def flavour(kernel, M_cap, M_est, N, K, epilogue, num_cus):
     """The kernel a forced selection (the hooks never read the environment) lands on: "small" (64x64), "mid" (128x128), "persist" (256x128),
     "big" (256x256, eight waves) or "quad" (256x256, four waves). The one-tile kernels add the residual of epilogue 2, the others do not."""
-    sel = kernel
-    p_tiles = (N // 128) * ((M_est + 255) // 256)
-    if (sel in (4, 6, 7) or (sel == 0 and p_tiles >= num_cus * 3 // 2)) and N % 128 == 0 and N <= PERSIST_BIAS_MAX:
-        osz = 4 if epilogue in (2, 3) else 2
-        out32 = (M_cap + 255) * N * osz < 2 ** 32
-        a32 = (M_cap + 255) * K * 2 < 2 ** 32
-        quad_ok = K % 128 == 0 and K >= 256
-        if sel == 7 and out32 and a32 and N % 256 == 0 and quad_ok:
-            return "quad"
-        if sel in (6, 0) and N % 256 == 0 and out32:
-            grid_, ntm_all = num_cus // 8 * 8, (M_est + 255) // 256
-
-            def cost256(max_rem):
-                head = head_row_tiles(ntm_all, N // 256, grid_, max_rem)
-                rounds = persistent_rounds(min(M_est, head * 256), 256, N, 256, num_cus // 8)
-                tail_tiles = ((max(0, M_est - head * 256) + 127) // 128) * (N // 128)
-                passes = (tail_tiles + grid_ - 1) // grid_
-                return rounds * (512.0 * K * 2 + 65536.0 * osz) + passes * 1.2 * (256.0 * K * 2 + 16384.0 * osz), rounds
-
-            (c_quad, rounds_q), (c_big, _) = cost256(grid_ // 4), cost256(grid_ // 2)
-            c_p = persistent_rounds(M_est, 256, N, 128, num_cus // 8) * (384.0 * K * 2 + 32768.0 * osz)
-            if sel == 6 or min(c_big, c_quad) < c_p:
-                if sel == 0 and a32 and quad_ok and (rounds_q == 1 or K >= 2048) and c_quad <= 1.15 * c_big:
-                    return "quad"
-                return "big"
-        return "persist"
-    mid_blocks, small_blocks = (N // 128) * ((M_est + 127) // 128), (N // 64) * ((M_est + 63) // 64)
-    c_mid, c_small = (mid_blocks + num_cus - 1) // num_cus * 256, (small_blocks + num_cus - 1) // num_cus * 128
-    if N % 128 == 0 and (sel == 2 or (sel == 0 and c_mid < c_small)):
-        return "mid"
-    return "small"
+    return NOMINAL[choice(kernel, M_cap, M_est, N, K, epilogue, num_cus)[0]]
 
 
-NOMINAL = {1: "small", 2: "mid", 4: "persist", 6: "big", 7: "quad"}
-
-
-def persistent_walk(fl, M, N, num_cus):
-    """(most tiles one workgroup owns, tail tiles) of a persistent flavour at M valid rows: the XCD split of gemm_persist_kernel / gemm_big_kernel /
-    gemm_quad_kernel (XCD x owns tiles [T x / 8, T (x + 1) / 8) and walks them round-robin over its num_cus / 8 workgroups)."""
-    grid_ = num_cus // 8 * 8
-    G = grid_ // 8
-    if fl == "persist":
-        ntn, ntm, tail = N // 128, (M + 255) // 256, 0
-    else:
-        ntn = N // 256
-        ntm = head_row_tiles((M + 255) // 256, ntn, grid_, grid_ // (2 if fl == "big" else 4))
-        tail = ((max(0, M - ntm * 256) + 127) // 128) * (N // 128)
+def persistent_walk(kernel, M, N, K, num_cus):
+    """(most tiles one workgroup owns, tail tiles) of the persistent kernel a selection lands on at M valid rows: the XCD split of
+    gemm_persist_kernel / gemm_big_kernel / gemm_quad_kernel (XCD x owns tiles [T x / 8, T (x + 1) / 8) and walks them round-robin over its
+    num_cus / 8 workgroups), over the row tiles the host counts; the 256x256 kernels finish the rows behind them on 128x128 tail tiles."""
+    kid, _, ntm = choice(kernel, M, M, N, K, 0, num_cus)
+    assert kid in (4, 6, 7), kid
+    G = num_cus // 8
+    ntn = N // 128 if kid == 4 else N // 256
+    tail = ((max(0, M - ntm * 256) + 127) // 128) * (N // 128)
     T = ntm * ntn
     most = max((T * (x + 1) // 8 - T * x // 8 + G - 1) // G for x in range(8))
     return most, tail

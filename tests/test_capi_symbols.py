@@ -91,7 +91,7 @@ def test_product_library_holds_no_measurement_code():
     assert hooks == ["mdr_stream_create_cu_range", "mdr_stream_destroy", "mdr_test_attn_stamps", "mdr_test_gemm_stamps", "mdr_test_i8_stamps"]
     for name in hooks:
         assert not hasattr(lib, name), f"{name} is a measurement hook but the product library exports it"
-    assert len([n for n in declared_symbols()]) == 33  # round 6: the CU-lane pair moved to the measurement header; + mdr_test_attention (a test hook like mdr_test_gemm_f16); + the four hooks of the trunk's row kernels (mdr_test_pack / embed_ln / layernorm / row_copy); + mdr_test_gemm_ex
+    assert len([n for n in declared_symbols()]) == 34  # round 6: the CU-lane pair moved to the measurement header; + mdr_test_attention (a test hook like mdr_test_gemm_f16); + the four hooks of the trunk's row kernels (mdr_test_pack / embed_ln / layernorm / row_copy); + mdr_test_gemm_ex; + mdr_test_gemm_choice (the launcher's kernel choice, reported instead of restated in the tests)
     blob = open(path, "rb").read()
     for knob in (b"MDR_GEMM_ABL", b"MDR_GEMM_EPI", b"MDR_I8_ABL", b"MDR_ATTN_ABL", b"g_gemm_stamp", b"g_i8_stamp", b"g_attn_stamp", b"g_stream_cus", b"mips_gemmk_kernel"):
         assert knob not in blob, f"{knob!r} found in the product library"

@@ -12,8 +12,8 @@ Every output lives in a buffer with 64 guard rows of a finite sentinel on both s
 their bits in every call of this file (run() asserts it).
 
 Kernels 0 (the heuristic), 1 (64x64), 2 (128x128), 4 (persistent 256x128), 6 and 7 (persistent 256x256 on eight and four waves); a forced
-kernel whose condition the shape does not meet falls back, which gemm_ref.flavour mirrors and the tests assert through res_added and
-bit-equality.
+kernel whose condition the shape does not meet falls back; gemm_ref.flavour asks the library which kernel a call lands on (the function the
+launcher itself switches on) and the tests assert it through res_added and bit-equality.
 """
 import ctypes
 
@@ -200,7 +200,7 @@ def test_several_tiles_per_workgroup_at_short_k(kernel, M, K):
     N = 3072
     fl = flavour_of(kernel, M, N, K, 0)
     assert fl == ref.NOMINAL[kernel]
-    most, tail = ref.persistent_walk(fl, M, N, num_cus())
+    most, tail = ref.persistent_walk(kernel, M, N, K, num_cus())
     assert most >= 2, "no workgroup owns two tiles: the grid changed, choose M again"
     assert fl == "persist" or tail > 0, "the 128x128 tail is empty: choose M again"
     tx, tw = device_grid((M, K), 100 + K), device_grid((N, K), 200 + K)

@@ -1,12 +1,16 @@
 """CPU: the reference of the forward GEMM suite (tests/gemm_ref.py) checked against itself. The fp32 chain of gelu_erf2 against the fp64 GELU
 within the derived bound over every finite fp16 value and a dense fp32 sweep; each GELU mutation thrown out, the unclamped polynomial (the
 code before the clamp) exactly where it goes wrong; a second implementation of the GEMM's dataflow inside the realistic-rows bound and equal to
-the exact grid result, each deliberate defect thrown out by the grid comparison. No device and no kernel runs here."""
+the exact grid result, each deliberate defect thrown out by the grid comparison; the launcher's kernel choice (mdr_test_gemm_choice, host
+integers only) pinned on a table of literals. No device and no kernel runs here."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
 
 import gemm_ref as ref
+from guarded import E_INVALID, OK
 from oracle import fp
 
 
@@ -141,7 +145,8 @@ def test_exact_refuses_inputs_off_the_grid():
 
 
 def test_flavour_mirror_on_the_documented_cases():
-    """forced selections and their fall-backs, and the three classes the M_est test of the GPU suite relies on (256 compute units)"""
+    """forced selections and their fall-backs, and the three classes the M_est test of the GPU suite relies on (256 compute units): the answers
+    of the function launch_gemm switches on (gemm_ref.flavour -> mdr_test_gemm_choice)"""
     f = ref.flavour
     assert [f(k, 300, 300, 256, 256, 0, 256) for k in (1, 2, 4, 6, 7)] == ["small", "mid", "persist", "big", "quad"]
     assert f(2, 300, 300, 192, 64, 0, 256) == "small" and f(2, 300, 300, 64, 64, 0, 256) == "small"   # no multiple of 128: 64x64 tiles
@@ -149,3 +154,80 @@ def test_flavour_mirror_on_the_documented_cases():
     assert f(7, 300, 300, 256, 64, 0, 256) == "persist" and f(7, 300, 300, 256, 192, 0, 256) == "persist" and f(7, 300, 300, 256, 384, 0, 256) == "quad"
     got = [f(0, 300, est, 3072, 256, 0, 256) for est in (1, 300, 4096, 70000)]
     assert got[0] in ("small", "mid") and got[1] in ("small", "mid") and {"quad", "big"} <= set(got[2:]), got
+
+
+# (kernel, M_cap, M_est, N, K, epilogue, num_cus) -> kernel id: 1 = 64x64, 2 = 128x128, 4 = persistent 256x128, 6 / 7 = 256x256 on eight / four waves.
+# One row per branch of gemm_choose (csrc/mdr_gemm_choice.h); the values are those of the Python mirror the GPU suite used before the hook existed.
+CHOICES = [
+    ((0, 300, 300, 768, 768, 0, 256), 1),             # few tiles, small wins the byte count
+    ((0, 2400, 2400, 2304, 768, 0, 256), 2),          # few tiles, mid wins
+    ((0, 2400, 2400, 768, 3072, 0, 256), 1),
+    ((0, 30720, 20480, 2304, 768, 0, 256), 6),        # QKV at bench size: big
+    ((0, 30720, 20480, 768, 768, 3, 256), 7),         # out-projection: quad (one round)
+    ((0, 30720, 20480, 3072, 768, 1, 256), 6),        # FFN1
+    ((0, 30720, 20480, 768, 3072, 3, 256), 7),        # FFN2 (K >= 2048)
+    ((0, 30720, 20480, 768, 3072, 2, 256), 7),        # epilogue 2 decides as 3
+    ((0, 65536, 43691, 1024, 1024, 0, 256), 6),
+    ((0, 65536, 43691, 4096, 1024, 1, 256), 2),       # N above the bias slot: one-tile whatever M
+    ((0, 65536, 43691, 1024, 4096, 3, 256), 7),
+    ((0, 30720, 20480, 384, 768, 0, 256), 2),         # too few persistent tiles
+    ((0, 30720, 20480, 1920, 768, 0, 256), 4),        # N % 256 != 0
+    ((0, 30720, 20480, 768, 192, 0, 256), 6),         # K % 128 != 0: no quad
+    ((0, 30720, 20480, 768, 320, 0, 256), 6),
+    ((0, 1500000, 1000000, 768, 768, 3, 256), 4),     # fp32 output of 4 GiB and more: no 32-bit store offsets
+    ((0, 1500000, 1000000, 768, 768, 0, 256), 6),     # the fp16 output still fits
+    ((0, 700000, 700000, 256, 3072, 0, 256), 6),      # A of 4 GiB and more: no quad
+    ((0, 22016, 22016, 768, 768, 0, 256), 7),         # 86 row tiles (the 258-tile step)
+    ((0, 11009, 11009, 3072, 256, 0, 256), 6),
+    ((0, 300, 4096, 3072, 256, 0, 256), 7),           # M_est alone decides ...
+    ((0, 300, 70000, 3072, 256, 0, 256), 6),          # ... both ways
+    ((0, 30720, 20480, 2304, 768, 0, 304), 6),        # another CU count
+    ((0, 30720, 20480, 768, 3072, 3, 304), 7),
+    ((0, 30720, 20480, 768, 768, 0, 64), 6),
+    ((0, 2400, 2400, 2304, 768, 0, 64), 6),
+    ((7, 300, 300, 256, 128, 0, 256), 4),             # forced 7, K < 256
+    ((7, 300, 300, 512, 256, 0, 256), 7),
+    ((6, 300, 300, 384, 64, 0, 256), 4),              # forced 6, N % 256 != 0
+    ((4, 300, 300, 3200, 64, 0, 256), 1),             # forced 4, N above the bias slot
+    ((2, 300, 300, 320, 64, 0, 256), 1),              # forced 2, N % 128 != 0
+    ((7, 9000000, 300, 256, 256, 0, 256), 4),         # forced 7 / 6 past the 32-bit guards
+    ((6, 9000000, 300, 256, 256, 3, 256), 4),
+    ((6, 9000000, 300, 256, 256, 0, 256), 4),
+]
+
+
+def test_the_kernel_choice_on_one_case_per_branch():
+    for args, kernel in CHOICES:
+        got, res_added, _ = ref.choice(*args)
+        assert got == kernel and res_added == (kernel in (1, 2)), (args, kernel, got, res_added)
+
+
+def raw_choice(*args):
+    from multihop_dense_retrieval_amd import _lib
+    return _lib.lib().mdr_test_gemm_choice(*args)
+
+
+def test_the_choice_hook_refuses_bad_arguments():
+    good = dict(kernel=0, M=300, M_est=300, N=256, K=256, epilogue=0, num_cus=256)
+    assert raw_choice(*good.values(), None, None, None) == OK
+    for change in (dict(kernel=3), dict(kernel=8), dict(epilogue=4), dict(M_est=0), dict(N=96), dict(num_cus=0)):
+        out = ctypes.c_int(-7)
+        assert raw_choice(*{**good, **change}.values(), ctypes.byref(out), None, None) == E_INVALID, change
+        assert out.value == -7, change
+
+
+def test_every_out_pointer_of_the_choice_hook_may_be_null():
+    args = (6, 22016, 22016, 768, 768, 0, 256)
+    want = ref.choice(*args)
+    assert want == (6, False, 85)
+    assert raw_choice(*args, None, None, None) == OK
+    for i in range(3):
+        outs = [ctypes.c_int(-7) for _ in range(3)]
+        assert raw_choice(*args, *[ctypes.byref(o) if j == i else None for j, o in enumerate(outs)]) == OK
+        assert [o.value for o in outs] == [int(want[j]) if j == i else -7 for j in range(3)]
+
+
+def test_walk_row_tiles():
+    """86 row tiles x 3 column tiles of 256 = 258 tiles on 256 workgroups: the one complete round is 85 row tiles, the 86th goes to the 128x128 tail;
+    the 256x128 kernel walks all 86; the one-tile kernels walk none."""
+    assert [ref.choice(k, 22016, 22016, 768, 768, 0, 256) for k in (6, 7, 4, 1)] == [(6, False, 85), (7, False, 85), (4, False, 86), (1, True, 0)]

@@ -148,8 +148,8 @@ def test_some_tested_shape_is_split():
 def test_large_shapes_reach_the_steady_state_and_the_persistent_gemm():
     """LARGE_MNK against the LIBRARY's split: three slabs or more per chunk, S >= 3, a ragged last chunk (linear_grad_ref.assert_large). dX of
     the FFN2 shape leaves the one-tile kernels on this device: launch_gemm (csrc/mdr_encoder.hip) is called with the GEMM's N = the Linear's
-    K, its K = the Linear's N and M_est = M, and gemm_ref.flavour restates its choice (p_tiles = (N / 128) * ceil(M_est / 256) >= 3/2 of the
-    compute units); at M = 300 the same Linear stays on a one-tile kernel."""
+    K, its K = the Linear's N and M_est = M, and gemm_ref.flavour reports the choice it makes (persistent from (N / 128) * ceil(M_est / 256) >=
+    3/2 of the compute units on); at M = 300 the same Linear stays on a one-tile kernel."""
     import gemm_ref
     from multihop_dense_retrieval_amd import linear
     props = ref.assert_large(chunks_of=linear.backward_chunks)

@@ -6,8 +6,8 @@ large enough for the persistent 256x256 kernels (gemm_big_kernel, gemm_quad_kern
 a. against HF ElectraModel in fp64 on the device plus the fp64 heads (test_reader_gpu._reference, 8 rows at a time), under the bars of that file;
 b. against the same rows run 4 at a time through the small-tile path those tests pin: every GEMM flavour accumulates K in the same order with the same
    MFMA, attention and LayerNorm work per sequence / per token, so the fp16 logits, rank and sp scores must be BIT-IDENTICAL;
-c. `gemm_choice` below restates launch_gemm's selection, and each case asserts that the kernels it means to test were chosen. THE RESTATEMENT MUST MOVE
-   WITH THE C++ (launch_gemm, gemm_head_row_tiles, persistent_rounds, kPersistBiasMax): it is what keeps this file from silently testing small tiles.
+c. `layer_gemm_plan` below asks the library which kernel launch_gemm picks for each GEMM of a layer (gemm_ref.flavour -> mdr_test_gemm_choice, the function
+   the launcher switches on), and each case asserts that the kernels it means to test were chosen: it is what keeps this file from silently testing small tiles.
 
 Plus: workspace reuse after a large call, decode(with_logits=False) (the CLI's call: logits live in the workspace), B > 1024 (chunked scan, no length
 sort) and a non-default stream. Run time on one MI355X: see profiles/reader_bench.md."""
@@ -17,68 +17,23 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 transformers = pytest.importorskip("transformers")
 
+import gemm_ref  # noqa: E402
 import test_reader_gpu as rg  # noqa: E402  (the helpers of the small-batch reader tests; tests/ is on sys.path through conftest.py)
 
 DEV = "cuda"
 N_SENT = 10
 
-# ---- (c) launch_gemm's choice, restated -------------------------------------------------------------------------------------------------------------
-K_PERSIST_BIAS_MAX = 3072  # csrc/mdr_encoder_gemm.inl
-
-
-def _cdiv(a, b):
-    return (a + b - 1) // b
-
-
-def head_row_tiles(ntm, ntn, G, max_rem):  # gemm_head_row_tiles
-    T = ntm * ntn
-    full, rem = divmod(T, G)
-    if full < 1 or rem == 0 or rem > max_rem:
-        return ntm
-    return full * G // ntn
-
-
-def persistent_rounds(M_est, bm, N, bn, wgs_per_xcd):
-    T = _cdiv(M_est, bm) * (N // bn)
-    return _cdiv(_cdiv(T, 8), wgs_per_xcd)
-
-
-def gemm_choice(M_cap, M_est, N, K, out_bytes, num_cus, lda=None, ldo=None):
-    """What launch_gemm<EPI> launches without MDR_GEMM_CFG: 'quad' (gemm_quad_kernel), 'big' (gemm_big_kernel), 'persist' (gemm_persist_kernel, 256x128)
-    -- the persistent branch -- or 'tile' (gemm_f16_kernel, one 64x64 / 128x128 tile per block). out_bytes: 4 for the fp32 epilogues, 2 otherwise."""
-    lda, ldo = lda or K, ldo or N
-    p_tiles = (N // 128) * _cdiv(M_est, 256)
-    if not (p_tiles >= num_cus * 3 // 2 and N % 128 == 0 and N <= K_PERSIST_BIAS_MAX):
-        return "tile"
-    out32 = (M_cap + 255) * ldo * out_bytes < 1 << 32
-    a32 = (M_cap + 255) * lda * 2 < 1 << 32
-    if N % 256 == 0 and out32:
-        grid, ntm_all, osz = num_cus // 8 * 8, _cdiv(M_est, 256), float(out_bytes)
-
-        def cost256(max_rem):
-            head = head_row_tiles(ntm_all, N // 256, grid, max_rem)
-            rounds = persistent_rounds(min(M_est, head * 256), 256, N, 256, num_cus // 8)
-            tail_tiles = _cdiv(max(0, M_est - head * 256), 128) * (N // 128)
-            passes = _cdiv(tail_tiles, grid)
-            return rounds * ((256.0 + 256.0) * K * 2 + 256.0 * 256.0 * osz) + passes * 1.2 * ((128.0 + 128.0) * K * 2 + 128.0 * 128.0 * osz), rounds
-
-        (c_quad, rounds_q), (c_big, _) = cost256(grid // 4), cost256(grid // 2)
-        c_p = persistent_rounds(M_est, 256, N, 128, num_cus // 8) * ((256.0 + 128.0) * K * 2 + 256.0 * 128.0 * osz)
-        if min(c_big, c_quad) < c_p:
-            if a32 and K % 128 == 0 and K >= 256 and (rounds_q == 1 or K >= 2048) and c_quad <= 1.15 * c_big:
-                return "quad"
-            return "big"
-    return "persist"
-
-
+# ---- (c) launch_gemm's choice, as the library reports it ------------------------------------------------------------------------------------------------
 def layer_gemm_plan(B, L, H, F, residual_fp32, num_cus):
     """The four GEMMs of one reader layer as mdr_reader_forward calls launch_gemm: M_cap = B * L, M_est = B * L - B * L / 3; the out-projection and FFN2
-    write fp16 in residual mode 2 and fp32 in modes 1 and 0 (mode 0: EPI_BIAS_RES_F32, which the persistent branch demotes to EPI_BIAS_F32)."""
+    write fp16 in residual mode 2 (epilogue 0) and fp32 in modes 1 (epilogue 3) and 0 (epilogue 2, which the persistent kernels run as 3); the choice
+    reads an epilogue's output width only, so FFN1's GELU stands as epilogue 0.
+    -> gemm_ref.flavour's names; "small" and "mid" are gemm_f16_kernel, one 64x64 / 128x128 tile per block."""
     T = B * L
     est = T - T // 3
-    wide = 2 if residual_fp32 == 2 else 4
-    return {"qkv": gemm_choice(T, est, 3 * H, H, 2, num_cus), "out": gemm_choice(T, est, H, H, wide, num_cus),
-            "ffn1": gemm_choice(T, est, F, H, 2, num_cus), "ffn2": gemm_choice(T, est, H, F, wide, num_cus)}
+    wide = {2: 0, 1: 3, 0: 2}[residual_fp32]
+    return {"qkv": gemm_ref.flavour(0, T, est, 3 * H, H, 0, num_cus), "out": gemm_ref.flavour(0, T, est, H, H, wide, num_cus),
+            "ffn1": gemm_ref.flavour(0, T, est, F, H, 0, num_cus), "ffn2": gemm_ref.flavour(0, T, est, H, F, wide, num_cus)}
 
 
 PERSISTENT = ("quad", "big", "persist")
@@ -206,7 +161,7 @@ def test_forward_at_production_shapes(case, residual_fp32):
     print(f"[reader {label}] {ncu} CUs, GEMMs of a layer: {plan}")
     assert any(v in PERSISTENT for v in plan.values()), (label, plan)
     if geom in ("large", "two") and (B, L) == (64, 512):
-        assert plan["qkv"] in PERSISTENT and plan["out"] in PERSISTENT and plan["ffn2"] in PERSISTENT and plan["ffn1"] == "tile", (label, plan)
+        assert plan["qkv"] in PERSISTENT and plan["out"] in PERSISTENT and plan["ffn2"] in PERSISTENT and plan["ffn1"] in ("small", "mid"), (label, plan)
     if case.startswith("edge"):
         assert sum(lens) < (B * L - B * L // 3) / 2
     m = _hip_model(geom, residual_fp32)
