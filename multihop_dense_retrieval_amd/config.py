@@ -1,6 +1,6 @@
-"""Flag sets of the corpus-encoder CLI and of the retriever's dev-set evaluation: `encode_args()` = `common_args()` + two
+"""Flag sets of the corpus-encoder CLI and of the retriever's training and dev-set evaluation: `encode_args()` = `common_args()` + two
 flags, `train_args()` = `common_args()` + the optimisation flags, flag for flag as
-/root/reference/mdr/retrieval/config.py:14-69,71-105,107-112 (training-only flags are accepted and ignored so
+/root/reference/mdr/retrieval/config.py:14-69,71-105,107-112 (flags a CLI does not use are accepted and ignored so
 existing command lines keep working)."""
 import argparse
 
@@ -52,7 +52,7 @@ def encode_args(argv=None):
 
 
 def train_args(argv=None):
-    """config.py:71-105: the flags of scripts/train_mhop.py (only --do_predict runs here; the README's training argv still parses)."""
+    """config.py:71-105: the flags of scripts/train_mhop.py (--do_train and --do_predict)."""
     p = common_args()
     p.add_argument("--prefix", type=str, default="eval")
     p.add_argument("--weight_decay", default=0.0, type=float)

@@ -43,6 +43,19 @@ EXPORTED_SYMBOLS = tuple(SIGNATURES)
 lib = _lib.binder(SIGNATURES)  # libmdrhip.so with the signatures of include/mdr_dropout.h bound
 
 
+ENCODES, MAX_LAYERS = 6, 64  # the six encodes of one in-batch loss; more layers than any geometry has
+PLACES = ("emb", "attn", "ao", "ff2")
+
+
+def site_of(encode, layer, place):
+    """The uint32 site of one dropout call of a training step (train.TrainableRetriever): encode 0 .. 5 (the index of the batch key in q,
+    q_sp1, c1, c2, neg_1, neg_2; a lone encode is 0), layer 0 .. 63, place one of PLACES ("emb" belongs to layer 0). Injective, and never 0.
+    The step itself is told apart by the seed."""
+    if not (0 <= encode < ENCODES and 0 <= layer < MAX_LAYERS and place in PLACES and (place != "emb" or layer == 0)):
+        raise ValueError(f"no dropout site for encode {encode}, layer {layer}, place {place!r}")
+    return 1 + (encode * MAX_LAYERS + layer) * len(PLACES) + PLACES.index(place)
+
+
 def threshold(p):
     """T = floor(256 p + 0.5) of mdr_dropout_threshold; ValueError for a p outside [0, 1) or one that rounds to 256."""
     T = int(lib().mdr_dropout_threshold(float(p)))

@@ -1,6 +1,7 @@
-"""Dev-set data path of scripts/train_mhop.py --do_predict (mdr/retrieval/data/mhop_dataset.py:12-121 of the reference):
+"""Data path of scripts/train_mhop.py, --do_predict and --do_train (mdr/retrieval/data/mhop_dataset.py:12-121 of the reference):
 
     MhopDataset(tokenizer, data_path, max_q_len, max_q_sp_len, max_c_len)   the eval branch; train=True raises
+    MhopTrainDataset(tokenizer, data_path, max_q_len, max_q_sp_len, max_c_len)   the train branch (--do_train)
     mhop_collate(samples, pad_id=0)
 
 JSONL records: `question`, `type`, `pos_paras` (two {title, text}), `bridge` (title of the second-hop passage, for every type but
@@ -45,14 +46,18 @@ class MhopDataset(torch.utils.data.Dataset):
     def __init__(self, tokenizer, data_path, max_q_len, max_q_sp_len, max_c_len, train=False):
         super().__init__()
         if train:
-            raise NotImplementedError("training is not supported: the retriever runs inference only (--do_predict)")
+            raise NotImplementedError("training is not supported by MhopDataset, the eval branch: the train branch is MhopTrainDataset")
         self.tokenizer = tokenizer
         self.max_q_len, self.max_c_len, self.max_q_sp_len = max_q_len, max_c_len, max_q_sp_len
         self.train = False
         print(f"Loading data from {data_path}")
         with open(data_path) as f:
-            self.data = [json.loads(line) for line in f.readlines()]
+            self.data = self.select([json.loads(line) for line in f.readlines()])
         print(f"Total sample count {len(self.data)}")
+
+    def select(self, data):
+        """The samples of the file this dataset keeps: all of them here; MhopTrainDataset has the train branch's rule."""
+        return data
 
     def encode_para(self, para, max_len):
         return _pair(self.tokenizer, para["title"].strip(), para["text"].strip(), max_len)
@@ -71,6 +76,8 @@ class MhopDataset(torch.utils.data.Dataset):
                     start_para = para
                 else:
                     bridge_para = para
+        if self.train:
+            random.shuffle(sample["neg_paras"])  # behind the comparison shuffle, as in the reference: the two draw from one generator
         return {
             "q_codes": _single(self.tokenizer, question, self.max_q_len),
             "q_sp_codes": _pair(self.tokenizer, question, start_para["text"].strip(), self.max_q_sp_len),
@@ -82,6 +89,23 @@ class MhopDataset(torch.utils.data.Dataset):
 
     def __len__(self):
         return len(self.data)
+
+
+class MhopTrainDataset(MhopDataset):
+    """The train=True branch of the reference's MhopDataset (mhop_dataset.py:30-39, :59-60): `neg_paras` is replaced by `tfidf_neg`, samples
+    with fewer than two negatives are dropped, and every __getitem__ shuffles the sample's negatives in place with the global `random`
+    generator and uses the first two. Deviations: a sample WITHOUT `tfidf_neg` keeps its `neg_paras` (the reference raises KeyError), and
+    the reference's leftover `pdb.set_trace()` is not there."""
+
+    def __init__(self, tokenizer, data_path, max_q_len, max_q_sp_len, max_c_len):
+        super().__init__(tokenizer, data_path, max_q_len, max_q_sp_len, max_c_len)
+        self.train = True
+
+    def select(self, data):
+        for sample in data:
+            if "tfidf_neg" in sample:
+                sample["neg_paras"] = sample["tfidf_neg"]
+        return [s for s in data if len(s["neg_paras"]) >= 2]
 
 
 _KEYS = (("q", "q_codes"), ("q_sp", "q_sp_codes"), ("c1", "start_para_codes"), ("c2", "bridge_para_codes"), ("neg1", "neg_codes_1"),

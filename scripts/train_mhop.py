@@ -1,27 +1,39 @@
-"""Drop-in for the reference's scripts/train_mhop.py at inference (--do_predict): the in-batch-negative MRR of a retriever
-checkpoint on a dev set, the number the reference selects checkpoint_best.pt by, without a corpus index.
+"""Drop-in for the reference's scripts/train_mhop.py: training the multi-hop retriever (--do_train) and the in-batch-negative MRR of a
+retriever checkpoint on a dev set (--do_predict), the number the reference selects checkpoint_best.pt by, without a corpus index.
 
+    python scripts/train_mhop.py --do_train --prefix ${RUN_ID} --predict_batch_size 3000 --model_name <roberta-base dir> \
+        --train_batch_size 150 --learning_rate 2e-5 --fp16 --train_file ${TRAIN_DATA_PATH} --predict_file ${DEV_DATA_PATH} --seed 16 \
+        --eval-period -1 --max_c_len 300 --max_q_len 70 --max_q_sp_len 350 --shared-encoder --warmup-ratio 0.1
     python scripts/train_mhop.py --do_predict --predict_batch_size 3000 --model_name <roberta-base dir> --fp16 \
         --predict_file ${DEV_DATA_PATH} --init_checkpoint q_encoder.pt --seed 16 --max_c_len 300 --max_q_len 70 \
         --max_q_sp_len 350 --shared-encoder --num_workers 0
 
-Flags are the reference's (mdr/retrieval/config.py train_args), parsed verbatim. It logs, through the same logger,
+Flags are the reference's (mdr/retrieval/config.py train_args), parsed verbatim. --do_predict logs, through the same logger,
 `Num of dev batches: ..`, `evaluated {n} examples...`, `MRR-1: ..`, `MRR-2: ..` and `test performance {dict}` with the keys
 mrr_1, mrr_2, mrr_avg. The six forwards of a batch run on the HIP encoder (RobertaRetriever.forward) and the ranks come from
 mdr_inbatch_rank (multihop_dense_retrieval_amd/criterions.py): --fp16 selects apex O1's fp16 scores, otherwise they are fp32.
---do_train exits: training is not supported. One rank.
 
-Deviations from the reference, all outside the numbers it reports: no dated `--output_dir` directory, `log.txt` or TensorBoard
-writer is created (the reference makes them even for --do_predict; an evaluation needs none); the checkpoint is loaded with
-load_saved(exact=False), so buffers a newer transformers saved beside the weights are dropped instead of refused; --model_name
-is a local directory (nothing is downloaded); the batches are loaded in this process whatever --num_workers says, which is also
-the only setting under which the reference's order of the comparison questions' positives (a global random.shuffle at eval
-time, multihop_dense_retrieval_amd/mhop_data.py) is reproducible.
+--do_train is lines 124-227 of the reference's script on multihop_dense_retrieval_amd/train.py, one rank: the two
+weight-decay groups, the linear schedule with warmup, the reference's accumulation boundary ((batch_step + 1) % g == 0, quirk included),
+the smoothed loss meter, --eval-period, the evaluation after every epoch, its log lines, and checkpoint_best.pt / checkpoint_last.pt (plain
+fp32 CPU state dicts with the reference's keys) under output_dir/<date>/<prefix>-seed..-bsz.. with log.txt beside them. The encoder starts
+from the weights in the --model_name directory, project.* from torch's default initialisers under --seed; --init_checkpoint overwrites both.
+Every forward draws its dropout seed from a torch.Generator seeded with --seed. The arithmetic is fp16 with fp32 masters whether or not
+--fp16 is given, so the dynamic loss scale is always on; --fp16 selects the fp16 score mode of the loss, as for --do_predict.
+Not built: --momentum (the reference trains it from a script of its own) and multi-rank training.
+
+Deviations from the reference, all outside the numbers it reports: for --do_predict no dated `--output_dir` directory, `log.txt` or
+TensorBoard writer is created (the reference makes them even there; an evaluation needs none); TensorBoard scalars are written only when
+torch.utils.tensorboard imports; the checkpoint is loaded with load_saved(exact=False), so buffers a newer transformers saved beside the
+weights are dropped instead of refused; --model_name is a local directory (nothing is downloaded); the batches are loaded in this process
+whatever --num_workers says, which is also the only setting under which the reference's order of the comparison questions' positives and
+of the training negatives (global random.shuffle calls, multihop_dense_retrieval_amd/mhop_data.py) is reproducible.
 """
 import logging
 import os
 import random
 import sys
+from datetime import date
 from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -49,17 +61,130 @@ def predict(args, model, eval_dataloader, device, logger):
     return acc
 
 
+class AverageMeter:
+    """utils.py:44-60 of the reference."""
+
+    def __init__(self):
+        self.val, self.avg, self.sum, self.count = 0, 0, 0, 0
+
+    def update(self, val, n=1):
+        self.val = val
+        self.sum += val * n
+        self.count += n
+        self.avg = self.sum / self.count
+
+
+def check_train_inputs(args):
+    """What --do_train needs from the command line, looked at before anything touches the device."""
+    if args.momentum:
+        sys.exit("training with --momentum is not built: the reference trains it from a script of its own")
+    if not os.path.isdir(args.model_name):
+        sys.exit(f"training is not supported with --model_name {args.model_name!r}: it must be a local directory with the RoBERTa config, "
+                 "tokenizer and weights (nothing is downloaded)")
+    for flag, path in (("--train_file", args.train_file), ("--predict_file", args.predict_file)):
+        if not os.path.isfile(path):
+            sys.exit(f"training needs {flag} {path!r}: no such file")
+    if args.init_checkpoint != "" and not os.path.isfile(args.init_checkpoint):
+        sys.exit(f"--init_checkpoint {args.init_checkpoint!r}: no such file")
+    if args.accumulate_gradients < 1:
+        raise ValueError("Invalid accumulate_gradients parameter: {}, should be >= 1".format(args.accumulate_gradients))
+    if args.local_rank != -1:
+        sys.exit("multi-rank training is not built: run one rank (--local_rank -1)")
+
+
+def encoder_weights(model_name, wanted):
+    """{`encoder.` + key: tensor} from the weights in the model directory, loaded on the CPU; {} when the directory holds none."""
+    import transformers
+    try:
+        hf = transformers.AutoModel.from_pretrained(model_name, local_files_only=True)
+    except (OSError, ValueError):
+        return {}
+    return {"encoder." + k: v.detach().float() for k, v in hf.state_dict().items() if "encoder." + k in wanted}
+
+
+def train(args, model, tokenizer, collate_fc, eval_dataloader, device, logger, tb_logger):
+    """train_mhop.py:124-227."""
+    import torch
+    from torch.utils.data import DataLoader
+    from multihop_dense_retrieval_amd import mhop_data, optim
+    from multihop_dense_retrieval_amd import train as mdr_train
+    from multihop_dense_retrieval_amd.retriever import move_to_cuda
+    optimizer = mdr_train.optimizer_for(model, args)
+    global_step, batch_step, best_mrr = 0, 0, 0  # gradient update step; forward batch count
+    train_loss_meter = AverageMeter()
+    model.train()
+    train_dataset = mhop_data.MhopTrainDataset(tokenizer, args.train_file, args.max_q_len, args.max_q_sp_len, args.max_c_len)
+    train_dataloader = DataLoader(train_dataset, batch_size=args.train_batch_size, collate_fn=collate_fc, num_workers=0, shuffle=True)
+    t_total = len(train_dataloader) // args.gradient_accumulation_steps * args.num_train_epochs
+    warmup_steps = t_total * args.warmup_ratio
+    scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lambda s: optim.linear_schedule_with_warmup(s, warmup_steps, t_total))
+    seeds = torch.Generator().manual_seed(args.seed)  # one dropout seed per forward
+    state = {"loss": None}
+
+    def save(name):
+        torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, os.path.join(args.output_dir, name))
+
+    def evaluate():
+        mrrs = predict(args, model.inference(), eval_dataloader, device, logger)
+        model.train()
+        return mrrs
+
+    def step_fn(batch, _batch_step):
+        seed = int(torch.randint(0, 2 ** 62, (1,), generator=seeds))
+        state["loss"] = mdr_train.train_step(model, move_to_cuda(batch), args, optimizer, seed)
+        train_loss_meter.update(state["loss"].item())
+
+    def update_fn(_batch_step):
+        nonlocal global_step, best_mrr
+        optimizer.step()
+        scheduler.step()
+        global_step += 1
+        if tb_logger is not None:
+            tb_logger.add_scalar("batch_train_loss", state["loss"].item(), global_step)
+            tb_logger.add_scalar("smoothed_train_loss", train_loss_meter.avg, global_step)
+        if args.eval_period != -1 and global_step % args.eval_period == 0:
+            mrr = evaluate()["mrr_avg"]
+            logger.info("Step %d Train loss %.2f MRR %.2f on epoch=%d" % (global_step, train_loss_meter.avg, mrr * 100, epoch))
+            if best_mrr < mrr:
+                logger.info("Saving model with best MRR %.2f -> MRR %.2f on epoch=%d" % (best_mrr * 100, mrr * 100, epoch))
+                save("checkpoint_best.pt")
+                best_mrr = mrr
+
+    logger.info("Start training....")
+    for epoch in range(int(args.num_train_epochs)):
+        batch_step = mdr_train.run_epoch(train_dataloader, step_fn, update_fn, args.gradient_accumulation_steps, batch_step)
+        mrrs = evaluate()
+        mrr = mrrs["mrr_avg"]
+        logger.info("Step %d Train loss %.2f MRR-AVG %.2f on epoch=%d" % (global_step, train_loss_meter.avg, mrr * 100, epoch))
+        if tb_logger is not None:
+            for k, v in mrrs.items():
+                tb_logger.add_scalar(k, v * 100, epoch)
+        save("checkpoint_last.pt")
+        if best_mrr < mrr:
+            logger.info("Saving model with best MRR %.2f -> MRR %.2f on epoch=%d" % (best_mrr * 100, mrr * 100, epoch))
+            save("checkpoint_best.pt")
+            best_mrr = mrr
+    logger.info("Training finished!")
+
+
 def main(argv=None):
     from multihop_dense_retrieval_amd.config import train_args
     args = train_args(argv)
+    handlers = [logging.StreamHandler()]
     if args.do_train:
-        sys.exit("training is not supported: this retriever runs inference only (--do_predict)")
+        check_train_inputs(args)
+        model_name = (f"{args.prefix}-seed{args.seed}-bsz{args.train_batch_size}-fp16{args.fp16}-lr{args.learning_rate}-decay{args.weight_decay}"
+                      f"-warm{args.warmup_ratio}-valbsz{args.predict_batch_size}-shared{args.shared_encoder}-multi{args.multi_vector}-scheme{args.scheme}")
+        args.output_dir = os.path.join(args.output_dir, date.today().strftime("%m-%d-%Y"), model_name)
+        if os.path.exists(args.output_dir) and os.listdir(args.output_dir):
+            print(f"output directory {args.output_dir} already exists and is not empty.")
+        os.makedirs(args.output_dir, exist_ok=True)
+        handlers.insert(0, logging.FileHandler(os.path.join(args.output_dir, "log.txt")))
     import numpy as np
     import torch
     from torch.utils.data import DataLoader
     from multihop_dense_retrieval_amd import data, mhop_data, retriever
-    logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S", level=logging.INFO,
-                        handlers=[logging.StreamHandler()])
+    logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S", level=logging.INFO, handlers=handlers)
     logger = logging.getLogger(__name__)
     logger.setLevel(logging.INFO)
     logger.info(args)
@@ -72,9 +197,13 @@ def main(argv=None):
         sys.exit(f"--model_name {args.model_name!r} must be a local directory with the RoBERTa config and tokenizer (nothing is downloaded)")
     import transformers
     bert_config = transformers.AutoConfig.from_pretrained(args.model_name, local_files_only=True)
-    model = retriever.RobertaRetriever(bert_config, args)
     tokenizer = data.load_tokenizer(args.model_name)
     collate_fc = partial(mhop_data.mhop_collate, pad_id=tokenizer.pad_token_id)
+    if args.do_train:
+        args.train_batch_size = int(args.train_batch_size / args.accumulate_gradients)
+        if args.max_c_len > bert_config.max_position_embeddings:
+            raise ValueError("Cannot use sequence length %d because the BERT model was only trained up to sequence length %d" %
+                             (args.max_c_len, bert_config.max_position_embeddings))
     # train_mhop.py:94-98. Seeded HERE, after the imports and the config / tokenizer loading above: importing transformers draws from the global
     # `random` generator, and the comparison questions' order of positives is the generator's state at the first __getitem__. In the reference
     # nothing between its seeding and that point draws from it (the model's initialisation uses torch's generator).
@@ -84,6 +213,30 @@ def main(argv=None):
     eval_dataset = mhop_data.MhopDataset(tokenizer, args.predict_file, args.max_q_len, args.max_q_sp_len, args.max_c_len)
     eval_dataloader = DataLoader(eval_dataset, batch_size=args.predict_batch_size, collate_fn=collate_fc, num_workers=0)
     logger.info(f"Num of dev batches: {len(eval_dataloader)}")
+    if args.do_train:
+        from multihop_dense_retrieval_amd import train as mdr_train
+        model = mdr_train.TrainableRetriever(bert_config, args)  # project.* from torch's default initialisers under --seed
+        start = encoder_weights(args.model_name, model.shapes)
+        if args.init_checkpoint != "":
+            ckpt = torch.load(args.init_checkpoint, map_location="cpu")
+            start.update({(k[7:] if k.startswith("module.") else k): v for k, v in ckpt.items()})
+        start = {k: v for k, v in start.items() if k in model.shapes}
+        missing = [k for k in model.shapes if k.startswith("encoder.") and "pooler" not in k and k not in start]
+        if missing:
+            sys.exit(f"no encoder weights to start from: {args.model_name!r} holds none and --init_checkpoint gives none ({len(missing)} tensors "
+                     f"missing, the first {missing[0]})")
+        model.load_state_dict(start, strict=False)
+        model.to(device)
+        print(f"number of trainable parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+        try:
+            from torch.utils.tensorboard import SummaryWriter
+            tb_logger = SummaryWriter(os.path.join(args.output_dir.replace("logs", "tflogs")))
+        except ImportError:
+            tb_logger = None
+            logger.info("TensorBoard is not installed: its scalars are not written")
+        train(args, model, tokenizer, collate_fc, eval_dataloader, device, logger, tb_logger)
+        return
+    model = retriever.RobertaRetriever(bert_config, args)
     if args.init_checkpoint != "":
         model = retriever.load_saved(model, args.init_checkpoint, exact=False, map_location="cpu")
     model.to(device)
