@@ -386,3 +386,6 @@ int mdr_reader_forward(mdr_reader* h, const int64_t* ids_dev, const int64_t* mas
 }
 
 }  // extern "C"
+
+// the training loss and the heads with gradients (include/mdr_reader_loss.h): the heads' forward is the three kernels above
+#include "mdr_reader_loss.inl"
