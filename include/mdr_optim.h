@@ -33,6 +33,9 @@
  *                 With zero_grads, g becomes +0 whether the step is skipped or not.
  * mdr_optim_ema: k = k * fp32(m) + q * fp32(1 - m) (two multiplies and an add, not contracted) and p16 = fp16(k) where table_k gives one.
  *
+ * include/mdr_optim_adamw.h declares mdr_optim_step_ex, this step with the decay's form as an argument: mode 0 is mdr_optim_step, mode 1
+ * is AdamW (decoupled decay, eps outside the bias correction), which the answer reader trains with.
+ *
  * No atomics: two runs from the same inputs give the same bits in p, m, v, p16 and the state.
  *
  * Validated on the host without a launch, MDR_E_INVALID with mdr_last_error(): a NULL table, state or sizes, a negative or zero size, a

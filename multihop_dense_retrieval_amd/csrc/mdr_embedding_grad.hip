@@ -37,11 +37,28 @@
 //   8. dg += dy * xhat, db += dy and dtype0 += d per token in the wave's order; ((w0 + w1) + w2) + w3 over the waves; the chunks strand
 //      by strand, the strands in order; the old value last. At most rows_per_chunk / 4 + 4 + S + 1 additions per element.
 // Non-finite values propagate by IEEE rules alone: nothing float is clamped, compared or used as an index.
+//
+// The reader's flavour (include/mdr_reader_embedding_grad.h; the forward is reader_embed_ln_kernel of csrc/mdr_reader.inl,
+//     x = (word[clamp(id)] + pos[tok_src % L]) + type[clamp(types[tok_src], 0, TV - 1)]):
+// emb_reader_keys_kernel: emb_keys_kernel with the position row tok_src % L; the header carries MDR_READER_EMBEDDING_PLAN_MAGIC, a pad row PER
+//   TABLE (words 7 and 8; the position table's is -1 for ELECTRA: row 0 is every sequence's [CLS]) and L (word 9). emb_rank_kernel and
+//   emb_segments_kernel serve both kinds; the segments kernel takes the position table's pad row from word 8 when the magic is the reader's.
+//   At most L distinct position rows, row p owning one token of every sequence longer than p: long segments, summed in the pieces above.
+// emb_scatter_kernel is told the plan kind it differentiates (magic, L): a plan of the other kind, or of another L, makes it do nothing.
+// emb_reader_ln_grad_kernel: emb_ln_grad_kernel's chunks, wave walk and expressions (rounding points 1 - 6 with t0 replaced by the token's
+//   type row; 8 for dg and db). The type gradient is one plane per type row, TV <= 4: a token adds its STORED d (never fused, as point 6 says
+//   of dtype0) to the plane of its own row and to no other, in the wave's token order (the planes are kept in LDS, one set per wave; the
+//   kernel is a template over H / 64, which keeps it out of register spills); per plane the four waves are added ((w0 + w1) + w2) + w3 into part_ty [S][TV][H]; one
+//   grad_strand_reduce_kernel over rows of TV * H columns
+//   adds the chunks strand by strand, then the old value. dtype[k] therefore has the chunk, wave and strand split of dtype0 (a function of
+//   (cap, H) alone) over the tokens of type k: at most rows_per_chunk / 4 + 4 + S + 1 additions per element, fewer where other types own
+//   tokens. dg and db go through part_gb [S][2][H] and the same reduce. Without types every token is type 0, and dtype[0] has dtype0's bits.
 #include <algorithm>
 #include <climits>
 
 #include "mdr_grad_common.h"
 #include "../../include/mdr_embedding_grad.h"
+#include "../../include/mdr_reader_embedding_grad.h"
 
 namespace mdr {
 namespace {
@@ -65,7 +82,9 @@ constexpr int kEgScatterThreads = 64 * kEgScatterWaves;
 constexpr int kEgScatterGrid = 1 << 16;                 // most workgroups of emb_scatter_kernel per table
 constexpr int kEgPlanes = 3;                            // dg, db, dtype0: the partial sums are [S][3][H] (the scatter's [S][1][H] uses the same split)
 
-enum { kHdrMagic = 0, kHdrTotal, kHdrSegWord, kHdrSegPos, kHdrCap, kHdrVocab, kHdrMaxPos, kHdrPadRow };
+// kHdrPadPos and kHdrL are the reader plan's (MDR_READER_EMBEDDING_PLAN_MAGIC); a retriever plan leaves words 8 .. 15 zero
+enum { kHdrMagic = 0, kHdrTotal, kHdrSegWord, kHdrSegPos, kHdrCap, kHdrVocab, kHdrMaxPos, kHdrPadRow, kHdrPadPos, kHdrL };
+constexpr int kEgMaxTypes = MDR_READER_EMBEDDING_MAX_TYPES;
 
 __host__ __device__ inline int eg_table_stride(int cap) { return (3 * cap + 1 + 3) / 4 * 4; }
 __host__ __device__ inline int eg_table_off(int cap, int tbl) { return kEgHeader + tbl * eg_table_stride(cap); }
@@ -98,6 +117,33 @@ __global__ void __launch_bounds__(256) emb_keys_kernel(const long long* __restri
     pid = pid >= max_pos ? max_pos - 1 : (pid < 0 ? 0 : pid);
     plan[eg_keys_off(cap, 0) + t] = (int)id;
     plan[eg_keys_off(cap, 1) + t] = pid;
+}
+
+// the reader's keys: the position row is tok_src % L (no tok_pid), and the header carries the plan kind's magic, a pad row per table and L
+__global__ void __launch_bounds__(256) emb_reader_keys_kernel(const long long* __restrict__ ids, const int* __restrict__ tok_src, const int* __restrict__ total_dev,
+                                                              int cap, int L, int vocab, int max_pos, int pad_word, int pad_pos, int* __restrict__ plan) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int total = eg_total(total_dev, cap);
+    if (t < kEgHeader) {
+        int v = 0;
+        if (t == kHdrMagic) v = MDR_READER_EMBEDDING_PLAN_MAGIC;
+        if (t == kHdrTotal) v = total;
+        if (t == kHdrCap) v = cap;
+        if (t == kHdrVocab) v = vocab;
+        if (t == kHdrMaxPos) v = max_pos;
+        if (t == kHdrPadRow) v = pad_word;
+        if (t == kHdrPadPos) v = pad_pos;
+        if (t == kHdrL) v = L;
+        if (t != kHdrSegWord && t != kHdrSegPos) plan[t] = v;  // (the segment counts are emb_segments_kernel's)
+    }
+    if (t >= total) return;
+    const int src = tok_src[t];
+    long long id = ids[src];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    int p = src % L;  // < L <= max_pos (checked on the host); the clamp keeps a negative tok_src, which the forward does not allow, in bounds
+    p = p < 0 ? 0 : p;
+    plan[eg_keys_off(cap, 0) + t] = (int)id;
+    plan[eg_keys_off(cap, 1) + t] = p;
 }
 
 __global__ void __launch_bounds__(kEgThreads) emb_rank_kernel(int* __restrict__ plan, int cap) {
@@ -150,7 +196,9 @@ __global__ void __launch_bounds__(kEgThreads) emb_rank_kernel(int* __restrict__ 
 __global__ void __launch_bounds__(kEgSegThreads) emb_segments_kernel(int* __restrict__ plan, int cap) {
     __shared__ int wsum[kEgSegThreads / 64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, tbl = blockIdx.x;
-    const int total = plan[kHdrTotal], pad_row = plan[kHdrPadRow];
+    const int total = plan[kHdrTotal];
+    // a retriever plan has one pad row for both tables; a reader plan one per table
+    const int pad_row = tbl && plan[kHdrMagic] == MDR_READER_EMBEDDING_PLAN_MAGIC ? plan[kHdrPadPos] : plan[kHdrPadRow];
     const int* keys = plan + eg_keys_off(cap, tbl);
     int* order = plan + eg_table_off(cap, tbl);
     int* seg_start = order + cap;
@@ -219,12 +267,14 @@ __device__ __forceinline__ void eg_piece_sum(const float* __restrict__ d32, int 
 }
 
 __global__ void __launch_bounds__(kEgScatterThreads)
-emb_scatter_kernel(const float* __restrict__ d32, const int* __restrict__ plan, int cap, int H, int vocab, int max_pos, float* dword, float* dpos, int accumulate) {
+emb_scatter_kernel(const float* __restrict__ d32, const int* __restrict__ plan, int magic, int L, int cap, int H, int vocab, int max_pos, float* dword, float* dpos,
+                   int accumulate) {
     __shared__ float red[kEgScatterWaves][kEgMaxH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tbl = blockIdx.y;
     float* out = tbl ? dpos : dword;
     if (!out) return;  // (uniform over the workgroup, as is every branch below but those on `wave`, `lane` and `tid`)
-    if (plan[kHdrMagic] != MDR_EMBEDDING_PLAN_MAGIC || plan[kHdrCap] != cap || plan[kHdrVocab] != vocab || plan[kHdrMaxPos] != max_pos) return;
+    // (magic, L): the plan kind the caller differentiates -- a retriever plan holds 0 at kHdrL. A plan of the other kind does nothing.
+    if (plan[kHdrMagic] != magic || plan[kHdrL] != L || plan[kHdrCap] != cap || plan[kHdrVocab] != vocab || plan[kHdrMaxPos] != max_pos) return;
     const int nseg = min(plan[kHdrSegWord + tbl], plan[kHdrTotal]);
     const int* order = plan + eg_table_off(cap, tbl);
     const int* seg_start = order + cap;
@@ -379,14 +429,116 @@ emb_colsum_kernel(const float* __restrict__ d32, const int* __restrict__ plan, i
     eg_store_partials<1>(red, sums, nl, H, part);
 }
 
+// The reader's flavour of emb_ln_grad_kernel (the forward is reader_embed_ln_kernel of csrc/mdr_reader.inl): the position row is tok_src % L, the
+// type row clamp(types[tok_src], 0, TV - 1) of a [TV, H] table (row 0 without types). Same chunks, same wave walk, same d; the type gradient
+// is one plane per type row: a token adds its d to the plane of its own row only. The planes live in LDS, one set per wave (a lane owns its
+// columns lane + 64 i of its wave's planes, so the walk needs no barrier). NL = H / 64 is a template argument here: with the other flavour's
+// sixteen `i < nl` tests and this one's longer argument list the scalar registers no longer sufficed. part_gb [S][2][H] (dg, db), part_ty [S][TV][H].
+template <int NL>
+__global__ void __launch_bounds__(kEgThreads)
+emb_reader_ln_grad_kernel(const long long* __restrict__ ids, const long long* __restrict__ types, const int* __restrict__ tok_src, const int* __restrict__ total_dev,
+                          int cap, int L, const float* __restrict__ word, const float* __restrict__ pos, const float* __restrict__ type_emb, int TV,
+                          const float* __restrict__ g, int vocab, float eps, const _Float16* __restrict__ dy16, const void* __restrict__ dy2, int dy2_f32, int rpc,
+                          float* __restrict__ d32, float* __restrict__ part_gb, float* __restrict__ part_ty) {
+    constexpr int H = 64 * NL;
+    __shared__ float ts[kEgWaves][kEgMaxTypes][H];  // dtype[k] of each wave; afterwards planes 0 and 1 carry the waves' dg and db
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int total = eg_total(total_dev, cap);
+    const int r0 = blockIdx.x * rpc, r1 = min(r0 + rpc, total);
+
+    float gv[NL], sums[2][NL];  // sums: dg, db
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+        gv[i] = g[lane + 64 * i];
+        sums[0][i] = sums[1][i] = 0.f;
+    }
+    for (int k = 0; k < TV; ++k)
+#pragma unroll
+        for (int i = 0; i < NL; ++i) ts[wave][k][lane + 64 * i] = 0.f;
+    for (int t = r0 + wave; t < r1; t += kEgWaves) {
+        const int src = tok_src[t];
+        int p = src % L;
+        p = p < 0 ? 0 : p;
+        long long id = ids[src];
+        id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+        long long tyl = types ? types[src] : 0;
+        const int ty = (int)(tyl < 0 ? 0 : (tyl >= TV ? TV - 1 : tyl));  // (uniform over the wave)
+        const float* wr = word + (size_t)id * H + lane;
+        const float* pr = pos + (size_t)p * H + lane;
+        const float* tr = type_emb + (size_t)ty * H + lane;
+        float* tsr = &ts[wave][ty][lane];
+        const size_t off = (size_t)t * H + lane;
+        float x[NL], dy[NL];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            const int e = 64 * i;
+            x[i] = wr[e] + pr[e] + tr[e];
+            s += x[i];
+            if (dy16) {
+                dy[i] = (float)dy16[off + e];
+                if (dy2) dy[i] += dy2_f32 ? ((const float*)dy2)[off + e] : (float)((const _Float16*)dy2)[off + e];
+            } else {
+                dy[i] = dy2_f32 ? ((const float*)dy2)[off + e] : (float)((const _Float16*)dy2)[off + e];
+            }
+        }
+        const float mu = grad_wave_sum(s) / H;
+        float v = 0.f;
+#pragma unroll
+        for (int i = 0; i < NL; ++i) { const float dlt = x[i] - mu; v += dlt * dlt; }
+        const float rstd = rsqrtf(grad_wave_sum(v) / H + eps);
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            const float xh = (x[i] - mu) * rstd;
+            const float a = dy[i] * gv[i];
+            s1 += a;
+            s2 += a * xh;
+            sums[0][i] += dy[i] * xh;
+            sums[1][i] += dy[i];
+            x[i] = xh;
+            dy[i] = a;
+        }
+        const float c1 = grad_wave_sum(s1) / H, c2 = grad_wave_sum(s2) / H;
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            const float d = rstd * ((dy[i] - c1) - x[i] * c2);
+            {
+                // dtype adds the d that is STORED, never fused with the product (emb_ln_grad_kernel's rule)
+#pragma clang fp contract(off)
+                tsr[64 * i] += d;
+            }
+            d32[off + 64 * i] = d;
+        }
+    }
+    __syncthreads();
+    if (part_ty)
+        for (int k = 0; k < TV; ++k)
+            for (int e = tid; e < H; e += kEgThreads)
+                part_ty[((size_t)blockIdx.x * TV + k) * H + e] = ((ts[0][k][e] + ts[1][k][e]) + ts[2][k][e]) + ts[3][k][e];
+    if (!part_gb) return;  // (uniform)
+    __syncthreads();  // the type planes are read: planes 0 and 1 now carry dg and db, added as eg_store_partials adds them
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+        for (int i = 0; i < NL; ++i) ts[wave][pl][lane + 64 * i] = sums[pl][i];
+    __syncthreads();
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl)
+        for (int e = tid; e < H; e += kEgThreads)
+            part_gb[((size_t)blockIdx.x * 2 + pl) * H + e] = ((ts[0][pl][e] + ts[1][pl][e]) + ts[2][pl][e]) + ts[3][pl][e];
+}
+
 // the table half of both entry points: accumulate = 0 zeroes the given tables first
-int eg_launch_tables(const float* d32, const int* plan, int cap, int H, int vocab, int max_pos, float* dword, float* dpos, int accumulate, hipStream_t st) {
+int eg_launch_tables(const float* d32, const int* plan, int magic, int L, int cap, int H, int vocab, int max_pos, float* dword, float* dpos, int accumulate,
+                     hipStream_t st) {
     if (!dword && !dpos) return MDR_OK;
     if (!accumulate) {
         if (dword) MDR_HIP_TRY(hipMemsetAsync(dword, 0, (size_t)vocab * H * sizeof(float), st));
         if (dpos) MDR_HIP_TRY(hipMemsetAsync(dpos, 0, (size_t)max_pos * H * sizeof(float), st));
     }
-    hipLaunchKernelGGL(emb_scatter_kernel, dim3(std::min(cap, kEgScatterGrid), 2), dim3(kEgScatterThreads), 0, st, d32, plan, cap, H, vocab, max_pos, dword, dpos, accumulate);
+    hipLaunchKernelGGL(emb_scatter_kernel, dim3(std::min(cap, kEgScatterGrid), 2), dim3(kEgScatterThreads), 0, st, d32, plan, magic, L, cap, H,
+                       vocab, max_pos, dword, dpos, accumulate);
     MDR_HIP_TRY(hipGetLastError());
     return MDR_OK;
 }
@@ -474,7 +626,7 @@ int mdr_embedding_scatter(const float* d32_dev, const void* plan_dev, int cap, i
         MDR_HIP_TRY(hipGetLastError());
         if (int rc = launch_strand_reduce(part, S, 1, H, dtype0_dev, nullptr, nullptr, accumulate, st)) return rc;
     }
-    return eg_launch_tables(d32_dev, plan, cap, H, vocab, max_pos, dword_dev, dpos_dev, accumulate, st);
+    return eg_launch_tables(d32_dev, plan, MDR_EMBEDDING_PLAN_MAGIC, 0, cap, H, vocab, max_pos, dword_dev, dpos_dev, accumulate, st);
 }
 
 int mdr_embedding_backward(const int64_t* ids_dev, const int* tok_src_dev, const int* tok_pid_dev, const int* total_dev, int cap, const float* word_dev,
@@ -512,7 +664,98 @@ int mdr_embedding_backward(const int64_t* ids_dev, const int* tok_src_dev, const
     MDR_HIP_TRY(hipGetLastError());
     if (part)
         if (int rc = launch_strand_reduce(part, S, kEgPlanes, H, dg_dev, db_dev, dtype0_dev, accumulate, st)) return rc;
-    return eg_launch_tables(d32, (const int*)plan_dev, cap, H, vocab, max_pos, dword_dev, dpos_dev, accumulate, st);
+    return eg_launch_tables(d32, (const int*)plan_dev, MDR_EMBEDDING_PLAN_MAGIC, 0, cap, H, vocab, max_pos, dword_dev, dpos_dev, accumulate, st);
+}
+
+// ---- the reader's flavour (include/mdr_reader_embedding_grad.h) ------------------------------------------------------------------------
+int mdr_reader_embedding_plan(const int64_t* ids_dev, const int* tok_src_dev, const int* total_dev, int cap, int L, int vocab, int max_pos, int pad_word,
+                              int pad_pos, void* plan_dev, size_t plan_bytes, int device, void* stream) {
+    using namespace mdr;
+    const char* fn = "mdr_reader_embedding_plan";
+    MDR_REQUIRE(ids_dev && tok_src_dev && total_dev, "%s: NULL pointer (ids, tok_src and total are required)", fn);
+    MDR_REQUIRE(eg_cap_ok(cap), "%s: cap=%d out of range (1 .. 2^20)", fn, cap);
+    MDR_REQUIRE(vocab >= 1 && vocab <= kEgMaxVocab, "%s: vocab=%d out of range (1 .. 2^20)", fn, vocab);
+    MDR_REQUIRE(max_pos >= 1 && max_pos <= kEgMaxPos, "%s: max_pos=%d out of range (1 .. 2^16)", fn, max_pos);
+    MDR_REQUIRE(L >= 1 && L <= max_pos, "%s: L=%d out of range (1 .. max_pos=%d)", fn, L, max_pos);
+    MDR_REQUIRE(pad_word >= -1 && pad_word < kEgMaxVocab, "%s: pad_word=%d out of range (-1 .. 2^20 - 1)", fn, pad_word);
+    MDR_REQUIRE(pad_pos >= -1 && pad_pos < kEgMaxPos, "%s: pad_pos=%d out of range (-1 .. 2^16 - 1)", fn, pad_pos);
+    MDR_REQUIRE(aligned16({plan_dev}), "%s: the plan must be 16-byte aligned", fn);
+    const size_t need = eg_plan_words(cap) * sizeof(int);
+    if (!(plan_dev && plan_bytes >= need))
+        return set_error(MDR_E_WORKSPACE, "%s: plan buffer of %zu bytes, need %zu (mdr_embedding_plan_bytes)", fn, plan_dev ? plan_bytes : (size_t)0, need);
+    MDR_ENTER_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    int* plan = (int*)plan_dev;
+    hipLaunchKernelGGL(emb_reader_keys_kernel, dim3((std::max(cap, kEgHeader) + 255) / 256), dim3(256), 0, st, (const long long*)ids_dev, tok_src_dev, total_dev, cap, L,
+                       vocab, max_pos, pad_word, pad_pos, plan);
+    MDR_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(emb_rank_kernel, dim3((cap + 63) / 64, 2), dim3(kEgThreads), 0, st, plan, cap);
+    MDR_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(emb_segments_kernel, dim3(2), dim3(kEgSegThreads), 0, st, plan, cap);
+    MDR_HIP_TRY(hipGetLastError());
+    return MDR_OK;
+}
+
+size_t mdr_reader_embedding_backward_workspace_bytes(int cap, int H, int type_vocab) {
+    using namespace mdr;
+    if (!(eg_cap_ok(cap) && grad_hidden_ok(H) && type_vocab >= 1 && type_vocab <= kEgMaxTypes)) return 0;
+    int rpc;
+    const size_t S = (size_t)grad_row_chunks(cap, H, kEgPlanes, &rpc);
+    return align_up((size_t)cap * H * sizeof(float), 256) + align_up(S * 2 * H * sizeof(float), 256) + align_up(S * type_vocab * H * sizeof(float), 256);
+}
+
+int mdr_reader_embedding_backward(const int64_t* ids_dev, const int64_t* types_dev, const int* tok_src_dev, const int* total_dev, int cap, int L,
+                                  const float* word_dev, const float* pos_dev, const float* type_dev, int type_vocab, const float* g_dev, int H, int vocab,
+                                  int max_pos, float eps, const void* dy16_dev, const void* dy2_dev, int dy2_f32, const void* plan_dev, float* dword_dev,
+                                  float* dpos_dev, float* dtype_dev, float* dg_dev, float* db_dev, float* d32_dev, int accumulate, void* workspace_dev,
+                                  size_t workspace_bytes, int device, void* stream) {
+    using namespace mdr;
+    const char* fn = "mdr_reader_embedding_backward";
+    MDR_REQUIRE(ids_dev && tok_src_dev && total_dev, "%s: NULL pointer (ids, tok_src and total are required; types may be NULL)", fn);
+    MDR_REQUIRE(word_dev && pos_dev && type_dev && g_dev, "%s: NULL pointer (word, pos, type and g are required)", fn);
+    MDR_REQUIRE(dy16_dev || dy2_dev, "%s: NULL pointer (dy16 and dy2: at least one is required)", fn);
+    MDR_REQUIRE(dword_dev || dpos_dev || dtype_dev || dg_dev || db_dev || d32_dev, "%s: NULL pointer (every output: at least one is required)", fn);
+    MDR_REQUIRE(plan_dev || !(dword_dev || dpos_dev), "%s: NULL pointer (dword and dpos need the plan)", fn);
+    MDR_REQUIRE(dy2_f32 == 0 || dy2_f32 == 1, "%s: dy2_f32 must be 0 or 1, got %d", fn, dy2_f32);
+    MDR_REQUIRE(accumulate == 0 || accumulate == 1, "%s: accumulate must be 0 or 1, got %d", fn, accumulate);
+    MDR_REQUIRE(eg_cap_ok(cap), "%s: cap=%d out of range (1 .. 2^20)", fn, cap);
+    MDR_REQUIRE(grad_hidden_ok(H), "%s: H=%d unsupported (a multiple of 64, 64 .. 1024)", fn, H);
+    MDR_REQUIRE(vocab >= 1 && vocab <= kEgMaxVocab, "%s: vocab=%d out of range (1 .. 2^20)", fn, vocab);
+    MDR_REQUIRE(max_pos >= 1 && max_pos <= kEgMaxPos, "%s: max_pos=%d out of range (1 .. 2^16)", fn, max_pos);
+    MDR_REQUIRE(L >= 1 && L <= max_pos, "%s: L=%d out of range (1 .. max_pos=%d)", fn, L, max_pos);
+    MDR_REQUIRE(type_vocab >= 1 && type_vocab <= kEgMaxTypes, "%s: type_vocab=%d out of range (1 .. %d)", fn, type_vocab, kEgMaxTypes);
+    MDR_REQUIRE(aligned16({word_dev, pos_dev, type_dev, g_dev, dy16_dev, dy2_dev, plan_dev, dword_dev, dpos_dev, dtype_dev, dg_dev, db_dev, d32_dev,
+                              workspace_dev}),
+                "%s: every float, plan and workspace pointer must be 16-byte aligned", fn);
+    int rpc;
+    const int S = grad_row_chunks(cap, H, kEgPlanes, &rpc);  // the split of mdr_embedding_backward_chunks: a function of (cap, H) alone
+    const size_t d_bytes = align_up((size_t)cap * H * sizeof(float), 256);
+    const size_t gb_bytes = align_up((size_t)S * 2 * H * sizeof(float), 256);
+    const size_t need = d_bytes + gb_bytes + (size_t)S * type_vocab * H * sizeof(float);
+    MDR_REQUIRE_WORKSPACE(fn, workspace_dev, workspace_bytes, need, "mdr_reader_embedding_backward_workspace_bytes");
+    MDR_ENTER_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    float* d32 = d32_dev ? d32_dev : (float*)workspace_dev;
+    float* part_gb = dg_dev || db_dev ? (float*)((char*)workspace_dev + d_bytes) : nullptr;
+    float* part_ty = dtype_dev ? (float*)((char*)workspace_dev + d_bytes + gb_bytes) : nullptr;
+#define MDR_EG_READER(NL)                                                                                                                                          \
+    case NL:                                                                                                                                                       \
+        hipLaunchKernelGGL(emb_reader_ln_grad_kernel<NL>, dim3(S), dim3(kEgThreads), 0, st, (const long long*)ids_dev, (const long long*)types_dev, tok_src_dev,  \
+                           total_dev, cap, L, word_dev, pos_dev, type_dev, type_vocab, g_dev, vocab, eps, (const _Float16*)dy16_dev, dy2_dev, dy2_f32, rpc, d32,   \
+                           part_gb, part_ty);                                                                                                                      \
+        break;
+    switch (H >> 6) {  // (1 .. 16: grad_hidden_ok)
+        MDR_EG_READER(1) MDR_EG_READER(2) MDR_EG_READER(3) MDR_EG_READER(4) MDR_EG_READER(5) MDR_EG_READER(6) MDR_EG_READER(7) MDR_EG_READER(8)
+        MDR_EG_READER(9) MDR_EG_READER(10) MDR_EG_READER(11) MDR_EG_READER(12) MDR_EG_READER(13) MDR_EG_READER(14) MDR_EG_READER(15) MDR_EG_READER(16)
+    }
+#undef MDR_EG_READER
+    MDR_HIP_TRY(hipGetLastError());
+    if (part_gb)
+        if (int rc = launch_strand_reduce(part_gb, S, 2, H, dg_dev, db_dev, nullptr, accumulate, st)) return rc;
+    // the type table's planes are [S][type_vocab * H]: one strand reduce over rows of type_vocab * H columns writes dtype [type_vocab, H]
+    if (part_ty)
+        if (int rc = launch_strand_reduce(part_ty, S, 1, type_vocab * H, dtype_dev, nullptr, nullptr, accumulate, st)) return rc;
+    return eg_launch_tables(d32, (const int*)plan_dev, MDR_READER_EMBEDDING_PLAN_MAGIC, L, cap, H, vocab, max_pos, dword_dev, dpos_dev, accumulate, st);
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@
 // written element by element, so nothing behind a tensor's n is touched. The grids are capped at 2048 workgroups and stride over the chunks.
 //   optim_norm_kernel      chunk c -> slot c of the workspace: {fp32 sum of (g / loss_scale)^2, some g is not finite}
 //   optim_finalize_kernel  one workgroup of 1024: the slots -> grad_norm, clip_coef, mult and the loss scaler's next state
-//   optim_update_kernel    Adam on every element of every tensor with a g; zeroes g
+//   optim_update_kernel    Adam (<0>) or AdamW (<1>) on every element of every tensor with a g; zeroes g
 //   optim_ema_kernel       k = k * m + q * (1 - m)
 //
 // Rounding points. Every operation is fp32 unless said otherwise, and NOTHING is contracted into an FMA (the pragma below: the kernels are
@@ -31,6 +31,17 @@
 //                     m = beta1 * m + omb1 * gd      v = beta2 * v + (omb2 * gd) * gd
 //                     denom = sqrt(v) / bc2 + eps    p = p - step_size * (m / denom)      p16 = fp16(p), round to nearest even
 //      Divide and sqrt are the correctly rounded ones (hipcc's default for fp32).
+//  5w. update with decay_mode = MDR_OPTIM_DECAY_DECOUPLED (mdr_optim_step_ex, include/mdr_optim_adamw.h): transformers.AdamW with
+//      correct_bias=True as the reference's scripts/train_qa.py ran it -- as remembered, not captured: no copy of that class is at hand.
+//      Once per thread: omb1 = 1 - beta1, omb2 = 1 - beta2, bc2 = sqrt(bias2), t = lr * bc2, step = t / bias1.
+//      Per element, in this order:
+//                     gh = g * mult                  (no decay enters gh)
+//                     m = beta1 * m + omb1 * gh      v = beta2 * v + (omb2 * gh) * gh
+//                     denom = sqrt(v) + eps          (eps OUTSIDE the bias correction)
+//                     q = m / denom                  p = p - step * q
+//                     only where weight_decay != 0:  w = lr * weight_decay      p = p - w * p     (the UPDATED p)
+//                     p16 = fp16(p)
+//      Norm, finalize, skip, loss scale, zero_grads and the state are mode 0's, unchanged. Mode 0 through mdr_optim_step_ex is mdr_optim_step.
 //   6. EMA: mf = fp32(m), omf = fp32(1 - m) with the subtraction in double on the host; k = k * mf + q * omf; p16 = fp16(k).
 // Non-finite values: the flag is the exponent test on g's bits; a non-finite sum skips as well. Nothing non-finite is used as an index.
 #include <algorithm>
@@ -38,6 +49,7 @@
 
 #include "mdr_common.h"
 #include "../../include/mdr_optim.h"
+#include "../../include/mdr_optim_adamw.h"
 
 #pragma clang fp contract(off)
 
@@ -218,8 +230,19 @@ struct OptAdam {
     float mult, beta1, beta2, omb1, omb2, step_size, bc2, eps;
 };
 
+// MODE 0 (MDR_OPTIM_DECAY_L2): torch.optim.Adam, rounding point 5. MODE 1 (MDR_OPTIM_DECAY_DECOUPLED): AdamW, rounding point 5w, where
+// k.step_size holds lr * sqrt(bias2) / bias1 and k.bc2 holds lr (the decay's factor is lr * weight_decay, formed per element: one multiply).
+template <int MODE>
 __device__ __forceinline__ void opt_adam(float g, float wd, const OptAdam& k, float& p, float& m, float& v) {
     float gd = g * k.mult;
+    if constexpr (MODE == 1) {
+        m = k.beta1 * m + k.omb1 * gd;
+        v = k.beta2 * v + (k.omb2 * gd) * gd;
+        const float denom = __builtin_sqrtf(v) + k.eps;
+        p = p - k.step_size * (m / denom);
+        if (wd != 0.f) p = p - (k.bc2 * wd) * p;
+        return;
+    }
     if (wd != 0.f) gd = gd + wd * p;
     m = k.beta1 * m + k.omb1 * gd;
     v = k.beta2 * v + (k.omb2 * gd) * gd;
@@ -227,6 +250,7 @@ __device__ __forceinline__ void opt_adam(float g, float wd, const OptAdam& k, fl
     p = p - k.step_size * (m / denom);
 }
 
+template <int MODE>
 __global__ void __launch_bounds__(kOptThreads)
 optim_update_kernel(const mdr_optim_tensor* __restrict__ tab, const OptMap* __restrict__ map, int n_chunks, const mdr_optim_state* __restrict__ state, float lr,
                     float beta1, float beta2, float eps, int zero_grads) {
@@ -239,8 +263,13 @@ optim_update_kernel(const mdr_optim_tensor* __restrict__ tab, const OptMap* __re
     k.beta2 = beta2;
     k.omb1 = 1.f - beta1;
     k.omb2 = 1.f - beta2;
-    k.step_size = lr / state->bias1;
-    k.bc2 = __builtin_sqrtf(state->bias2);
+    if constexpr (MODE == 1) {
+        k.step_size = (lr * __builtin_sqrtf(state->bias2)) / state->bias1;
+        k.bc2 = lr;
+    } else {
+        k.step_size = lr / state->bias1;
+        k.bc2 = __builtin_sqrtf(state->bias2);
+    }
     k.eps = eps;
     const of32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
@@ -279,7 +308,7 @@ optim_update_kernel(const mdr_optim_tensor* __restrict__ tab, const OptMap* __re
                     pe[i] = pv[j][i];
                     me[i] = mv[j][i];
                     ve[i] = vv[j][i];
-                    opt_adam(gv[j][i], wd, k, pe[i], me[i], ve[i]);
+                    opt_adam<MODE>(gv[j][i], wd, k, pe[i], me[i], ve[i]);
                 }
                 opt_st((gf32x4*)(p + e), (of32x4){pe[0], pe[1], pe[2], pe[3]});
                 opt_st((gf32x4*)(m + e), (of32x4){me[0], me[1], me[2], me[3]});
@@ -295,7 +324,7 @@ optim_update_kernel(const mdr_optim_tensor* __restrict__ tab, const OptMap* __re
                     if (e >= len) break;
                     if (!skipped) {
                         float pe = p[e], me = m[e], ve = v[e];
-                        opt_adam(g[e], wd, k, pe, me, ve);
+                        opt_adam<MODE>(g[e], wd, k, pe, me, ve);
                         p[e] = pe;
                         m[e] = me;
                         v[e] = ve;
@@ -440,8 +469,17 @@ int mdr_optim_state_init(mdr_optim_state* state_dev, float loss_scale, int devic
 int mdr_optim_step(const void* table_dev, int n_tensors, int n_chunks, mdr_optim_state* state_dev, float lr, float beta1, float beta2, float eps,
                    float max_grad_norm, int dynamic, int scale_window, float max_scale, int zero_grads, void* workspace_dev, size_t workspace_bytes,
                    int device, void* stream) {
+    return mdr_optim_step_ex(table_dev, n_tensors, n_chunks, state_dev, lr, beta1, beta2, eps, max_grad_norm, dynamic, scale_window, max_scale, zero_grads,
+                             MDR_OPTIM_DECAY_L2, workspace_dev, workspace_bytes, device, stream);
+}
+
+int mdr_optim_step_ex(const void* table_dev, int n_tensors, int n_chunks, mdr_optim_state* state_dev, float lr, float beta1, float beta2, float eps,
+                      float max_grad_norm, int dynamic, int scale_window, float max_scale, int zero_grads, int decay_mode, void* workspace_dev,
+                      size_t workspace_bytes, int device, void* stream) {
     using namespace mdr;
-    const char* fn = "mdr_optim_step";
+    const char* fn = decay_mode == MDR_OPTIM_DECAY_L2 ? "mdr_optim_step" : "mdr_optim_step_ex";
+    MDR_REQUIRE(decay_mode == MDR_OPTIM_DECAY_L2 || decay_mode == MDR_OPTIM_DECAY_DECOUPLED, "%s: decay_mode must be 0 (L2, Adam) or 1 (decoupled, AdamW), got %d", fn,
+                decay_mode);
     MDR_REQUIRE(table_dev && state_dev, "%s: NULL pointer (table and state are required)", fn);
     MDR_REQUIRE(n_tensors >= 1, "%s: n_tensors=%d must be at least 1", fn, n_tensors);
     MDR_REQUIRE(n_chunks >= n_tensors, "%s: n_chunks=%d is less than n_tensors=%d (mdr_optim_chunks)", fn, n_chunks, n_tensors);
@@ -467,7 +505,10 @@ int mdr_optim_step(const void* table_dev, int n_tensors, int n_chunks, mdr_optim
     hipLaunchKernelGGL(optim_finalize_kernel, dim3(1), dim3(kOptFinalThreads), 0, st, slots, n_chunks, state_dev, beta1, beta2, max_grad_norm, dynamic,
                        scale_window, max_scale);
     MDR_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(optim_update_kernel, grid, dim3(kOptThreads), 0, st, tab, map, n_chunks, state_dev, lr, beta1, beta2, eps, zero_grads);
+    if (decay_mode == MDR_OPTIM_DECAY_DECOUPLED)
+        hipLaunchKernelGGL(optim_update_kernel<1>, grid, dim3(kOptThreads), 0, st, tab, map, n_chunks, state_dev, lr, beta1, beta2, eps, zero_grads);
+    else
+        hipLaunchKernelGGL(optim_update_kernel<0>, grid, dim3(kOptThreads), 0, st, tab, map, n_chunks, state_dev, lr, beta1, beta2, eps, zero_grads);
     MDR_HIP_TRY(hipGetLastError());
     return MDR_OK;
 }

@@ -1,7 +1,7 @@
 """The optimizer step of the retriever's training loop on the device, and the momentum encoder's EMA:
 
     opt = FusedAdam(params_or_groups, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, max_grad_norm=2.0, loss_scale="dynamic",
-                    scale_window=2000, fp16_copies=False)
+                    scale_window=2000, fp16_copies=False, decoupled_weight_decay=False)
     opt.scale_loss(loss).backward(); opt.step()
     momentum_update(params_k, params_q, m)
     linear_schedule_with_warmup(step, warmup_steps, total_steps)
@@ -43,6 +43,12 @@ SIGNATURES = {
     "mdr_optim_ema": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
+# include/mdr_optim_adamw.h: mdr_optim_step with the decay's form as an argument behind zero_grads
+ADAMW_SIGNATURES = {
+    "mdr_optim_step_ex": (_c.c_int, SIGNATURES["mdr_optim_step"][1][:13] + [_c.c_int] + SIGNATURES["mdr_optim_step"][1][13:]),
+}
+ADAMW_EXPORTED_SYMBOLS = tuple(ADAMW_SIGNATURES)
+DECAY_L2, DECAY_DECOUPLED = 0, 1  # MDR_OPTIM_DECAY_L2, MDR_OPTIM_DECAY_DECOUPLED
 # struct mdr_optim_tensor and struct mdr_optim_state
 TENSOR_DTYPE = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("p16", "<u8"), ("n", "<i8"), ("weight_decay", "<f4"),
                          ("reserved0", "<i4"), ("reserved1", "<i8")])
@@ -50,7 +56,7 @@ STATE_DTYPE = np.dtype([("loss_scale", "<f4"), ("unskipped", "<i4"), ("adam_step
                         ("skipped_last", "<i4"), ("grad_norm", "<f4"), ("clip_coef", "<f4"), ("mult", "<f4"), ("skipped_total", "<i4"),
                         ("bias1", "<f4"), ("bias2", "<f4")])
 _STATE_WORDS = 16  # the device buffer: 64 bytes, the struct is the first 48
-lib = _lib.binder(SIGNATURES)  # libmdrhip.so with the signatures of include/mdr_optim.h bound
+lib = _lib.binder(SIGNATURES, ADAMW_SIGNATURES)  # libmdrhip.so with the signatures of include/mdr_optim.h and include/mdr_optim_adamw.h bound
 
 
 def _sizes(sizes):
@@ -109,11 +115,12 @@ def linear_schedule_with_warmup(step, warmup_steps, total_steps):
 
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, max_grad_norm=2.0, loss_scale="dynamic", scale_window=2000,
-                 fp16_copies=False, init_scale=2.0 ** 16, max_loss_scale=2.0 ** 24, zero_grads=True):
+                 fp16_copies=False, init_scale=2.0 ** 16, max_loss_scale=2.0 ** 24, zero_grads=True, decoupled_weight_decay=False):
         """loss_scale: "dynamic" (apex's LossScaler: init_scale, doubled after scale_window clean steps up to max_loss_scale, halved by a
         non-finite gradient) or a fixed number (a non-finite gradient still skips the step). fp16_copies: True keeps an fp16 copy of every
         parameter of two or more dimensions (the Linear weights and the embedding tables), or an iterable of the parameters to keep one of;
-        half(p) returns it."""
+        half(p) returns it. decoupled_weight_decay: False is torch.optim.Adam (L2 decay into the gradient, mdr_optim_step); True is
+        transformers.AdamW with correct_bias=True (mdr_optim_step_ex in mode 1, include/mdr_optim_adamw.h), the reader's optimizer."""
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"betas {betas} must lie in [0, 1)")
         if not eps > 0.0:
@@ -123,6 +130,7 @@ class FusedAdam(torch.optim.Optimizer):
         if int(scale_window) < 1:
             raise ValueError(f"scale_window = {scale_window} must be at least 1")
         self._dynamic = loss_scale == "dynamic"
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
         scale0 = float(init_scale if self._dynamic else loss_scale)
         if not (scale0 > 0.0 and np.isfinite(scale0)):
             raise ValueError(f"loss_scale = {loss_scale} must be \"dynamic\" or a positive number")
@@ -204,9 +212,12 @@ class FusedAdam(torch.optim.Optimizer):
                 if self._workspace is None:
                     self._workspace = torch.empty(workspace_bytes([r[5] for r in rows]), dtype=torch.uint8, device=dev)
                 self._key = rows
-            _lib.call(L.mdr_optim_step, ptr(self._table), len(rows), self._n_chunks, ptr(self._state), lr, self.betas[0], self.betas[1], self.eps,
-                      self.max_grad_norm, 1 if self._dynamic else 0, self.scale_window, self.max_loss_scale, 1 if self.zero_grads else 0,
-                      ptr(self._workspace), self._workspace.numel(), dev=dev)
+            head = (ptr(self._table), len(rows), self._n_chunks, ptr(self._state), lr, self.betas[0], self.betas[1], self.eps, self.max_grad_norm,
+                    1 if self._dynamic else 0, self.scale_window, self.max_loss_scale, 1 if self.zero_grads else 0)
+            if self.decoupled_weight_decay:
+                _lib.call(L.mdr_optim_step_ex, *head, DECAY_DECOUPLED, ptr(self._workspace), self._workspace.numel(), dev=dev)
+            else:
+                _lib.call(L.mdr_optim_step, *head, ptr(self._workspace), self._workspace.numel(), dev=dev)
         self.last_lr = lr
         return loss
 
