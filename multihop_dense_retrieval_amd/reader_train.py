@@ -14,9 +14,9 @@ reader_loss.qa_loss. The kernels are the inference reader's: in eval() mode, or 
 reader.QAModel(batch) bit for bit on the same weights. The reference's QAModel adds no dropout of its own (mdr/qa/qa_model.py): the sites
 are the encoder's. Only the default numerics mode of the trunk (residual_fp32 = 2) is built.
 
-Everything runs on one HIP device and is enqueued on the current stream; there is no CPU fallback. The dataset of the training branch
-(QADataset(train=True)), MhopSampler and the loop of scripts/train_qa.py --do_train are not built yet: `batch` is a qa_collate net_inputs
-dict that already holds starts, ends, label and, with --sp-pred, sent_labels.
+Everything runs on one HIP device and is enqueued on the current stream; there is no CPU fallback. `batch` is a qa_collate net_inputs dict
+that already holds starts, ends, label and, with --sp-pred, sent_labels: the training dataset and MhopSampler are qa_train_data.py, the
+batches come from qa_train_arena.py, and the loop is scripts/train_qa.py --do_train.
 """
 import os
 

@@ -1,14 +1,34 @@
-"""Drop-in for the reference's scripts/train_qa.py at inference (--do_predict / --do_test) on the HIP reader.
+"""Drop-in for the reference's scripts/train_qa.py on the HIP reader: inference (--do_predict / --do_test) and training (--do_train).
 
     python scripts/train_qa.py --do_predict --predict_file <retrieval jsonl with sp / answer> --init_checkpoint qa_electra.pt \
         --model_name <ELECTRA / BERT dir or cached name> --sp-pred --fp16 --max_ans_len 35 --save-prediction out.json
+    python scripts/train_qa.py --do_train --prefix electra_large --model_name <ELECTRA dir> --train_file train.jsonl --predict_file dev.jsonl \
+        --train_batch_size 128 --predict_batch_size 1024 --learning_rate 5e-5 --fp16 --seed 42 --eval-period 250 --max_seq_len 512 \
+        --max_q_len 64 --gradient_accumulation_steps 8 --neg-num 5 --sp-pred --sp-weight 0.05 --warmup-ratio 0.1 --num_train_epochs 7
 
 Flags are the reference's (mdr/qa/config.py), parsed verbatim. --do_predict runs predict() with the fixed 0.8 combination factor and
-writes its log lines and --save-prediction; --do_test runs eval_final(). --do_train exits: training is not supported. One rank; the
-batches are the reference's (sequential, --predict_batch_size chains) and are loaded in this process (num_workers is accepted and not
-used: the forward is on the device and data workers would fork a process that holds it). Numerics are apex O1's whether or not --fp16
-is given (the README's QA command passes it). The config and the tokenizer come from --model_name, a local directory or a model in the
-local cache; nothing is downloaded.
+writes its log lines and --save-prediction; --do_test runs eval_final(). One rank; the dev batches are the reference's (sequential,
+--predict_batch_size chains) and are loaded in this process (num_workers is accepted and not used: the forward is on the device and data
+workers would fork a process that holds it). Numerics are apex O1's whether or not --fp16 is given (the README's QA command passes it). The
+config and the tokenizer come from --model_name, a local directory or a model in the local cache; nothing is downloaded.
+
+--do_train is lines 138-211 of the reference's script on multihop_dense_retrieval_amd/reader_train.py. The training set
+(qa_train_data.QATrainDataset, the reference's QADataset(train=True)) is prepared once into an item arena on the device
+(qa_train_arena.QATrainArena); every step's batch is built there by mdr_reader_train_assemble from the indices qa_train_data.MhopSampler
+draws, and nothing is tokenised after start-up. Kept from the reference: the sampler's n_gpu = 8 default (len(qid2gold) % 8 questions
+sit out every epoch, and len(loader), t_total and the warm-up overstate the real step count, so the schedule never reaches zero), the
+negatives shuffled in place under the global `random` generator seeded once by --seed, the short last batch, the accumulation boundary
+(batch_step + 1) % gradient_accumulation_steps == 0, the loss meter fed by loss.item(), the evaluation every --eval-period steps and after
+every epoch (predict() over eleven combination factors), its log lines, and checkpoint_best.pt when em improves: the state dict as plain
+fp32 CPU tensors with the reference's keys. The encoder starts from the weights in the --model_name directory, the pooler and the heads
+from torch.nn.Linear's default initialiser under --seed (the draws are not claimed to be the reference's: it builds the encoder first, with
+another transformers version); --init_checkpoint overwrites both. Every forward draws its dropout seed from a torch.Generator seeded with
+--seed. One addition: checkpoint_last.pt after the last epoch, as the retriever's CLI writes; the reference saves only when em improves, so
+a run whose dev em stays 0 would leave no weights. TensorBoard scalars are written only when torch.utils.tensorboard imports.
+
+Whatever keeps --do_train from running exits with a message that begins "training is not supported: ": a --model_name that the trainable
+reader refuses (it is built for ELECTRA, from a local directory; the default bert-base-uncased is refused), no HIP device, a missing
+--train_file. The command line is checked for these before any file or device is opened.
 """
 import argparse
 import logging
@@ -81,10 +101,208 @@ def run_batches(model, loader, args, final):
     return chains, gold
 
 
+def check_train_inputs(args):
+    """What --do_train needs, read from the command line alone, before any file or device is opened: every refusal begins alike."""
+    no = "training is not supported: "
+    name = args.model_name
+    if "electra" not in name.lower() or not os.path.isdir(name):
+        sys.exit(f"{no}--model_name {name!r} is not a local ELECTRA directory (the trainable reader is built for ELECTRA, QAModel's own pooler; "
+                 "the config, the tokenizer and the weights come from that directory and nothing is downloaded)")
+    if args.local_rank != -1:
+        sys.exit(f"{no}multi-rank training is not built: run one rank (--local_rank -1)")
+    import torch
+    if args.no_cuda or not torch.cuda.is_available():
+        sys.exit(f"{no}no HIP device is visible (the reader trains on a HIP device only; there is no CPU fallback)")
+    for flag, path in (("--train_file", args.train_file), ("--predict_file", args.predict_file)):
+        if not os.path.isfile(path):
+            sys.exit(f"{no}{flag} {path!r}: no such file")
+    if args.init_checkpoint != "" and not os.path.isfile(args.init_checkpoint):
+        sys.exit(f"{no}--init_checkpoint {args.init_checkpoint!r}: no such file")
+    if args.gradient_accumulation_steps < 1 or args.train_batch_size < 1:
+        sys.exit(f"{no}--gradient_accumulation_steps and --train_batch_size must be at least 1")
+
+
+class AverageMeter:
+    """mdr/qa/utils.py:85-101 of the reference."""
+
+    def __init__(self):
+        self.val, self.avg, self.sum, self.count = 0, 0, 0, 0
+
+    def update(self, val, n=1):
+        self.val = val
+        self.sum += val * n
+        self.count += n
+        self.avg = self.sum / self.count
+
+
+def arena_batches(arena, pad_id, device):
+    """The product's feed: one epoch's indices go to the device once; every batch is mdr_reader_train_assemble on a slice of them, its
+    widths from the arena's host metadata (no synchronisation)."""
+    import torch
+    from multihop_dense_retrieval_amd import qa_train_arena
+
+    def feed(indices, batch_size):
+        on_dev = torch.tensor(indices, dtype=torch.int64, device=device)
+        for lo in range(0, len(indices), batch_size):
+            out_len, n_sent, n_span = arena.batch_shape(indices[lo:lo + batch_size])
+            out = arena.assemble(on_dev[lo:lo + batch_size], out_len, n_sent, n_span, pad_id)
+            yield {k: out[k] for k in qa_train_arena.NET_KEYS}
+    return feed
+
+
+def host_batches(dataset, pad_id, device):
+    """The reference's feed, in this process: __getitem__ per row, qa_train_collate, upload. Not reachable from the command line; the tests
+    and scripts/measure/qa_train_loop_bench.py compare the product's feed with it."""
+    import torch
+    from multihop_dense_retrieval_amd import qa_train_data
+
+    def feed(indices, batch_size):
+        for lo in range(0, len(indices), batch_size):
+            net = qa_train_data.qa_train_collate([dataset[i] for i in indices[lo:lo + batch_size]], pad_id=pad_id)["net_inputs"]
+            yield {k: v.to(device=device, dtype=torch.int64) for k, v in net.items()}  # (qa_collate's paragraph_mask is float 0 / 1)
+    return feed
+
+
+def train(args, model, sampler, feed, evaluate, logger, tb_logger=None, loss_scale="dynamic"):
+    """train_qa.py:138-211. sampler: qa_train_data.MhopSampler; feed(indices, batch_size) yields the net_inputs of one epoch's batches;
+    evaluate() returns predict()'s metrics on the current weights; loss_scale: reader_train.optimizer_for's (the script runs the dynamic one).
+    Returns {"loss": every batch's, "epoch_means", "global_step", "skipped_steps": the
+    optimizer steps the dynamic loss scale skipped while it came down from 2^16, as apex skips them (the schedule advances all the same)}."""
+    import torch
+    from multihop_dense_retrieval_amd import optim, qa_train_data, reader_train
+    from multihop_dense_retrieval_amd import train as mdr_train
+    optimizer = reader_train.optimizer_for(model, args, loss_scale=loss_scale)
+    global_step, batch_step, best_em = 0, 0, 0  # gradient update step; forward batch count
+    train_loss_meter = AverageMeter()
+    model.train()
+    t_total = qa_train_data.total_steps(sampler, args.train_batch_size, args.gradient_accumulation_steps, args.num_train_epochs)
+    warmup_steps = t_total * args.warmup_ratio
+    scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lambda s: optim.linear_schedule_with_warmup(s, warmup_steps, t_total))
+    seeds = torch.Generator().manual_seed(args.seed)  # one dropout seed per forward
+    state, losses, epoch_means = {"loss": None}, [], []
+
+    def save(name):
+        if not args.output_dir:  # (in-process callers that want no files)
+            return
+        torch.save({k: v.detach().float().cpu() for k, v in model.state_dict().items()}, os.path.join(args.output_dir, name))
+
+    def step_fn(batch, _batch_step):
+        seed = int(torch.randint(0, 2 ** 62, (1,), generator=seeds))
+        state["loss"] = reader_train.train_step(model, batch, args, optimizer, seed)
+        losses.append(state["loss"].item())
+        train_loss_meter.update(losses[-1])
+
+    def update_fn(_batch_step):
+        nonlocal global_step, best_em
+        optimizer.step()
+        scheduler.step()
+        global_step += 1
+        if tb_logger is not None:
+            tb_logger.add_scalar("batch_train_loss", losses[-1], global_step)
+            tb_logger.add_scalar("smoothed_train_loss", train_loss_meter.avg, global_step)
+        if args.eval_period != -1 and global_step % args.eval_period == 0:
+            em = evaluate()["em"]
+            model.train()
+            logger.info("Step %d Train loss %.2f em %.2f on epoch=%d" % (global_step, train_loss_meter.avg, em * 100, epoch))
+            if best_em < em:
+                logger.info("Saving model with best em %.2f -> em %.2f on step=%d" % (best_em * 100, em * 100, global_step))
+                save("checkpoint_best.pt")
+                best_em = em
+
+    logger.info("Start training....")
+    for epoch in range(int(args.num_train_epochs)):
+        first = len(losses)
+        batch_step = mdr_train.run_epoch(feed(list(iter(sampler)), args.train_batch_size), step_fn, update_fn, args.gradient_accumulation_steps,
+                                         batch_step)
+        epoch_means.append(sum(losses[first:]) / max(1, len(losses) - first))
+        em = evaluate()["em"]
+        model.train()
+        logger.info("Step %d Train loss %.2f em %.2f" % (global_step, train_loss_meter.avg, em * 100))
+        if tb_logger is not None:
+            tb_logger.add_scalar("dev_em", em * 100, global_step)
+        if best_em < em:
+            logger.info("Saving model with best em %.2f -> em %.2f on epoch=%d" % (best_em * 100, em * 100, epoch))
+            save("checkpoint_best.pt")
+            best_em = em
+    save("checkpoint_last.pt")  # not in the reference (module docstring)
+    logger.info("Training finished!")
+    return {"loss": losses, "epoch_means": epoch_means, "global_step": global_step, "skipped_steps": optimizer.read_state()["skipped_total"]}
+
+
+def initial_state(args, config, model):
+    """{name: tensor} the run starts from: the encoder of the --model_name directory (when it holds weights), the pooler and the heads from
+    torch.nn.Linear's default initialiser, --init_checkpoint over both. Exits when an encoder tensor has no source."""
+    import torch
+    import transformers
+    H = config.hidden_size
+    start = {}
+    for name, n_out in (("pooler.dense", H), ("qa_outputs", 2), ("rank", 1), ("sp", 1)):
+        if name + ".weight" in model.shapes:
+            lin = torch.nn.Linear(H, n_out)
+            start[name + ".weight"], start[name + ".bias"] = lin.weight.detach(), lin.bias.detach()
+    try:
+        hf = transformers.AutoModel.from_pretrained(args.model_name, local_files_only=True)
+        start.update({"encoder." + k: v.detach().float() for k, v in hf.state_dict().items() if "encoder." + k in model.shapes})
+    except (OSError, ValueError):
+        pass
+    if args.init_checkpoint != "":
+        ckpt = torch.load(args.init_checkpoint, map_location="cpu")
+        start.update({(k[7:] if k.startswith("module.") else k): v.float() for k, v in ckpt.items()})
+    start = {k: v for k, v in start.items() if k in model.shapes}
+    missing = [k for k in model.shapes if k not in start]
+    if missing:
+        sys.exit(f"training is not supported: no weights to start from: {args.model_name!r} holds none and --init_checkpoint gives none "
+                 f"({len(missing)} tensors missing, the first {missing[0]})")
+    return start
+
+
+def start_training(args, config, tokenizer, device, logger):
+    import random
+    import numpy as np
+    import torch
+    from torch.utils.data import DataLoader
+    from multihop_dense_retrieval_amd import qa_data, qa_train_arena, qa_train_data, reader_train
+    if args.shared_norm:
+        assert (args.train_batch_size // 1) == args.neg_num + 1  # chains of each question are on the same gpu (n_gpu = 1)
+    # train_qa.py:78-80. Seeded HERE, after the imports and the config / tokenizer loading: importing transformers draws from the global
+    # `random` generator, and nothing between this point and the sampler's first shuffle does.
+    random.seed(args.seed)
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    try:
+        model = reader_train.TrainableReader(config, args)
+    except NotImplementedError as e:
+        sys.exit(f"training is not supported: {e}")
+    collate = partial(qa_data.qa_collate, pad_id=tokenizer.pad_token_id)
+    eval_dataset = qa_data.QADataset(tokenizer, args.predict_file, args.max_seq_len, args.max_q_len)
+    eval_loader = DataLoader(eval_dataset, batch_size=args.predict_batch_size, collate_fn=collate, num_workers=0)
+    logger.info(f"Num of dev batches: {len(eval_loader)}")
+    if args.init_checkpoint != "":
+        logger.info(f"Loading model from {args.init_checkpoint}")
+    model.load_state_dict(initial_state(args, config, model))
+    model.to(device)
+    print(f"number of trainable parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+    try:
+        from torch.utils.tensorboard import SummaryWriter
+        tb_logger = SummaryWriter(os.path.join(args.output_dir.replace("logs", "tflogs")))
+    except ImportError:
+        tb_logger = None
+        logger.info("TensorBoard is not installed: its scalars are not written")
+    train_dataset = qa_train_data.QATrainDataset(tokenizer, args.train_file, args.max_seq_len, args.max_q_len)
+    sampler = qa_train_data.MhopSampler(train_dataset, num_neg=args.neg_num)
+    arena = qa_train_arena.QATrainArena.load_or_build(args.train_file, train_dataset, tokenizer, log=logger.info).to(device)
+
+    def evaluate():
+        chains, gold = run_batches(model.inference(), eval_loader, args, final=False)
+        return qa_data.predict_metrics(chains, gold, args.sp_pred, logger, fixed_thresh=None)[0]
+
+    return train(args, model, sampler, arena_batches(arena, tokenizer.pad_token_id, device), evaluate, logger, tb_logger)
+
+
 def main(argv=None):
     args = train_args(argv)
     if args.do_train:
-        sys.exit("training is not supported: this reader runs inference only (--do_predict / --do_test)")
+        check_train_inputs(args)
     import json
     import torch
     import transformers
@@ -94,6 +312,8 @@ def main(argv=None):
     model_name = (f"{args.prefix}-seed{args.seed}-bsz{args.train_batch_size}-fp16{args.fp16}-lr{args.learning_rate}-decay{args.weight_decay}"
                   f"-neg{args.neg_num}-sn{args.shared_norm}-adam{args.use_adam}-warm{args.warmup_ratio}-sp{args.sp_weight}")
     args.output_dir = os.path.join(args.output_dir, date_curr, model_name)
+    if args.do_train and os.path.exists(args.output_dir) and os.listdir(args.output_dir):
+        print(f"output directory {args.output_dir} already exists and is not empty.")
     os.makedirs(args.output_dir, exist_ok=True)
     logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S", level=logging.INFO,
                         handlers=[logging.FileHandler(os.path.join(args.output_dir, "log.txt")), logging.StreamHandler()])
@@ -106,6 +326,8 @@ def main(argv=None):
     logger.info("device %s n_gpu %d distributed training %r", device, 1, False)
     config = transformers.AutoConfig.from_pretrained(args.model_name, local_files_only=True)
     tokenizer = transformers.BertTokenizer.from_pretrained(args.model_name, local_files_only=True)
+    if args.do_train:
+        return start_training(args, config, tokenizer, device, logger)
     model = reader.QAModel(config, args)
     collate = partial(qa_data.qa_collate, pad_id=tokenizer.pad_token_id)
     dataset = qa_data.QADataset(tokenizer, args.predict_file, args.max_seq_len, args.max_q_len)
