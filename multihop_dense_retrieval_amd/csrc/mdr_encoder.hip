@@ -20,6 +20,8 @@
 //   attention<NT>                       per (sequence, head): K and V^T of the sequence staged in LDS once,
 //                                       S = QK^T on MFMA, fp32 softmax in registers, O = PV on MFMA
 //   layernorm                           fp32 [T,H] -> fp16 (hidden state) or fp32 (final embedding)
+//   layernorm_dropout / embed_ln_dropout  the two above with the hidden-state dropout mask folded in (mdr_encoder_dropout.inl): the
+//                                       training-mode forward of include/mdr_encoder_dropout.h
 //
 // Host side, in this order: the GEMM / attention launchers (here); the transformer trunk shared with the answer reader -- weights and their
 // upload, workspace, packing prologue, layer body (mdr_encoder_trunk.inl); the encoder's own part -- its embedding launch, the CLS-only last
@@ -39,13 +41,17 @@
 #include <vector>
 
 #include "mdr_common.h"
+#include "mdr_dropout.h"
 #include "mdr_gemm_choice.h"
+#include "../../include/mdr_dropout.h"
+#include "../../include/mdr_encoder_dropout.h"
 #include "../../include/mdr_reader.h"
 
 namespace mdr {
 namespace {
 
 #include "mdr_encoder_pack_ln.inl"
+#include "mdr_encoder_dropout.inl"
 #include "mdr_encoder_gemm.inl"
 #include "mdr_encoder_gemm_quad.inl"
 #include "mdr_encoder_attention.inl"
@@ -200,9 +206,13 @@ namespace {
 // the encoder's embedding launch (RoBERTa position ids from tok_pid, one type row): one wave per packed token, cap = batch * seq_len waves launched
 void launch_embed_ln(const long long* ids, const int* tok_src, const int* tok_pid, const int* total, int cap, const float* word, const float* pos,
                      const float* type0, const float* g, const float* b, int H, int vocab, int max_pos, float eps, _Float16* out16, float* out32,
-                     hipStream_t st) {
-    hipLaunchKernelGGL(embed_ln_kernel, dim3((cap + 3) / 4), dim3(256), 0, st, ids, tok_src, tok_pid, total, word, pos, type0, g, b, H, vocab, max_pos, eps,
-                       out16, out32);
+                     hipStream_t st, const DropoutParams* drop = nullptr) {
+    if (drop)  // y * m, then the fp16 copy of the masked value (mdr_encoder_dropout.inl)
+        hipLaunchKernelGGL(embed_ln_dropout_kernel, dim3((cap + 3) / 4), dim3(256), 0, st, ids, tok_src, tok_pid, total, word, pos, type0, g, b, H, vocab,
+                           max_pos, eps, *drop, out16, out32);
+    else
+        hipLaunchKernelGGL(embed_ln_kernel, dim3((cap + 3) / 4), dim3(256), 0, st, ids, tok_src, tok_pid, total, word, pos, type0, g, b, H, vocab, max_pos,
+                           eps, out16, out32);
 }
 
 // What the GEMM test hooks ask of their integers. mdr_test_gemm_f16 has no epilogue 2 and, in MDR_GEMM_EXTRA_CFGS builds, the kernels 8-13.
@@ -245,6 +255,9 @@ int test_gemm(const void* A_dev, const void* W_dev, const float* bias_dev, const
 }
 
 }  // namespace
+
+static int encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* mask_dev, int batch, int seq_len, const TrunkDropout* drop,
+                           float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 extern "C" {
 
@@ -391,6 +404,15 @@ size_t mdr_encoder_workspace_bytes(const mdr_encoder* h, int batch, int seq_len)
 
 int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* mask_dev, int batch, int seq_len, float* out_dev, void* workspace_dev,
                         size_t workspace_bytes, void* stream) {
+    return encoder_forward(h, ids_dev, mask_dev, batch, seq_len, nullptr, out_dev, workspace_dev, workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+// mdr_encoder_forward (drop == nullptr) and mdr_encoder_forward_dropout (mdr_encoder_dropout_api.inl): one launch sequence, the dropout
+// places live where drop's thresholds are not 0
+static int encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* mask_dev, int batch, int seq_len, const TrunkDropout* drop,
+                           float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
     MDR_REQUIRE(h != nullptr, "encoder handle is NULL");
     MDR_REQUIRE(batch >= 0 && seq_len > 0, "bad shape batch=%d seq_len=%d", batch, seq_len);
     if (batch == 0) return MDR_OK;
@@ -429,12 +451,15 @@ int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* m
         }
     }
 #endif
-    launch_embed_ln(ids, w.tok_src, w.tok_pid, w.total, Tcap, t.word, t.pos, t.type, t.emb_g, t.emb_b, H, c.vocab, c.max_pos, c.ln_eps, w.h16, w.h32, st);
+    const bool drop_hid = drop && drop->T_hidden, drop_att = drop && drop->T_attention;
+    const DropoutParams emb_drop = drop_hid ? drop->params(0, kPlaceEmb) : DropoutParams{};
+    launch_embed_ln(ids, w.tok_src, w.tok_pid, w.total, Tcap, t.word, t.pos, t.type, t.emb_g, t.emb_b, H, c.vocab, c.max_pos, c.ln_eps, w.h16, w.h32, st,
+                    drop_hid ? &emb_drop : nullptr);
     MDR_HIP_TRY(hipGetLastError());
     const Rows tokens{w.h16, w.h32, w.pre, Tcap, w.total, Test}, cls{w.cls16, w.cls32, w.clspre, B, nullptr, B};
     int rc;
     for (int i = 0; i + 1 < c.layers; ++i) {
-        rc = trunk_layer(t, t.layers[i], w, tokens, B, L, ncu, st);
+        rc = trunk_layer(t, t.layers[i], w, tokens, B, L, ncu, st, drop, i);
         if (rc) return rc;
     }
     // ---- last layer: everything after the K/V projection only for the CLS rows ([B, H] instead of [T, H]) ----
@@ -442,9 +467,16 @@ int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* m
     rc = launch_qkv(t, last, w, tokens, ncu, st);
     if (rc) return rc;
     launch_gather_cls(w.h16, w.h32, w.cu, B, H, w.cls16, w.cls32, st);
-    hipLaunchKernelGGL(attention_cls_kernel, dim3(c.heads, B), dim3(64), 0, st, (const _Float16*)w.qkv, (const int*)w.cu, H, w.ctx);
-    MDR_HIP_TRY(hipGetLastError());
-    rc = layer_tail(t, last, w.ctx, w.ffn, cls, ncu, st);
+    const int li = c.layers - 1;
+    if (drop_att) {  // the first query of each sequence under the attention mask (mode 3 of include/mdr_dropout.h)
+        rc = mdr_attention_dropout_forward(w.qkv, w.cu, B, L, H, c.heads, 3, (int)drop->T_attention, drop->seed, drop->site(li, kPlaceAttn), w.ctx, t.device,
+                                           stream);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL(attention_cls_kernel, dim3(c.heads, B), dim3(64), 0, st, (const _Float16*)w.qkv, (const int*)w.cu, H, w.ctx);
+        MDR_HIP_TRY(hipGetLastError());
+    }
+    rc = layer_tail(t, last, w.ctx, w.ffn, cls, ncu, st, drop, li);
     if (rc) return rc;
     rc = launch_gemm<EPI_BIAS_F32>(w.cls16, H, h->wproj, h->bproj, B, nullptr, H, H, w.clspre, H, nullptr, 0, B, ncu, st);
     if (rc) return rc;
@@ -454,12 +486,12 @@ int mdr_encoder_forward(mdr_encoder* h, const int64_t* ids_dev, const int64_t* m
     return MDR_OK;
 }
 
-}  // extern "C"
-
 // the answer reader (include/mdr_reader.h) shares this translation unit's file-local kernels and launchers
 #include "mdr_reader.inl"
 #include "mdr_reader_assemble.inl"
 // the mdr_test_* hooks of the packing / embedding / LayerNorm / row kernels (behind the reader: its embedding kernel is one of them)
 #include "mdr_encoder_test_rows.inl"
+// the training-mode forward and the test hooks of its two row kernels (include/mdr_encoder_dropout.h)
+#include "mdr_encoder_dropout_api.inl"
 // the backward of the trunk's Linears (include/mdr_linear_grad.h): its dX goes through launch_gemm
 #include "mdr_linear_grad.inl"

@@ -40,6 +40,24 @@ void launch_layernorm(const IN_T* in, const _Float16* res16, const float* res32,
     hipLaunchKernelGGL(layernorm_kernel<IN_T>, dim3((rows_cap + 3) / 4), dim3(256), 0, st, in, res16, res32, rows_cap, rows_dev, H, g, b, eps, out16, out32);
 }
 
+// layernorm_kernel<_Float16> over fp32(fp16(fp32(in) * m)): the hidden-state dropout of a training-mode forward (mdr_encoder_dropout.inl)
+void launch_layernorm_dropout(const _Float16* in, const float* res32, int rows_cap, const int* rows_dev, int H, const float* g, const float* b, float eps,
+                              const DropoutParams& dp, _Float16* out16, float* out32, hipStream_t st) {
+    hipLaunchKernelGGL(layernorm_dropout_kernel, dim3((rows_cap + 3) / 4), dim3(256), 0, st, in, res32, rows_cap, rows_dev, H, g, b, eps, dp, out16, out32);
+}
+
+// The dropout of one training-mode forward (include/mdr_encoder_dropout.h): the thresholds of the two kinds (0: that kind's places are
+// plain), the step's seed and which of a step's encodes this is. The site of a place is dropout.site_of's:
+//   site = 1 + (encode * 64 + layer) * 4 + place,   place: 0 emb (layer 0 only), 1 attn, 2 ao, 3 ff2
+enum { kPlaceEmb = 0, kPlaceAttn = 1, kPlaceAo = 2, kPlaceFf2 = 3, kDropoutMaxLayers = 64, kDropoutEncodes = 6 };
+struct TrunkDropout {
+    unsigned T_hidden, T_attention;
+    uint64_t seed;
+    int encode;
+    uint32_t site(int layer, int place) const { return 1u + ((uint32_t)encode * kDropoutMaxLayers + (uint32_t)layer) * 4u + (uint32_t)place; }
+    DropoutParams params(int layer, int place) const { return dropout_params(place == kPlaceAttn ? T_attention : T_hidden, seed, site(layer, place)); }
+};
+
 void launch_gather_cls(const _Float16* h16, const float* h32, const int* cu, int B, int H, _Float16* out16, float* out32, hipStream_t st) {
     hipLaunchKernelGGL(gather_cls_kernel, dim3((B * H + 255) / 256), dim3(256), 0, st, h16, h32, cu, B, H, out16, out32);
 }
@@ -254,29 +272,37 @@ int gemm_to_pre(const mdr_encoder_config& c, const _Float16* x, int K, const _Fl
     return launch_gemm<EPI_BIAS_RES_F32>(x, K, W, bias, r.cap, r.n_dev, H, K, r.pre, H, r.h16, H, r.est, ncu, st, res_in);
 }
 
-// r.h16 (and r.h32) = LayerNorm(r.pre + residual): the one place that knows where the residual comes from
-void post_ln(const mdr_encoder_config& c, const Rows& r, bool res_in_gemm, const float* g, const float* b, hipStream_t st) {
+// r.h16 (and r.h32) = LayerNorm(r.pre + residual): the one place that knows where the residual comes from. drop (residual_fp32 = 2 only: the
+// training-mode forward's callers refuse the other modes): r.pre goes through the hidden-state mask first.
+void post_ln(const mdr_encoder_config& c, const Rows& r, bool res_in_gemm, const float* g, const float* b, hipStream_t st,
+             const DropoutParams* drop = nullptr) {
     const bool r32 = c.residual_fp32 != 0;
-    if (c.residual_fp32 == 2)
+    if (drop)
+        launch_layernorm_dropout((const _Float16*)r.pre, (const float*)r.h32, r.cap, r.n_dev, c.hidden, g, b, c.ln_eps, *drop, r.h16, r.h32, st);
+    else if (c.residual_fp32 == 2)
         launch_layernorm((const _Float16*)r.pre, (const _Float16*)nullptr, (const float*)r.h32, r.cap, r.n_dev, c.hidden, g, b, c.ln_eps, r.h16, r.h32, st);
     else
         launch_layernorm((const float*)r.pre, (const _Float16*)(r32 || res_in_gemm ? nullptr : r.h16), (const float*)(r32 ? r.h32 : nullptr), r.cap, r.n_dev,
                          c.hidden, g, b, c.ln_eps, r.h16, (float*)(r32 ? r.h32 : nullptr), st);
 }
 
-// out-projection of ctx -> LayerNorm -> FFN1 (GELU) into ffn -> FFN2 -> LayerNorm, over r
-int layer_tail(const Trunk& t, const Layer& Ly, const _Float16* ctx, _Float16* ffn, const Rows& r, int ncu, hipStream_t st) {
+// out-projection of ctx -> LayerNorm -> FFN1 (GELU) into ffn -> FFN2 -> LayerNorm, over r. drop (with a hidden threshold): the two
+// Linear outputs in front of the LayerNorms are masked at layer `li`'s ao and ff2 sites.
+int layer_tail(const Trunk& t, const Layer& Ly, const _Float16* ctx, _Float16* ffn, const Rows& r, int ncu, hipStream_t st,
+               const TrunkDropout* drop = nullptr, int li = 0) {
     const mdr_encoder_config& c = t.cfg;
     const int H = c.hidden, F = c.ffn;
+    const bool masked = drop && drop->T_hidden;
+    const DropoutParams ao = masked ? drop->params(li, kPlaceAo) : DropoutParams{}, ff2 = masked ? drop->params(li, kPlaceFf2) : DropoutParams{};
     bool res_in;
     int rc = gemm_to_pre(c, ctx, H, Ly.wo, Ly.bo, r, ncu, st, &res_in);
     if (rc) return rc;
-    post_ln(c, r, res_in, Ly.ln1_g, Ly.ln1_b, st);
+    post_ln(c, r, res_in, Ly.ln1_g, Ly.ln1_b, st, masked ? &ao : nullptr);
     rc = launch_gemm<EPI_BIAS_GELU_F16>(r.h16, H, Ly.w1, Ly.b1, r.cap, r.n_dev, F, H, ffn, F, nullptr, 0, r.est, ncu, st);
     if (rc) return rc;
     rc = gemm_to_pre(c, ffn, F, Ly.w2, Ly.b2, r, ncu, st, &res_in);
     if (rc) return rc;
-    post_ln(c, r, res_in, Ly.ln2_g, Ly.ln2_b, st);
+    post_ln(c, r, res_in, Ly.ln2_g, Ly.ln2_b, st, masked ? &ff2 : nullptr);
     MDR_HIP_TRY(hipGetLastError());
     return MDR_OK;
 }
@@ -287,12 +313,17 @@ int launch_qkv(const Trunk& t, const Layer& Ly, const Workspace& w, const Rows& 
 }
 
 // one whole layer over every packed token (r: the token rows of w)
-int trunk_layer(const Trunk& t, const Layer& Ly, const Workspace& w, const Rows& r, int B, int L, int ncu, hipStream_t st) {
+int trunk_layer(const Trunk& t, const Layer& Ly, const Workspace& w, const Rows& r, int B, int L, int ncu, hipStream_t st,
+                const TrunkDropout* drop = nullptr, int li = 0) {
     int rc = launch_qkv(t, Ly, w, r, ncu, st);
     if (rc) return rc;
-    rc = launch_attention_for(MDR_ATTN_FORCE, w.qkv, w.cu, w.order, B, L, t.cfg.hidden, t.cfg.heads, w.ctx, st);
+    if (drop && drop->T_attention)  // the training attention forward (include/mdr_dropout.h, mode 0): every query under the mask of layer li's attn site
+        rc = mdr_attention_dropout_forward(w.qkv, w.cu, B, L, t.cfg.hidden, t.cfg.heads, 0, (int)drop->T_attention, drop->seed, drop->site(li, kPlaceAttn), w.ctx,
+                                           t.device, (void*)st);
+    else
+        rc = launch_attention_for(MDR_ATTN_FORCE, w.qkv, w.cu, w.order, B, L, t.cfg.hidden, t.cfg.heads, w.ctx, st);
     if (rc) return rc;
-    return layer_tail(t, Ly, w.ctx, w.ffn, r, ncu, st);
+    return layer_tail(t, Ly, w.ctx, w.ffn, r, ncu, st, drop, li);
 }
 
 }  // namespace

@@ -20,7 +20,8 @@ fp32 CPU state dicts with the reference's keys) under output_dir/<date>/<prefix>
 from the weights in the --model_name directory, project.* from torch's default initialisers under --seed; --init_checkpoint overwrites both.
 Every forward draws its dropout seed from a torch.Generator seeded with --seed. The arithmetic is fp16 with fp32 masters whether or not
 --fp16 is given, so the dynamic loss scale is always on; --fp16 selects the fp16 score mode of the loss, as for --do_predict.
-Not built: --momentum (the reference trains it from a script of its own) and multi-rank training.
+--momentum is refused here: the reference trains it from a script of its own, and so does this repository (scripts/train_momentum.py, which
+calls this file's train() with its own step, evaluation model and checkpoint names). Not built: multi-rank training.
 
 Deviations from the reference, all outside the numbers it reports: for --do_predict no dated `--output_dir` directory, `log.txt` or
 TensorBoard writer is created (the reference makes them even there; an evaluation needs none); TensorBoard scalars are written only when
@@ -77,7 +78,7 @@ class AverageMeter:
 def check_train_inputs(args):
     """What --do_train needs from the command line, looked at before anything touches the device."""
     if args.momentum:
-        sys.exit("training with --momentum is not built: the reference trains it from a script of its own")
+        sys.exit("training with --momentum is not built in this script: the reference trains it from a script of its own, scripts/train_momentum.py")
     if not os.path.isdir(args.model_name):
         sys.exit(f"training is not supported with --model_name {args.model_name!r}: it must be a local directory with the RoBERTa config, "
                  "tokenizer and weights (nothing is downloaded)")
@@ -102,14 +103,21 @@ def encoder_weights(model_name, wanted):
     return {"encoder." + k: v.detach().float() for k, v in hf.state_dict().items() if "encoder." + k in wanted}
 
 
-def train(args, model, tokenizer, collate_fc, eval_dataloader, device, logger, tb_logger):
-    """train_mhop.py:124-227."""
+def train(args, model, tokenizer, collate_fc, eval_dataloader, device, logger, tb_logger, steps=None, eval_model=None, saved=None,
+          best=("checkpoint_best.pt",), last="checkpoint_last.pt"):
+    """train_mhop.py:124-227, and train_momentum.py:125-208 of the reference, which is the same loop. What differs between the two comes in
+    from the caller: steps, the module with optimizer_for and train_step (default: multihop_dense_retrieval_amd.train); eval_model(), what
+    predict() is given (default: model.inference()); saved(), the state dict a checkpoint holds (default: model's); best and last, the
+    checkpoint files' names (every name of `best` gets the same tensors)."""
     import torch
     from torch.utils.data import DataLoader
     from multihop_dense_retrieval_amd import mhop_data, optim
     from multihop_dense_retrieval_amd import train as mdr_train
     from multihop_dense_retrieval_amd.retriever import move_to_cuda
-    optimizer = mdr_train.optimizer_for(model, args)
+    steps = steps or mdr_train
+    eval_model = eval_model or model.inference
+    saved = saved or model.state_dict
+    optimizer = steps.optimizer_for(model, args)
     global_step, batch_step, best_mrr = 0, 0, 0  # gradient update step; forward batch count
     train_loss_meter = AverageMeter()
     model.train()
@@ -121,17 +129,18 @@ def train(args, model, tokenizer, collate_fc, eval_dataloader, device, logger, t
     seeds = torch.Generator().manual_seed(args.seed)  # one dropout seed per forward
     state = {"loss": None}
 
-    def save(name):
-        torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, os.path.join(args.output_dir, name))
+    def save(*names):
+        for name in names:
+            torch.save({k: v.detach().cpu() for k, v in saved().items()}, os.path.join(args.output_dir, name))
 
     def evaluate():
-        mrrs = predict(args, model.inference(), eval_dataloader, device, logger)
+        mrrs = predict(args, eval_model(), eval_dataloader, device, logger)
         model.train()
         return mrrs
 
     def step_fn(batch, _batch_step):
         seed = int(torch.randint(0, 2 ** 62, (1,), generator=seeds))
-        state["loss"] = mdr_train.train_step(model, move_to_cuda(batch), args, optimizer, seed)
+        state["loss"] = steps.train_step(model, move_to_cuda(batch), args, optimizer, seed)
         train_loss_meter.update(state["loss"].item())
 
     def update_fn(_batch_step):
@@ -147,7 +156,7 @@ def train(args, model, tokenizer, collate_fc, eval_dataloader, device, logger, t
             logger.info("Step %d Train loss %.2f MRR %.2f on epoch=%d" % (global_step, train_loss_meter.avg, mrr * 100, epoch))
             if best_mrr < mrr:
                 logger.info("Saving model with best MRR %.2f -> MRR %.2f on epoch=%d" % (best_mrr * 100, mrr * 100, epoch))
-                save("checkpoint_best.pt")
+                save(*best)
                 best_mrr = mrr
 
     logger.info("Start training....")
@@ -159,10 +168,10 @@ def train(args, model, tokenizer, collate_fc, eval_dataloader, device, logger, t
         if tb_logger is not None:
             for k, v in mrrs.items():
                 tb_logger.add_scalar(k, v * 100, epoch)
-        save("checkpoint_last.pt")
+        save(last)
         if best_mrr < mrr:
             logger.info("Saving model with best MRR %.2f -> MRR %.2f on epoch=%d" % (best_mrr * 100, mrr * 100, epoch))
-            save("checkpoint_best.pt")
+            save(*best)
             best_mrr = mrr
     logger.info("Training finished!")
 
