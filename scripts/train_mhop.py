@@ -26,9 +26,13 @@ calls this file's train() with its own step, evaluation model and checkpoint nam
 Deviations from the reference, all outside the numbers it reports: for --do_predict no dated `--output_dir` directory, `log.txt` or
 TensorBoard writer is created (the reference makes them even there; an evaluation needs none); TensorBoard scalars are written only when
 torch.utils.tensorboard imports; the checkpoint is loaded with load_saved(exact=False), so buffers a newer transformers saved beside the
-weights are dropped instead of refused; --model_name is a local directory (nothing is downloaded); the batches are loaded in this process
+weights are dropped instead of refused; --model_name is a local directory (nothing is downloaded); the batches are built in this process
 whatever --num_workers says, which is also the only setting under which the reference's order of the comparison questions' positives and
-of the training negatives (global random.shuffle calls, multihop_dense_retrieval_amd/mhop_data.py) is reproducible.
+of the training negatives (global random.shuffle calls, multihop_dense_retrieval_amd/mhop_data.py) is reproducible. Under --do_train the
+train file and the dev file are each tokenised ONCE into a token arena on the device, cached beside the data file as
+`<file>.mhop_arena.npz` (its status goes to stdout, not to the log), and every batch is assembled there by one kernel from the reference's
+own shuffle draws (multihop_dense_retrieval_amd/mhop_arena.py): the same batches, checkpoint bytes and generator states
+as the reference's per-step tokenising, which train(..., feed="host") still runs. Only RoBERTa-family tokenizers are served there.
 """
 import logging
 import os
@@ -103,15 +107,32 @@ def encoder_weights(model_name, wanted):
     return {"encoder." + k: v.detach().float() for k, v in hf.state_dict().items() if "encoder." + k in wanted}
 
 
+def dev_batches(args, tokenizer, collate_fc, device, feed="host"):
+    """The dev set's batches, an iterable with len(): today's DataLoader over mhop_data.MhopDataset (feed="host"), or the feed of a token arena
+    built or loaded once for --predict_file (feed="arena": multihop_dense_retrieval_amd/mhop_arena.py), whose batches are already on `device`.
+    Both read the samples in file order and make the same draws on `random` and on torch's generator."""
+    from torch.utils.data import DataLoader
+    from multihop_dense_retrieval_amd import mhop_arena, mhop_data
+    eval_dataset = mhop_data.MhopDataset(tokenizer, args.predict_file, args.max_q_len, args.max_q_sp_len, args.max_c_len)
+    if feed == "arena":
+        return mhop_arena.MhopArena.load_or_build(args.predict_file, eval_dataset, tokenizer).to(device).feed(args.predict_batch_size, shuffle=False)
+    if feed != "host":
+        raise ValueError(f"feed = {feed!r}: \"arena\" or \"host\"")
+    return DataLoader(eval_dataset, batch_size=args.predict_batch_size, collate_fn=collate_fc, num_workers=0)
+
+
 def train(args, model, tokenizer, collate_fc, eval_dataloader, device, logger, tb_logger, steps=None, eval_model=None, saved=None,
-          best=("checkpoint_best.pt",), last="checkpoint_last.pt"):
+          best=("checkpoint_best.pt",), last="checkpoint_last.pt", feed="arena"):
     """train_mhop.py:124-227, and train_momentum.py:125-208 of the reference, which is the same loop. What differs between the two comes in
     from the caller: steps, the module with optimizer_for and train_step (default: multihop_dense_retrieval_amd.train); eval_model(), what
     predict() is given (default: model.inference()); saved(), the state dict a checkpoint holds (default: model's); best and last, the
-    checkpoint files' names (every name of `best` gets the same tensors)."""
+    checkpoint files' names (every name of `best` gets the same tensors). feed: where a step's batch comes from. "arena": the train file is
+    tokenised once into a token arena on `device` and every batch is assembled there by one kernel from that step's choices
+    (multihop_dense_retrieval_amd/mhop_arena.py); "host": the reference's way, a DataLoader that tokenises six sequences per sample on every
+    read. Under one seed the two leave the same checkpoint bytes and the same generator states."""
     import torch
     from torch.utils.data import DataLoader
-    from multihop_dense_retrieval_amd import mhop_data, optim
+    from multihop_dense_retrieval_amd import mhop_arena, mhop_data, optim
     from multihop_dense_retrieval_amd import train as mdr_train
     from multihop_dense_retrieval_amd.retriever import move_to_cuda
     steps = steps or mdr_train
@@ -122,7 +143,12 @@ def train(args, model, tokenizer, collate_fc, eval_dataloader, device, logger, t
     train_loss_meter = AverageMeter()
     model.train()
     train_dataset = mhop_data.MhopTrainDataset(tokenizer, args.train_file, args.max_q_len, args.max_q_sp_len, args.max_c_len)
-    train_dataloader = DataLoader(train_dataset, batch_size=args.train_batch_size, collate_fn=collate_fc, num_workers=0, shuffle=True)
+    if feed == "arena":  # the batches are already on the device: step_fn's move_to_cuda is a no-op on them
+        train_dataloader = mhop_arena.MhopArena.load_or_build(args.train_file, train_dataset, tokenizer).to(device).feed(args.train_batch_size, shuffle=True)
+    elif feed == "host":
+        train_dataloader = DataLoader(train_dataset, batch_size=args.train_batch_size, collate_fn=collate_fc, num_workers=0, shuffle=True)
+    else:
+        raise ValueError(f"feed = {feed!r}: \"arena\" or \"host\"")
     t_total = len(train_dataloader) // args.gradient_accumulation_steps * args.num_train_epochs
     warmup_steps = t_total * args.warmup_ratio
     scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lambda s: optim.linear_schedule_with_warmup(s, warmup_steps, t_total))
@@ -191,7 +217,6 @@ def main(argv=None):
         handlers.insert(0, logging.FileHandler(os.path.join(args.output_dir, "log.txt")))
     import numpy as np
     import torch
-    from torch.utils.data import DataLoader
     from multihop_dense_retrieval_amd import data, mhop_data, retriever
     logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S", level=logging.INFO, handlers=handlers)
     logger = logging.getLogger(__name__)
@@ -219,8 +244,8 @@ def main(argv=None):
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
-    eval_dataset = mhop_data.MhopDataset(tokenizer, args.predict_file, args.max_q_len, args.max_q_sp_len, args.max_c_len)
-    eval_dataloader = DataLoader(eval_dataset, batch_size=args.predict_batch_size, collate_fn=collate_fc, num_workers=0)
+    # a training run evaluates the dev set after every epoch and every --eval-period steps: tokenised once. --do_predict alone is one pass.
+    eval_dataloader = dev_batches(args, tokenizer, collate_fc, device, feed="arena" if args.do_train else "host")
     logger.info(f"Num of dev batches: {len(eval_dataloader)}")
     if args.do_train:
         from multihop_dense_retrieval_amd import train as mdr_train

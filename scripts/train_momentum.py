@@ -22,7 +22,7 @@ output_dir/<date>/{prefix}-seed..-bsz..-fp16..-lr..-decay..-warm..-valbsz..-m{m}
 
 Not built: several ranks (--local_rank other than -1, and the reference's DataParallel split of a batch). Inputs are checked before the
 device is touched; every reason the script cannot run exits with a message. The other deviations are scripts/train_mhop.py's (no
-TensorBoard without the package, local --model_name, batches loaded in this process).
+TensorBoard without the package, local --model_name, batches built in this process: under --do_train from token arenas on the device).
 """
 import logging
 import os
@@ -106,7 +106,6 @@ def main(argv=None):
         handlers.insert(0, logging.FileHandler(os.path.join(args.output_dir, "log.txt")))
     import numpy as np
     import torch
-    from torch.utils.data import DataLoader
     import train_mhop
     from multihop_dense_retrieval_amd import data, mhop_data, momentum
     logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S", level=logging.INFO, handlers=handlers)
@@ -132,8 +131,7 @@ def main(argv=None):
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     model = build_model(args, bert_config, device)
-    eval_dataset = mhop_data.MhopDataset(tokenizer, args.predict_file, args.max_q_len, args.max_q_sp_len, args.max_c_len)
-    eval_dataloader = DataLoader(eval_dataset, batch_size=args.predict_batch_size, collate_fn=collate_fc, num_workers=0)
+    eval_dataloader = train_mhop.dev_batches(args, tokenizer, collate_fc, device, feed="arena" if args.do_train else "host")
     logger.info(f"Num of dev batches: {len(eval_dataloader)}")
     print(f"number of trainable parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
     if args.do_train:
