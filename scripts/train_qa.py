@@ -26,6 +26,14 @@ another transformers version); --init_checkpoint overwrites both. Every forward 
 --seed. One addition: checkpoint_last.pt after the last epoch, as the retriever's CLI writes; the reference saves only when em improves, so
 a run whose dev em stays 0 would leave no weights. TensorBoard scalars are written only when torch.utils.tensorboard imports.
 
+--piece-arena (not a flag of the reference, off by default) feeds the same loop from qa_train_pieces.QATrainPieces: one stored row per
+question and per distinct passage, five integers per item, every batch spliced on the device by mdr_reader_train_compose, byte for byte the
+batches of the default arena. It is the path for a train file with many candidate chains per question (the README's
+train_retrieval_b100_k100_sp.json): the default arena runs __getitem__ on every chain of every question, in one process, before the first
+step. The pieces are built before the model goes to the device (this process holds no stream, no memory there yet), with
+min(16, --num_workers) forked workers, and cached beside the train file. It
+takes chains of exactly two passages; another length exits and names the default arena.
+
 Whatever keeps --do_train from running exits with a message that begins "training is not supported: ": a --model_name that the trainable
 reader refuses (it is built for ELECTRA, from a local directory; the default bert-base-uncased is refused), no HIP device, a missing
 --train_file. The command line is checked for these before any file or device is opened.
@@ -83,6 +91,7 @@ def train_args(argv=None):
     p.add_argument("--use-adam", action="store_true")
     p.add_argument("--warmup-ratio", default=0, type=float)
     p.add_argument("--sp-weight", default=0, type=float)
+    p.add_argument("--piece-arena", action="store_true")  # not in the reference: the training feed's piece arena (module docstring)
     return p.parse_args(argv)
 
 
@@ -261,7 +270,7 @@ def start_training(args, config, tokenizer, device, logger):
     import numpy as np
     import torch
     from torch.utils.data import DataLoader
-    from multihop_dense_retrieval_amd import qa_data, qa_train_arena, qa_train_data, reader_train
+    from multihop_dense_retrieval_amd import qa_data, qa_train_arena, qa_train_data, qa_train_pieces, reader_train
     if args.shared_norm:
         assert (args.train_batch_size // 1) == args.neg_num + 1  # chains of each question are on the same gpu (n_gpu = 1)
     # train_qa.py:78-80. Seeded HERE, after the imports and the config / tokenizer loading: importing transformers draws from the global
@@ -280,6 +289,13 @@ def start_training(args, config, tokenizer, device, logger):
     if args.init_checkpoint != "":
         logger.info(f"Loading model from {args.init_checkpoint}")
     model.load_state_dict(initial_state(args, config, model))
+    pieces = None
+    if args.piece_arena:  # built HERE, before model.to(device) makes this process hold the device: its workers are forked processes
+        train_dataset = qa_train_data.QATrainDataset(tokenizer, args.train_file, args.max_seq_len, args.max_q_len)
+        try:
+            pieces = qa_train_pieces.QATrainPieces.load_or_build(args.train_file, train_dataset, tokenizer, log=logger.info, workers=min(16, args.num_workers))
+        except ValueError as e:
+            sys.exit(f"training is not supported: {e} (run without --piece-arena: the default item arena takes chains of any length)")
     model.to(device)
     print(f"number of trainable parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
     try:
@@ -288,9 +304,10 @@ def start_training(args, config, tokenizer, device, logger):
     except ImportError:
         tb_logger = None
         logger.info("TensorBoard is not installed: its scalars are not written")
-    train_dataset = qa_train_data.QATrainDataset(tokenizer, args.train_file, args.max_seq_len, args.max_q_len)
+    if pieces is None:
+        train_dataset = qa_train_data.QATrainDataset(tokenizer, args.train_file, args.max_seq_len, args.max_q_len)
     sampler = qa_train_data.MhopSampler(train_dataset, num_neg=args.neg_num)
-    arena = qa_train_arena.QATrainArena.load_or_build(args.train_file, train_dataset, tokenizer, log=logger.info).to(device)
+    arena = (pieces if pieces is not None else qa_train_arena.QATrainArena.load_or_build(args.train_file, train_dataset, tokenizer, log=logger.info)).to(device)
 
     def evaluate():
         chains, gold = run_batches(model.inference(), eval_loader, args, final=False)
