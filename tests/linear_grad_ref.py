@@ -70,7 +70,26 @@ M_SWEEP = [1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 300]   # 63 .. 65 and 127 .
 # 128 tile, and FFN2 at the M from which its dX leaves the one-tile GEMMs (17 slabs per chunk). assert_large() states the properties; the
 # host test holds it against the library's split, so a change of the split constants fails there instead of shrinking the coverage.
 # The host emulation runs over every one of them (a few seconds each).
-LARGE_MNK = [(2051, 768, 768), (2051, 2304, 768), (2051, 3072, 768), (11011, 256, 384), (33000, 64, 192), (33000, 192, 64), (4099, 768, 3072)]
+# The two reader shapes: the answer reader's fused QKV (S = 3, 704 rows per chunk, a last chunk of 643) and its out-projection (S = 7, 320
+# rows per chunk, a last chunk of 131), at the same smallest M as the retriever's.
+LARGE_MNK = [(2051, 768, 768), (2051, 2304, 768), (2051, 3072, 768), (11011, 256, 384), (33000, 64, 192), (33000, 192, 64), (4099, 768, 3072),
+             (2051, 3072, 1024), (2051, 1024, 1024)]
+# The four Linears of the answer reader at ELECTRA-large geometry (width 1024, FFN 4096): fused QKV, out-projection (and the pooler), FFN1
+# (the GELU path in the model), FFN2. M = 300 like MODEL_NK: several dW tiles in both directions at a width no roberta-base shape has, and
+# dX as a forward GEMM with (N, K) = (1024, 3072), (1024, 1024), (1024, 4096) and (4096, 1024).
+READER_NK = [(3072, 1024), (1024, 1024), (4096, 1024), (1024, 4096)]
+# The reader's pooler: packed_linear on the B CLS rows of a batch, no device-side row count. One row, a row count that is no multiple of
+# the MFMA's four-row groups, and one whole slab: the smallest, an odd and the largest batch the reader trains at.
+POOLER_MNK = [(1, 1024, 1024), (3, 1024, 1024), (64, 1024, 1024)]
+# The reader's FFN Linears have 32 x 8 = 256 dW tiles, so the split is S = 2 at EVERY M (512 / 256): two chunks however long. 2051 rows are
+# the smallest M of LARGE_MNK's kind: 1088 rows per chunk (17 slabs: the steady state of the slab loop, as long a chain as FFN2's at 4099
+# rows), a last chunk of 963 rows = 16 slabs, the last one 3 rows. assert_two_chunks() states it; assert_large() cannot (it wants S >= 3).
+TWO_CHUNK_MNK = [(2051, 4096, 1024), (2051, 1024, 4096)]
+# The smallest M, and a ragged one, at which dX of the reader's QKV and FFN1 leaves the one-tile GEMMs on 256 compute units (8 ceil(M / 256)
+# >= 384: M >= 12033): dX is then a persistent forward GEMM with N = 1024 and K = 3072 / 4096 (gemm_choose's K >= 2048 branch), and a chunk
+# of FFN1's dW (S = 2) is a chain of 97 slabs. FFN2's dX has GEMM N = 4096 > kPersistBiasMax and stays on the one-tile kernels at any M.
+# Too large for the host emulation (minutes in numpy's fp32 slab loop): the GPU test runs them on the exact grid alone.
+PERSIST_DX_MNK = [(12300, 3072, 1024), (12300, 4096, 1024)]
 
 
 def assert_large(shapes=None, chunks_of=None):
@@ -86,6 +105,18 @@ def assert_large(shapes=None, chunks_of=None):
         out.append((M, N, K, S, rpc, last))
     fewer = [(last + SLAB - 1) // SLAB < rpc // SLAB for *_, rpc, last in out]
     assert any(fewer) and not all(fewer), out
+    return out
+
+
+def assert_two_chunks(shapes=None, chunks_of=None):
+    """Every shape of TWO_CHUNK_MNK: exactly S = 2 chunks of three slabs or more (the slab loop's steady state), M no multiple of the slab and
+    a last chunk that is shorter than the first and not empty. Returns [(M, N, K, S, rows_per_chunk, rows of the last chunk)]."""
+    out = []
+    for M, N, K in (TWO_CHUNK_MNK if shapes is None else shapes):
+        S, rpc = (chunks_of or chunks)(M, N, K)
+        last = M - (S - 1) * rpc
+        assert S == 2 and rpc >= 3 * SLAB and M % SLAB != 0 and 0 < last < rpc, (M, N, K, S, rpc, last)
+        out.append((M, N, K, S, rpc, last))
     return out
 
 

@@ -7,7 +7,8 @@ tolerance here was read off a device. The one-hot, zero-score and zero-gradient 
 
 Many lengths are packed into one ragged call: at one head every length from 1 to 129 (twice the block of 64 owners, plus one); at twelve
 heads and L = 512 the lengths -1, 0, +1 around every multiple of the MFMA tile of 16 (the owner blocks and swept chunks of 64 are multiples
-of it) with 1, 2, 70, 300, 350, 511 and 512, in four interleaved groups so that a case's fp64 reference takes a few seconds. dqkv starts
+of it) with 1, 2, 70, 300, 350, 511 and 512, in four interleaved groups so that a case's fp64 reference takes a few seconds; at sixteen
+heads (the answer reader's, a row stride of 3072 halves) the second of those groups in two families, and the one-hot case. dqkv starts
 as a finite sentinel with 64 guard rows on both sides, which must keep their bits, in every call of this file.
 """
 import ctypes
@@ -28,6 +29,17 @@ pytestmark = pytest.mark.gpu
 GUARD = 64        # rows of dqkv in front of and behind the call's own, which must keep their bits
 LENS = [pytest.param(1, 129, ref.LENS_SWEEP, id="h1-L129-sweep")] + [
     pytest.param(12, 512, ref.LENS_EDGES[g::4], id=f"h12-L512-edges{g}") for g in range(4)]
+# The answer reader's ELECTRA-large: 16 heads, a row stride of 3 x 1024 halves in qkv and dqkv, where every case above has 64 or 768 per part.
+# One group of the edge lengths, in the two families that carry the most (realistic rows under four times the score scale, and a spike of 16).
+H16 = (16, 512, ref.LENS_EDGES[1::4])
+H16_ID = "h16-L512-edges1"
+H16_FAMILIES = ("realistic4", "spike16")
+
+
+def with_h16(params):
+    """params x every family, plus the 16-head case in H16_FAMILIES: [(heads, L, lens, family)] with the ids the stacked decorators gave"""
+    out = [pytest.param(*p.values, f, id=f"{p.id}-{f}") for f in ref.FAMILY_NAMES for p in params]
+    return out + [pytest.param(*H16, f, id=f"{H16_ID}-{f}") for f in H16_FAMILIES]
 
 
 def call(qkv, dctx, cu, heads, L, mode, out, ws="auto", stream="current"):
@@ -76,8 +88,7 @@ def dctx_for(cu, heads, mode, seed, scale=1.0):
 
 
 @pytest.mark.parametrize("scale", [1.0, 256.0], ids=["unit", "x256"])
-@pytest.mark.parametrize("family", ref.FAMILY_NAMES)
-@pytest.mark.parametrize("heads,L,lens", LENS)
+@pytest.mark.parametrize("heads,L,lens,family", with_h16(LENS))
 def test_every_query_within_the_derived_bound(heads, L, lens, family, scale):
     qkv, cu = ao.FAMILIES[family](lens, heads, 11)
     dctx = dctx_for(cu, heads, 0, 2, scale)
@@ -85,8 +96,7 @@ def test_every_query_within_the_derived_bound(heads, L, lens, family, scale):
 
 
 @pytest.mark.parametrize("scale", [1.0, 256.0], ids=["unit", "x256"])
-@pytest.mark.parametrize("family", ref.FAMILY_NAMES)
-@pytest.mark.parametrize("heads,L,lens", [pytest.param(1, 129, ref.LENS_SWEEP, id="h1-L129-sweep"), pytest.param(12, 512, ref.LENS_EDGES, id="h12-L512-edges")])
+@pytest.mark.parametrize("heads,L,lens,family", with_h16([pytest.param(1, 129, ref.LENS_SWEEP, id="h1-L129-sweep"), pytest.param(12, 512, ref.LENS_EDGES, id="h12-L512-edges")]))
 def test_first_query_within_the_derived_bound(heads, L, lens, family, scale):
     """Mode 3. The dQ rows behind a sequence's first have reference 0 and bound 0: they must compare equal to zero."""
     qkv, cu = ao.FAMILIES[family](lens, heads, 11)
@@ -94,7 +104,8 @@ def test_first_query_within_the_derived_bound(heads, L, lens, family, scale):
     check_bound(run(qkv, dctx, cu, heads, L, 3), qkv, dctx, cu, heads, 3, f"family={family} heads={heads} L={L} scale={scale}")
 
 
-@pytest.mark.parametrize("heads,L,lens", [pytest.param(1, 129, ref.LENS_SWEEP, id="h1-L129-sweep"), pytest.param(12, 512, ref.LENS_EDGES[1::4], id="h12-L512-edges1")])
+@pytest.mark.parametrize("heads,L,lens", [pytest.param(1, 129, ref.LENS_SWEEP, id="h1-L129-sweep"), pytest.param(12, 512, ref.LENS_EDGES[1::4], id="h12-L512-edges1"),
+                                          pytest.param(*H16, id=H16_ID)])
 def test_onehot_permutation_moves_dO_rows_bit_for_bit(heads, L, lens):
     """q_i = code(pi(i)): the fp16-rounded p is exactly a permutation matrix, so dV[pi(i)] == dO[i] bit for bit -- the query-to-key map of every
     tile, chunk, lane slot and block. dQ and dK stay within the bound."""

@@ -40,6 +40,9 @@ SHAPES = [  # (M, N, K): encoder shapes incl. ragged M, one tile, many tiles per
     # is asked for), FFN2 (K = 4096: the four-wave kernel's K >= 2048 branch), QKV, out-projection; FFN2 at the reader's M_est = 32768 - 32768 / 3 and at 256 * 80 + 1 rows
     (1536, 4096, 1024), (32768, 4096, 1024), (20000, 1024, 4096), (32768, 1024, 4096), (32768, 3072, 1024), (32768, 1024, 1024), (21846, 1024, 4096),
     (20481, 1024, 4096),
+    # dX of the reader's fused QKV projection in training (N = 1024, K = 3072): on the one-tile kernels, and past the 12033 rows from which 256 compute
+    # units hand it to a persistent kernel (K >= 2048: the four-wave kernel's branch)
+    (2413, 1024, 3072), (12300, 1024, 3072),
 ]
 
 

@@ -15,6 +15,19 @@ one whole tile, several tiles with a remainder, each at M = 1 .. 300 around the 
 the four Linears of roberta-base at M = 300; and linear_grad_ref.LARGE_MNK, the smallest training row counts at which a chunk of the
 weight-gradient kernel holds three slabs or more (its register double buffer in the steady state, S >= 3 partials, a ragged last chunk) and
 at which dX of FFN2 leaves the one-tile GEMMs for a persistent kernel with its device-side row count.
+
+The answer reader's geometry (ELECTRA-large: width 1024, FFN 4096), each shape the smallest that reaches its path:
+READER_NK        the reader's four Linears at M = 300 beside roberta-base's: 8 dW tile columns (K = 1024) or 32 (K = 4096) where the
+                 retriever has 6 or 24, and dX as a forward GEMM of (N, K) = (1024, 3072), (1024, 1024), (1024, 4096), (4096, 1024).
+POOLER_MNK       (1024, 1024) at M = 1, 3 and 64 rows without a device-side row count: the pooler runs on the B CLS rows of a batch, and
+                 below M = 300 the model widths were never run (one row, a count that is no multiple of 4, one whole slab).
+LARGE_MNK        gains the fused QKV (2051, 3072, 1024): S = 3, and the out-projection (2051, 1024, 1024): S = 7, at the list's own smallest M.
+TWO_CHUNK_MNK    FFN1 and FFN2 at 2051 rows. Their 256 dW tiles make the split S = 2 at every M, which assert_large (S >= 3) rules out and
+                 the small shapes only have with ONE slab per chunk; here a chunk is 17 slabs and the last ends on a slab of 3 rows.
+PERSIST_DX_MNK   QKV and FFN1 at 12300 rows: from 12033 rows on (256 compute units) their dX leaves the one-tile GEMMs for a persistent one
+                 with N = 1024 and K = 3072 / 4096, and a chunk of FFN1's dW is a chain of 97 slabs. On the exact grid alone (every sum stays
+                 exact: exact_grid asserts it), with a device-side row count one row into the last row tile. FFN2's dX (GEMM N = 4096, wider
+                 than kPersistBiasMax) stays on the one-tile kernels at every M, which is asserted instead of run.
 """
 import numpy as np
 import pytest
@@ -29,9 +42,12 @@ pytestmark = pytest.mark.gpu
 
 GUARD = 64        # rows of dx / elements of dw and db in front of and behind the call's own, which must keep their bits
 # (M, N, K): M None is the shape's sweep of small row counts (ms_for); LARGE_MNK gives its own M
-ALL_NK = [pytest.param(None, N, K, id=f"N{N}-K{K}") for N, K in ref.SMALL_NK + ref.MODEL_NK] + \
-         [pytest.param(M, N, K, id=f"M{M}-N{N}-K{K}") for M, N, K in ref.LARGE_MNK]
+ALL_NK = [pytest.param(None, N, K, id=f"N{N}-K{K}") for N, K in ref.SMALL_NK + ref.MODEL_NK + ref.READER_NK] + \
+         [pytest.param(M, N, K, id=f"M{M}-N{N}-K{K}") for M, N, K in ref.LARGE_MNK + ref.TWO_CHUNK_MNK]
+POOLER = [pytest.param(M, N, K, id=f"M{M}-N{N}-K{K}") for M, N, K in ref.POOLER_MNK]
+PERSIST_DX = [pytest.param(M, N, K, id=f"M{M}-N{N}-K{K}") for M, N, K in ref.PERSIST_DX_MNK]
 FFN2_LARGE = (4099, 768, 3072)  # the shape of LARGE_MNK whose dX takes a persistent GEMM
+READER_FFN2 = (1024, 4096)      # (N, K) of the reader Linear whose dX stays on the one-tile GEMMs at every M
 
 
 def ms_for(N, K, M=None):
@@ -136,7 +152,7 @@ def grid_inputs(M, N, K, seed, loss_scale=False):
 
 def test_some_tested_shape_is_split():
     from multihop_dense_retrieval_amd import linear
-    split = [(M, N, K) + linear.backward_chunks(M, N, K) for N, K in ref.SMALL_NK + ref.MODEL_NK for M in ms_for(N, K)]
+    split = [(M, N, K) + linear.backward_chunks(M, N, K) for N, K in ref.SMALL_NK + ref.MODEL_NK + ref.READER_NK for M in ms_for(N, K)]
     assert any(S > 1 for *_, S, _ in split)
     # M_SWEEP's 63 .. 65 and 127 .. 129 are -1, 0, +1 around one and two chunks wherever the shape is split
     for M, N, K, S, rpc in split:
@@ -161,8 +177,30 @@ def test_large_shapes_reach_the_steady_state_and_the_persistent_gemm():
     assert gemm_ref.flavour(0, 300, 300, K, N, 0, ncu) in ("small", "mid")
 
 
+def test_reader_shapes_have_two_long_chunks_and_reach_the_persistent_gemm():
+    """TWO_CHUNK_MNK against the LIBRARY's split: S = 2 with 17 slabs a chunk and a ragged last one (linear_grad_ref.assert_two_chunks). dX of
+    the PERSIST_DX_MNK shapes (GEMM N = the Linear's K = 1024, GEMM K = 3072 and 4096) leaves the one-tile kernels on this device, and stays
+    on them at the largest M below the threshold that M = 300 and 2051 stand for; FFN1's chunk there is 97 slabs. dX of the reader's FFN2 has
+    GEMM N = 4096 > kPersistBiasMax: a one-tile kernel at every M, so no large M is run for it."""
+    import gemm_ref
+    from multihop_dense_retrieval_amd import linear
+    props = ref.assert_two_chunks(chunks_of=linear.backward_chunks)
+    assert props == ref.assert_two_chunks()
+    assert [(rpc, last) for *_, rpc, last in props] == [(17 * ref.SLAB, 15 * ref.SLAB + 3)] * 2
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    for M, N, K in ref.PERSIST_DX_MNK:
+        assert gemm_ref.flavour(0, M, M, K, N, 0, ncu) in ("persist", "big", "quad"), (M, N, K, ncu, gemm_ref.flavour(0, M, M, K, N, 0, ncu))
+        for small_m in (300, 2051):
+            assert gemm_ref.flavour(0, small_m, small_m, K, N, 0, ncu) in ("small", "mid"), (small_m, N, K)
+    assert linear.backward_chunks(12300, 4096, 1024) == (2, 97 * ref.SLAB)
+    N, K = READER_FFN2
+    assert READER_FFN2 in ref.READER_NK and (2051, N, K) in ref.TWO_CHUNK_MNK
+    for M in (300, 2051, 12300, 32768, 65536):
+        assert gemm_ref.flavour(0, M, M, K, N, 0, ncu) in ("small", "mid"), (M, gemm_ref.flavour(0, M, M, K, N, 0, ncu))
+
+
 @pytest.mark.parametrize("loss_scale", [False, True], ids=["unit", "x256"])
-@pytest.mark.parametrize("M,N,K", ALL_NK)
+@pytest.mark.parametrize("M,N,K", ALL_NK + POOLER + PERSIST_DX)
 def test_exact_grid_equality(M, N, K, loss_scale):
     for M in ms_for(N, K, M):
         x, w, dy = grid_inputs(M, N, K, 3, loss_scale)
@@ -189,9 +227,10 @@ def check_bound(got, rb, m, label):
 
 
 @pytest.mark.parametrize("scale", [1.0, 256.0], ids=["unit", "x256"])
-@pytest.mark.parametrize("M,N,K", ALL_NK)
+@pytest.mark.parametrize("M,N,K", ALL_NK + POOLER)
 def test_realistic_rows_within_the_derived_bound(M, N, K, scale):
-    """Identity and GELU path (u from the forward hook with epilogue 0), and the GELU path with one invalid row of NaN behind m = M - 1."""
+    """Identity and GELU path (u from the forward hook with epilogue 0), and the GELU path with one invalid row of NaN behind m = M - 1 (the
+    pooler's shapes too, beside their calls without a device-side row count)."""
     for M in ms_for(N, K, M):
         x, w, dy = ref.realistic(M, N, K, 11, scale)
         check_bound(run(x, w, dy), ref.reference_and_bound(x, w, dy), M, f"identity M={M} N={N} K={K} scale={scale}")
@@ -242,21 +281,45 @@ def large_ms(M, N, K):
     return ms
 
 
+def two_chunk_ms(M, N, K):
+    """valid-row counts for a shape of two long chunks (large_ms needs S >= 3): none, one row into the second slab of chunk 0, one row short of
+    the seam, the seam itself (chunk 1 all zero-fill), a count that cuts chunk 1 in its second slab, all"""
+    S, rpc = ref.chunks(M, N, K)
+    ms = (0, ref.SLAB + 1, rpc - 1, rpc, rpc + ref.SLAB + 6, M)
+    assert S == 2 and rpc >= 3 * ref.SLAB and list(ms) == sorted(set(ms))
+    return ms
+
+
+def valid_rows(M, N, K):
+    if M == 200:
+        return (0, 1, M - 1, M)
+    if (M, N, K) in ref.TWO_CHUNK_MNK:
+        return two_chunk_ms(M, N, K)
+    if (M, N, K) in ref.PERSIST_DX_MNK:  # one count: one row into the last row tile of dX's persistent GEMM (256 rows, and 128 in its tail)
+        m = (M - 1) // 256 * 256 + 1
+        assert M - 128 < m - 1 and m < M
+        return (m,)
+    return large_ms(M, N, K)
+
+
 # the small shapes at M = 200 on both paths; (2051, 768, 768) and FFN2 at 4099 rows (dX through a persistent GEMM whose device-side row count
-# lies well below the cap) once each, one on either path
+# lies well below the cap) once each, one on either path; the reader's FFN1 (the GELU path in the model) and FFN2 with their two long chunks;
+# the reader's QKV and FFN1 at 12300 rows, dX through a persistent GEMM whose row count ends one row into the last row tile
 ROWS_BEHIND = [pytest.param(200, N, K, g, id=f"{'gelu0' if g else 'identity'}-N{N}-K{K}") for g in (False, True) for N, K in ((128, 128), (256, 384), (768, 768))] + \
-              [pytest.param(2051, 768, 768, False, id="identity-M2051-N768-K768"), pytest.param(*FFN2_LARGE, True, id="gelu0-M4099-N768-K3072")]
+              [pytest.param(2051, 768, 768, False, id="identity-M2051-N768-K768"), pytest.param(*FFN2_LARGE, True, id="gelu0-M4099-N768-K3072"),
+               pytest.param(2051, 4096, 1024, True, id="gelu0-M2051-N4096-K1024"), pytest.param(2051, 1024, 4096, False, id="identity-M2051-N1024-K4096"),
+               pytest.param(12300, 3072, 1024, False, id="identity-M12300-N3072-K1024"), pytest.param(12300, 4096, 1024, True, id="gelu0-M12300-N4096-K1024")]
 
 
 @pytest.mark.parametrize("M,N,K,gelu0", ROWS_BEHIND)
 def test_rows_behind_m_dev_do_not_exist(M, N, K, gelu0):
-    """m in {0, 1, M - 1, M} (the large shapes: large_ms), rows at or behind m of x, dy and pre NaN and Inf: outputs finite and equal, bit for
+    """m in {0, 1, M - 1, M} (the large shapes: valid_rows), rows at or behind m of x, dy and pre NaN and Inf: outputs finite and equal, bit for
     bit, to the call on the first m rows alone (on the grid every sum is exact, so the different split of the shorter call does not matter);
     dx rows at or behind m keep the sentinel (run() asserts it); m = 0 gives zeros, or the old value with accumulate."""
     x, w, dy = grid_inputs(M, N, K, 17)
     pre = np.zeros((M, N), np.float16) if gelu0 else None
     old_dw, old_db = fp.grid((N, K), 18), fp.grid((N,), 19)
-    for m in ((0, 1, M - 1, M) if M == 200 else large_ms(M, N, K)):
+    for m in valid_rows(M, N, K):
         xb, dyb = x.copy(), dy.copy()
         xb[m:], dyb[m:] = np.nan, np.inf
         xb[m + 1::2], dyb[m + 1::2] = -np.inf, np.nan

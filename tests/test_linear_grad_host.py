@@ -1,6 +1,10 @@
 """CPU: the fp64 statement of the Linear backward (tests/linear_grad_ref.py) against torch.autograd in float64, the fp32 gelu' formula over
 every finite fp16 pre-activation, the emulation of the kernels' dataflow against the derived bound, each mutation against the same bound,
-and the header / binding / split contract of include/mdr_linear_grad.h. No device and no kernel runs here."""
+and the header / binding / split contract of include/mdr_linear_grad.h. No device and no kernel runs here.
+
+The emulation runs over every list of the GPU test -- SMALL_NK, MODEL_NK, READER_NK, POOLER_MNK, LARGE_MNK, TWO_CHUNK_MNK -- except
+PERSIST_DX_MNK: (12300, 3072, 1024) and (12300, 4096, 1024) cost six times the largest case here (the numpy slab loop and three fp64 products
+of 12300 x 4096 x 1024, about a minute a shape) and are left to the GPU test, which runs them on the exact grid, where no bound is needed."""
 
 import numpy as np
 import pytest
@@ -73,8 +77,8 @@ def test_gelu_grad_formula_over_every_finite_fp16():
     assert (wrong > bnd).any()
 
 
-@pytest.mark.parametrize("M,N,K", [pytest.param(None, N, K, id=f"{N}-{K}") for N, K in ref.SMALL_NK + ref.MODEL_NK] +
-                         [pytest.param(M, N, K, id=f"M{M}-{N}-{K}") for M, N, K in ref.LARGE_MNK])
+@pytest.mark.parametrize("M,N,K", [pytest.param(None, N, K, id=f"{N}-{K}") for N, K in ref.SMALL_NK + ref.MODEL_NK + ref.READER_NK] +
+                         [pytest.param(M, N, K, id=f"M{M}-{N}-{K}") for M, N, K in ref.POOLER_MNK + ref.LARGE_MNK + ref.TWO_CHUNK_MNK])
 def test_emulation_stays_inside_the_bound(M, N, K):
     """A second implementation of the listed dataflow, on every shape the GPU tests use, identity and GELU, unit and loss scale (the shapes
     of LARGE_MNK, where the slab loop and the chunk reduction add thousands of terms: under the loss scale, as in training)."""
@@ -111,8 +115,8 @@ def test_split_is_a_function_of_the_shape_and_workspace_covers_it():
     from multihop_dense_retrieval_amd import linear
     lib = linear.lib()
     some_split = False
-    for N, K in ref.SMALL_NK + ref.MODEL_NK:
-        for M in ref.M_SWEEP + [8608, 20000]:
+    for N, K in ref.SMALL_NK + ref.MODEL_NK + ref.READER_NK:
+        for M in ref.M_SWEEP + [8608, 20000, 32768]:
             S, rpc = linear.backward_chunks(M, N, K)
             assert (S, rpc) == ref.chunks(M, N, K) and S >= 1 and rpc % 64 == 0 and (S - 1) * rpc < M <= S * rpc, (M, N, K, S, rpc)
             some_split |= S > 1
@@ -120,9 +124,19 @@ def test_split_is_a_function_of_the_shape_and_workspace_covers_it():
             assert full >= M * N * 2 + N * K * 2 + K * 4 + (S * N * K * 4 + S * N * 4 if S > 1 else 0)
             assert lib.mdr_linear_backward_workspace_bytes(M, N, K, 4) == (0 if S == 1 else (S * N * 4 + 255) // 256 * 256)
     assert some_split
-    for M, N, K, S, rpc, _ in ref.assert_large(chunks_of=linear.backward_chunks):  # the large shapes keep their properties under the LIBRARY's split
+    # the large shapes, and the reader's FFN shapes with their two long chunks, keep their properties under the LIBRARY's split
+    for M, N, K, S, rpc, _ in ref.assert_large(chunks_of=linear.backward_chunks) + ref.assert_two_chunks(chunks_of=linear.backward_chunks):
         assert (S, rpc) == ref.chunks(M, N, K)
         assert lib.mdr_linear_backward_workspace_bytes(M, N, K, 15) >= M * N * 2 + N * K * 2 + K * 4 + S * N * K * 4 + S * N * 4
+    assert ref.assert_two_chunks(chunks_of=linear.backward_chunks) == [(2051, 4096, 1024, 2, 1088, 963), (2051, 1024, 4096, 2, 1088, 963)]
+    for M in ref.M_SWEEP + [2051, 12300, 32768]:  # the reader's FFN shapes: 256 dW tiles, so never more than two chunks, and two from 65 rows on
+        for N, K in ((4096, 1024), (1024, 4096)):
+            assert linear.backward_chunks(M, N, K)[0] == (2 if M > ref.SLAB else 1), (M, N, K)
+    for M, N, K in ref.POOLER_MNK:  # the pooler's row counts fit one slab: one chunk, no partials
+        assert linear.backward_chunks(M, N, K) == ref.chunks(M, N, K) == (1, ref.SLAB)
+    for M, N, K in ref.PERSIST_DX_MNK:
+        assert linear.backward_chunks(M, N, K) == ref.chunks(M, N, K)
+    assert linear.backward_chunks(12300, 4096, 1024) == (2, 97 * ref.SLAB)
     for M, N, K in ((0, 64, 64), (-1, 64, 64), (5, 0, 64), (5, 64, 0), (5, 96, 64), (5, 64, 100), (5, -64, 64)):
         assert lib.mdr_linear_backward_workspace_bytes(M, N, K, 15) == 0
         assert linear.backward_chunks(M, N, K) == (0, 0)

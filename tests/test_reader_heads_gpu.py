@@ -3,7 +3,10 @@ tests/reader_loss_ref.py, and the whole brick -- CLS gather, linear.packed_linea
 backward() -- against the gradients the reference's own QAModel.forward produced in fp32 (tests/golden/reader_loss_ref.npz).
 
 Bounds: the helper's DERIVED windows (fp32 accumulation in any order; an fp16 rounding may flip only where a boundary lies inside the fp32
-error). On the exact grid every product and sum is exact in fp32, so the logits are the helper's bits."""
+error). On the exact grid every product and sum is exact in fp32, so the logits are the helper's bits.
+
+Shapes of the backward: SINGLE_ROW (B L <= 256: one token row per wave of the token kernel) and SEVERAL_ROWS (whole batches of L = 512 at
+H = 1024 and 128, the smallest with two and three rows per wave); the comments at the lists say why each is there."""
 import os
 
 import numpy as np
@@ -97,8 +100,9 @@ def test_forward_on_an_exact_grid_is_bit_equal():
     assert fp.same_bits(got["rank"], val["rank"].astype(np.float16))
 
 
-@pytest.mark.parametrize("H,B,L,NS", [(128, 3, 33, 4), (768, 5, 40, 5), (1024, 4, 64, 30), (256, 1, 17, 0)])
+@pytest.mark.parametrize("H,B,L,NS", [(128, 3, 33, 4), (768, 5, 40, 5), (1024, 4, 64, 30), (256, 1, 17, 0), (1024, 6, 512, 30)])
 def test_forward_within_the_derived_bound(H, B, L, NS):
+    """(the last case: rows of L = 512 logits at the reader's width, the first of SEVERAL_ROWS below)"""
     c = ref.make_heads_case(B, L, NS, H, 5)
     got = forward(c, device_case(c))
     val, win = ref.heads_forward(c["seq"], c["dense"], c["lens"], c["pmask"], c["offs"], c["P"])
@@ -110,14 +114,30 @@ def test_forward_within_the_derived_bound(H, B, L, NS):
 
 # T = 127, 128, 129 packed rows; B in {1, 4, 5}; ragged rows; NS = 30 > 2 duplicate markers and padded offsets that name the CLS row; B L / 4 chunks
 # of the token split (rows per chunk = 4 at these sizes: 32 .. 64 chunks, more than the 16 strands of the second stage)
-BACKWARD = [(128, 1, 127, 0, [127]), (128, 4, 40, 5, [40, 33, 30, 25]), (768, 5, 40, 5, [40, 20, 31, 17, 21]), (1024, 4, 64, 30, None), (256, 5, 50, 1, None)]
+SINGLE_ROW = [(128, 1, 127, 0, [127]), (128, 4, 40, 5, [40, 33, 30, 25]), (768, 5, 40, 5, [40, 20, 31, 17, 21]), (1024, 4, 64, 30, None), (256, 5, 50, 1, None)]
+# With B L <= 256 a chunk of the token split is 4 rows: each of the four waves of reader_heads_token_grad_kernel walks ONE row, its fp32 fma
+# chains a0 / a1 / a2 hold one term and the `i += 4` loop body runs once -- an accumulator that is overwritten instead of added to passes all
+# of the above. The chunk grows only with B L (1024 chunks at the most, fewer at H = 1024 where the partials' byte cap binds first), so the
+# smallest shapes with several rows per wave are whole batches of L = 512, the reader's own row length: at H = 1024, B = 3 is the smallest
+# batch with 8 rows per chunk (2 per wave, 192 chunks) and B = 6 the smallest with 12 (3 per wave, 256 chunks, NS = 30 markers); at H = 128,
+# the other end of the widths, B = 9 is the smallest with 8 (576 chunks, 36 for each of the sixteen strands of the second stage). Ragged rows of
+# the helper's own lengths: a wave's rows lie in different sequences and some are skipped as padding.
+SEVERAL_ROWS = [(1024, 6, 512, 30, None), (1024, 3, 512, 5, None), (128, 9, 512, 5, None)]
+BACKWARD = SINGLE_ROW + SEVERAL_ROWS
 
 
 @pytest.mark.parametrize("H,B,L,NS,lens", BACKWARD, ids=[f"H{s[0]}-B{s[1]}-L{s[2]}-NS{s[3]}" for s in BACKWARD])
 def test_backward_within_the_derived_bound(H, B, L, NS, lens):
     from multihop_dense_retrieval_amd import reader_loss
     c = ref.make_heads_case(B, L, NS, H, 7, lens=lens)
-    assert int(reader_loss.lib().mdr_reader_heads_backward_workspace_bytes(B, L, H)) >= 3 * H * 4 * 8  # several chunks
+    ws_bytes = int(reader_loss.lib().mdr_reader_heads_backward_workspace_bytes(B, L, H))
+    assert ws_bytes >= 3 * H * 4 * 8  # several chunks
+    if (H, B, L, NS, lens) in SEVERAL_ROWS:  # the workspace is [S][3][H] floats: S chunks of at least 8 rows, two rows or more for every wave
+        assert ws_bytes % (3 * H * 4) == 0
+        S = ws_bytes // (3 * H * 4)
+        assert S * 8 <= (B * L + 7) // 8 * 8, (S, B * L)
+        live = np.arange(L)[None, :] < np.asarray(c["lens"])[:, None]
+        assert B * L % S == 0 and (live.reshape(S, B * L // S).sum(axis=1) >= 8).any(), "no chunk holds two live rows for every wave"
     if lens is not None:
         assert sum(lens) in (127, 128, 129)
     if NS >= 2:

@@ -19,9 +19,13 @@ pytestmark = pytest.mark.gpu
 
 G0, SPW = 64.0, 1.0
 # (B, L, A, NS): every B of {1, 3, 4, 5, 97}, every L of {1, 63, 64, 65, 256, 257, 512} (one wave of positions, its edges, 256 = one position per
-# thread, 257 = the second position of thread 0, 512 = the LDS rows full), every A of {1, 3, 64, 65} (65: no tile edge, but past one wave of
-# candidates) and every NS of {0, 1, 5, 30} appear
-SHAPES = [(1, 1, 1, 0), (3, 63, 3, 1), (4, 64, 64, 5), (5, 65, 65, 30), (97, 256, 3, 5), (4, 257, 1, 30), (3, 512, 65, 5)]
+# thread, 257 = the second position of thread 0, 512 = the LDS rows full), every A of {1, 3, 64, 65, 256, 257, 300, 513} and every NS of
+# {0, 1, 5, 30} appear. reader_loss_grad_kernel stages the candidates in LDS in tiles of 256 (the `a0` loop): A <= 65 stays inside the first
+# tile (65: past one wave of candidates). 256 = exactly one tile, the smallest A at which n = min(256, A - a0) is the whole tile; 257 = one
+# candidate into the second trip, the smallest at which ts / te / tp are written again behind the barrier; 513 = one into the third, the
+# smallest with two re-uses, at L = 512 (LDS rows full); 300 = a ragged second tile of 44 at L = 512 with the most markers and the most rows
+SHAPES = [(1, 1, 1, 0), (3, 63, 3, 1), (4, 64, 64, 5), (5, 65, 65, 30), (97, 256, 3, 5), (4, 257, 1, 30), (3, 512, 65, 5),
+          (4, 300, 256, 1), (3, 64, 257, 0), (2, 512, 513, 5), (5, 512, 300, 30)]
 KEYS = ("start", "end", "rank", "sp")
 
 
@@ -161,14 +165,16 @@ def test_an_overflowing_scale_arrives_as_infinity_of_the_right_sign():
 
 
 def test_two_runs_and_a_side_stream_give_the_same_bits():
-    inp = ref.make_loss_case(5, 257, 65, 5, seed=11)
-    a = run(inp)
-    b = run(inp)
-    c = run(inp, stream=torch.cuda.Stream())
-    for other in (b, c):
-        assert fp.same_bits(np.float32(a[0]), np.float32(other[0]))
-        for k in a[1]:
-            assert fp.same_bits(a[1][k], other[1][k]), k
+    """(the second case: three trips through the candidate tiles, the LDS rows written three times)"""
+    for B, L, A, NS in ((5, 257, 65, 5), (2, 512, 513, 5)):
+        inp = ref.make_loss_case(B, L, A, NS, seed=11)
+        a = run(inp)
+        b = run(inp)
+        c = run(inp, stream=torch.cuda.Stream())
+        for other in (b, c):
+            assert fp.same_bits(np.float32(a[0]), np.float32(other[0])), (A,)
+            for k in a[1]:
+                assert fp.same_bits(a[1][k], other[1][k]), (A, k)
 
 
 @pytest.mark.parametrize("has_sp", [True, False])
