@@ -72,4 +72,9 @@ def train_args(argv=None):
     p.add_argument("--stop-drop", default=0, type=float)
     p.add_argument("--use-adam", action="store_true")
     p.add_argument("--warmup-ratio", default=0, type=float)
+    # several ranks (scripts/train_mhop.py --do_train under a launcher): not the reference's flags
+    p.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl")  # "nccl" is RCCL
+    p.add_argument("--share-gpu", action="store_true")  # every rank on device 0, gloo only: the rehearsal on one card
+    p.add_argument("--dist-timeout", type=int, default=1800)  # seconds, init_process_group's
+    p.add_argument("--check-ranks", action="store_true")  # compare the parameters' checksum over the ranks at every evaluation
     return p.parse_args(argv)

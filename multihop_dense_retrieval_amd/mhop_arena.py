@@ -306,17 +306,21 @@ class MhopArena:
         _lib.call(lib().mdr_mhop_assemble, ctypes.byref(a), _lib.ptr(table_dev), B, (_c.c_int32 * 6)(*widths), ids, mask, int(pad_id), dev=dev)  # B == 0: a no-op
         return out
 
-    def feed(self, batch_size, shuffle):
-        return Feed(self, batch_size, shuffle)
+    def feed(self, batch_size, shuffle, rank_rows=None):
+        return Feed(self, batch_size, shuffle, rank_rows)
 
 
 class Feed:
     """The device batches of one arena, an iterable with len(). The index order comes from a torch DataLoader over the bare indices with the
     host feed's batch_size, shuffle and num_workers=0, so torch's global generator is drawn from exactly as the host feed's loader draws (the
     sampler's seed and the iterator's base seed) and len() is that loader's. A step's only host-to-device traffic is its row table, copied
-    from one of RING pinned tables; a table is written again only after the event behind its last copy has completed."""
+    from one of RING pinned tables; a table is written again only after the event behind its last copy has completed.
 
-    def __init__(self, arena, batch_size, shuffle):
+    rank_rows: None, or on one rank of several (dist.py) the function from a batch's sample count B to this rank's rows (lo, hi). Every rank
+    makes the same draws and builds the same [B, 6] table, so `random` and torch's generator move as on one rank; the rank then assembles its
+    rows alone, padded to the FULL table's widths, and the batch says so under train.RANK_ROWS: (lo, hi, B)."""
+
+    def __init__(self, arena, batch_size, shuffle, rank_rows=None):
         if arena.dev is None:
             raise RuntimeError("MhopArena.to(device) first")
         self.arena = arena
@@ -325,6 +329,7 @@ class Feed:
         self.ring = [torch.empty((max(1, int(batch_size)), 6), dtype=torch.int32).pin_memory() for _ in range(RING)]
         self.busy = [None] * RING
         self.at = 0
+        self.rank_rows = rank_rows
 
     def __len__(self):
         return len(self.loader)
@@ -345,4 +350,10 @@ class Feed:
     def __iter__(self):
         for indices in self.loader:
             table, widths = self.arena.choose(indices)
-            yield self.arena.assemble(self.upload(table), widths)
+            if self.rank_rows is None:
+                yield self.arena.assemble(self.upload(table), widths)
+            else:
+                lo, hi = self.rank_rows(len(table))
+                batch = self.arena.assemble(self.upload(np.ascontiguousarray(table[lo:hi])), widths)
+                batch["_rank_rows"] = (lo, hi, len(table))  # train.RANK_ROWS
+                yield batch

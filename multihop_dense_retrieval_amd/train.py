@@ -207,14 +207,53 @@ def optimizer_for(model, args, loss_scale="dynamic"):
                            fp16_copies=[P[n] for n in fp16_copy_names(list(P))])
 
 
-def train_step(model, batch, args, opt, seed):
+RANK_ROWS = "_rank_rows"  # a batch that holds one rank's rows alone says so here: (lo, hi, B), widths of the full batch (mhop_arena.Feed)
+
+
+def rank_outputs(model, batch, opt, seed, world):
+    """This rank's part of one forward on several ranks: the six matrices of the full batch, differentiable with respect to
+    this rank's rows. The rank encodes rows dist.slice_bounds(B, N)[rank] of the full-batch tensors (the widths are the full batch's, so a
+    sequence's input does not depend on the rank count) under dist.rank_seed(seed, rank), and dist.gather_with_grad puts every rank's rows
+    together. A rank whose slice is empty makes no encoder call, contributes zero rows and still joins the six gathers."""
+    from . import dist
+    if RANK_ROWS in batch:
+        lo, hi, B = batch[RANK_ROWS]
+        local = batch
+    else:
+        B = int(batch["q_input_ids"].shape[0])
+        lo, hi = dist.slice_bounds(B, world.size)[world.rank]
+        local = {k: v[lo:hi] if torch.is_tensor(v) and v.dim() and v.shape[0] == B else v for k, v in batch.items()}
+    bounds = dist.slice_bounds(B, world.size)
+    if (lo, hi) != bounds[world.rank]:
+        raise ValueError(f"the batch holds rows {lo} .. {hi} of {B}, rank {world.rank} of {world.size} owns {bounds[world.rank]}")
+    if hi > lo:
+        outputs = model(local, seed=dist.rank_seed(seed, world.rank), half=opt.half)
+    else:
+        dev = next(model.parameters()).device
+        outputs = {name: torch.zeros((0, model.config.hidden_size), dtype=torch.float32, device=dev) for name in ENCODE_INDEX}
+    return {name: dist.gather_with_grad(world, outputs[name], bounds) for name in ENCODE_INDEX}, hi > lo
+
+
+def train_step(model, batch, args, opt, seed, world=None, bucket=None):
     """One forward and backward of the in-batch loss: criterions.mhop_loss over model(batch, seed, opt.half), divided by
     gradient_accumulation_steps, scaled by the optimizer's loss scale for the backward. Returns the unscaled loss (a 0-d device tensor). The
-    caller owns opt.step() and scheduler.step(); FusedAdam zeroes the gradients in place, so zero_grad() is never called."""
+    caller owns opt.step() and scheduler.step(); FusedAdam zeroes the gradients in place, so zero_grad() is never called.
+
+    world (a dist.TorchWorld or a rank of dist.LoopbackWorld) and bucket (the dist.GradBucket behind the parameters' gradients): the step of
+    one rank of several. The loss is the full batch's on every rank, the backward fills this rank's share of the gradients, and the caller
+    runs bucket.reduce() at the accumulation boundary, immediately before opt.step()."""
     if getattr(args, "momentum", False):
         raise NotImplementedError("--momentum is not built: the reference trains it from a script of its own")
-    loss = criterions.mhop_loss(lambda b: model(b, seed=seed, half=opt.half), batch, args)
+    if world is None:
+        loss = criterions.mhop_loss(lambda b: model(b, seed=seed, half=opt.half), batch, args)
+        has_rows = True
+    else:
+        if bucket is None or bucket.world is not world:
+            raise ValueError("a step on several ranks needs the dist.GradBucket of this world behind the gradients")
+        outputs, has_rows = rank_outputs(model, batch, opt, seed, world)
+        loss = criterions.mhop_loss_outputs(outputs, args)
     if args.gradient_accumulation_steps > 1:
         loss = loss / args.gradient_accumulation_steps
-    opt.scale_loss(loss).backward()
+    if has_rows:  # a rank without rows has nothing to differentiate: its bucket stays all zero
+        opt.scale_loss(loss).backward()
     return loss.detach()
