@@ -340,29 +340,27 @@ def chain_results(batch, head, sp_pred, final=False):
     return out
 
 
-def predict_metrics(chains, gold, sp_pred, logger, fixed_thresh=None):
-    """predict()'s ranking / metrics / log lines over all chains ([(qid, label, answer dict)] in dataloader order) and
-    gold = {qid: (gold_answer, sp_gold)}. Returns (metrics dict, best_res)."""
-    id2result, id2answer = collections.defaultdict(list), collections.defaultdict(list)
-    for qid, label, ans in chains:
-        id2result[qid].append((label, ans["rank_score"]))
-        id2answer[qid].append(ans)
-    acc = []
-    for qid, res in id2result.items():
-        res.sort(key=lambda x: x[1], reverse=True)
-        acc.append(res[0][0] == 1)
-    logger.info(f"evaluated {len(id2result)} questions...")
+def combination_factors(fixed_thresh=None):
+    """predict()'s combination factors: the fixed one, or the sweep 0, 0.1, ..., 1."""
+    return [fixed_thresh] if fixed_thresh else [0, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9, 1]
+
+
+def metrics_report(qids, acc, lambdas, top, gold, sp_pred, logger):
+    """predict()'s metric arithmetic and log lines, the ONE statement of them: predict_metrics below (every chain decoded on the host) and
+    qa_eval.predict_metrics (only the chosen chains decoded) both end here. qids: the questions in first-appearance order; acc: per
+    question, whether the chain with the top rank score is the gold one; top(k, lambda_, qid): the answer dict on top of question qid's
+    list after the sorts for lambdas[0 .. k], called once per (k, qid) in that order; gold = {qid: (gold_answer, sp_gold)}.
+    Returns (metrics dict, best_res)."""
+    logger.info(f"evaluated {len(qids)} questions...")
     logger.info(f"chain ranking em: {np.mean(acc)}")
     best_em, best_f1, best_joint_em, best_joint_f1, best_sp_em, best_sp_f1 = 0, 0, 0, 0, 0, 0
     best_res = None
-    lambdas = [fixed_thresh] if fixed_thresh else [0, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9, 1]
-    for lambda_ in lambdas:
+    for k, lambda_ in enumerate(lambdas):
         ems, f1s, sp_ems, sp_f1s, joint_ems, joint_f1s = [], [], [], [], [], []
         results = collections.defaultdict(dict)
-        for qid in id2result:
-            ans_res = id2answer[qid]
-            ans_res.sort(key=lambda x: lambda_ * x["rank_score"] + (1 - lambda_) * x["span_score"], reverse=True)
-            top_pred, top_sp = ans_res[0]["pred_str"], ans_res[0]["pred_sp"]
+        for qid in qids:
+            first = top(k, lambda_, qid)
+            top_pred, top_sp = first["pred_str"], first["pred_sp"]
             results["answer"][qid] = top_pred
             results["sp"][qid] = top_sp
             ems.append(exact_match_score(top_pred, gold[qid][0][0]))
@@ -395,18 +393,50 @@ def predict_metrics(chains, gold, sp_pred, logger, fixed_thresh=None):
     return {"em": best_em, "f1": best_f1, "joint_em": best_joint_em, "joint_f1": best_joint_f1, "sp_em": best_sp_em, "sp_f1": best_sp_f1}, best_res
 
 
+def predict_metrics(chains, gold, sp_pred, logger, fixed_thresh=None):
+    """predict()'s ranking / metrics / log lines over all chains ([(qid, label, answer dict)] in dataloader order) and
+    gold = {qid: (gold_answer, sp_gold)}. Returns (metrics dict, best_res). Each question's answer list is sorted IN PLACE once per
+    factor, as the reference sorts it: the sort for a factor starts from the order the factor before it left."""
+    id2result, id2answer = collections.defaultdict(list), collections.defaultdict(list)
+    for qid, label, ans in chains:
+        id2result[qid].append((label, ans["rank_score"]))
+        id2answer[qid].append(ans)
+    acc = []
+    for qid, res in id2result.items():
+        res.sort(key=lambda x: x[1], reverse=True)
+        acc.append(res[0][0] == 1)
+
+    def top(k, lambda_, qid):
+        ans_res = id2answer[qid]
+        ans_res.sort(key=lambda x: lambda_ * x["rank_score"] + (1 - lambda_) * x["span_score"], reverse=True)
+        return ans_res[0]
+
+    return metrics_report(list(id2result), acc, combination_factors(fixed_thresh), top, gold, sp_pred, logger)
+
+
+def final_report(qids, top):
+    """eval_final()'s result dict from the chosen answer dict top(qid) of every question, for final_results below and qa_eval.final_results."""
+    results = collections.defaultdict(dict)
+    for qid in qids:
+        first = top(qid)
+        results["answer"][qid] = first["pred_str"]
+        results["sp"][qid] = first["pred_sp"]
+        results["titles"][qid] = first["chain_titles"]
+    return results
+
+
 def final_results(chains, weight=0.8):
     """eval_final()'s selection: per question the chain with the best weight * rank + (1 - weight) * span; answer, sp and titles."""
     id2answer = collections.defaultdict(list)
     for qid, _, ans in chains:
         id2answer[qid].append(ans)
-    results = collections.defaultdict(dict)
-    for qid, ans_res in id2answer.items():
+
+    def top(qid):
+        ans_res = id2answer[qid]
         ans_res.sort(key=lambda x: weight * x["rank_score"] + (1 - weight) * x["span_score"], reverse=True)
-        results["answer"][qid] = ans_res[0]["pred_str"]
-        results["sp"][qid] = ans_res[0]["pred_sp"]
-        results["titles"][qid] = ans_res[0]["chain_titles"]
-    return results
+        return ans_res[0]
+
+    return final_report(list(id2answer), top)
 
 
 def add_sp_labels(raw_path, input_file, save_path, title2sent_map="data/hotpot_index/title2sents.txt"):

@@ -34,6 +34,16 @@ step. The pieces are built before the model goes to the device (this process hol
 min(16, --num_workers) forked workers, and cached beside the train file. It
 takes chains of exactly two passages; another length exits and names the default arena.
 
+--eval-arena (not a flag of the reference, off by default) runs --do_predict, --do_test and every evaluation inside --do_train from
+qa_eval.QAEvalPieces instead of QADataset + qa_collate: the predict file's questions and DISTINCT passages are tokenised once (cached beside
+the file as <predict file>.qa_eval_pieces.npz, built before the model goes to the device with min(16, --num_workers) forked workers), every
+batch -- the same consecutive --predict_batch_size chains -- is written on the device by mdr_reader_assemble, bit for bit qa_collate's rows,
+decode()'s outputs stay on the device in a score table, mdr_reader_select picks per question and combination factor the chain that predict()'s
+in-place sorts leave on top (the largest (key_k, ..., key_0), lowest index among equals: DESIGN.md §32), and only the distinct winners are
+decoded to strings. Log lines, metrics, --save-prediction bytes and checkpoint_best.pt decisions are the host path's. It exits with a message
+that begins "--eval-arena is not supported: " and names the host path for a chain that does not have exactly two passages, an _id on two
+lines of the file, or a tokenizer for which "yes" or "no" is not a single WordPiece.
+
 Whatever keeps --do_train from running exits with a message that begins "training is not supported: ": a --model_name that the trainable
 reader refuses (it is built for ELECTRA, from a local directory; the default bert-base-uncased is refused), no HIP device, a missing
 --train_file. The command line is checked for these before any file or device is opened.
@@ -92,6 +102,7 @@ def train_args(argv=None):
     p.add_argument("--warmup-ratio", default=0, type=float)
     p.add_argument("--sp-weight", default=0, type=float)
     p.add_argument("--piece-arena", action="store_true")  # not in the reference: the training feed's piece arena (module docstring)
+    p.add_argument("--eval-arena", action="store_true")  # not in the reference: evaluation from a dev piece arena (module docstring)
     return p.parse_args(argv)
 
 
@@ -108,6 +119,18 @@ def run_batches(model, loader, args, final):
         for idx, qid in enumerate(batch["qids"]):
             gold[qid] = (batch["gold_answer"][idx], batch["sp_gold"][idx])
     return chains, gold
+
+
+def eval_pieces_for(args, tokenizer, logger):
+    """--eval-arena: the predict file as pieces (qa_eval.QAEvalPieces), built or loaded BEFORE this process holds the device: its workers
+    are forked. Whatever the pieces do not take exits and names the host path."""
+    from multihop_dense_retrieval_amd import qa_eval
+    try:
+        return qa_eval.QAEvalPieces.load_or_build(args.predict_file, tokenizer, args.max_seq_len, args.max_q_len, args.predict_batch_size,
+                                                  log=logger.info, workers=min(16, args.num_workers))
+    except ValueError as e:
+        sys.exit(f"--eval-arena is not supported: {e} (run without --eval-arena: the host path, QADataset and qa_collate in this process, "
+                 "takes every predict file)")
 
 
 def check_train_inputs(args):
@@ -270,7 +293,7 @@ def start_training(args, config, tokenizer, device, logger):
     import numpy as np
     import torch
     from torch.utils.data import DataLoader
-    from multihop_dense_retrieval_amd import qa_data, qa_train_arena, qa_train_data, qa_train_pieces, reader_train
+    from multihop_dense_retrieval_amd import qa_data, qa_eval, qa_train_arena, qa_train_data, qa_train_pieces, reader_train
     if args.shared_norm:
         assert (args.train_batch_size // 1) == args.neg_num + 1  # chains of each question are on the same gpu (n_gpu = 1)
     # train_qa.py:78-80. Seeded HERE, after the imports and the config / tokenizer loading: importing transformers draws from the global
@@ -282,10 +305,15 @@ def start_training(args, config, tokenizer, device, logger):
         model = reader_train.TrainableReader(config, args)
     except NotImplementedError as e:
         sys.exit(f"training is not supported: {e}")
-    collate = partial(qa_data.qa_collate, pad_id=tokenizer.pad_token_id)
-    eval_dataset = qa_data.QADataset(tokenizer, args.predict_file, args.max_seq_len, args.max_q_len)
-    eval_loader = DataLoader(eval_dataset, batch_size=args.predict_batch_size, collate_fn=collate, num_workers=0)
-    logger.info(f"Num of dev batches: {len(eval_loader)}")
+    eval_pieces = eval_loader = None
+    if args.eval_arena:  # built HERE, as the training pieces below: before model.to(device), its workers are forked processes
+        eval_pieces = eval_pieces_for(args, tokenizer, logger)
+        logger.info(f"Num of dev batches: {len(eval_pieces.batches)}")
+    else:
+        collate = partial(qa_data.qa_collate, pad_id=tokenizer.pad_token_id)
+        eval_dataset = qa_data.QADataset(tokenizer, args.predict_file, args.max_seq_len, args.max_q_len)
+        eval_loader = DataLoader(eval_dataset, batch_size=args.predict_batch_size, collate_fn=collate, num_workers=0)
+        logger.info(f"Num of dev batches: {len(eval_loader)}")
     if args.init_checkpoint != "":
         logger.info(f"Loading model from {args.init_checkpoint}")
     model.load_state_dict(initial_state(args, config, model))
@@ -297,6 +325,8 @@ def start_training(args, config, tokenizer, device, logger):
         except ValueError as e:
             sys.exit(f"training is not supported: {e} (run without --piece-arena: the default item arena takes chains of any length)")
     model.to(device)
+    if eval_pieces is not None:
+        eval_pieces.to(device)
     print(f"number of trainable parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
     try:
         from torch.utils.tensorboard import SummaryWriter
@@ -310,6 +340,9 @@ def start_training(args, config, tokenizer, device, logger):
     arena = (pieces if pieces is not None else qa_train_arena.QATrainArena.load_or_build(args.train_file, train_dataset, tokenizer, log=logger.info)).to(device)
 
     def evaluate():
+        if eval_pieces is not None:
+            table = qa_eval.score_table(model.inference(), eval_pieces, args.max_ans_len)
+            return qa_eval.predict_metrics(eval_pieces, table, tokenizer, args.sp_pred, logger, fixed_thresh=None)[0]
         chains, gold = run_batches(model.inference(), eval_loader, args, final=False)
         return qa_data.predict_metrics(chains, gold, args.sp_pred, logger, fixed_thresh=None)[0]
 
@@ -324,7 +357,7 @@ def main(argv=None):
     import torch
     import transformers
     from torch.utils.data import DataLoader
-    from multihop_dense_retrieval_amd import qa_data, reader
+    from multihop_dense_retrieval_amd import qa_data, qa_eval, reader
     date_curr = date.today().strftime("%m-%d-%Y")
     model_name = (f"{args.prefix}-seed{args.seed}-bsz{args.train_batch_size}-fp16{args.fp16}-lr{args.learning_rate}-decay{args.weight_decay}"
                   f"-neg{args.neg_num}-sn{args.shared_norm}-adam{args.use_adam}-warm{args.warmup_ratio}-sp{args.sp_weight}")
@@ -346,24 +379,38 @@ def main(argv=None):
     if args.do_train:
         return start_training(args, config, tokenizer, device, logger)
     model = reader.QAModel(config, args)
-    collate = partial(qa_data.qa_collate, pad_id=tokenizer.pad_token_id)
-    dataset = qa_data.QADataset(tokenizer, args.predict_file, args.max_seq_len, args.max_q_len)
-    loader = DataLoader(dataset, batch_size=args.predict_batch_size, collate_fn=collate, num_workers=0)
-    logger.info(f"Num of dev batches: {len(loader)}")
+    pieces = loader = None
+    if args.eval_arena:  # before model.to(device): the workers that tokenise the passages are forked
+        pieces = eval_pieces_for(args, tokenizer, logger)
+        logger.info(f"Num of dev batches: {len(pieces.batches)}")
+    else:
+        collate = partial(qa_data.qa_collate, pad_id=tokenizer.pad_token_id)
+        dataset = qa_data.QADataset(tokenizer, args.predict_file, args.max_seq_len, args.max_q_len)
+        loader = DataLoader(dataset, batch_size=args.predict_batch_size, collate_fn=collate, num_workers=0)
+        logger.info(f"Num of dev batches: {len(loader)}")
     if args.init_checkpoint != "":
         logger.info(f"Loading model from {args.init_checkpoint}")
         reader.load_saved(model, args.init_checkpoint, exact=False, map_location="cpu")
     model.to(device).eval()
+    table = None
+    if pieces is not None and (args.do_predict or args.do_test):
+        table = qa_eval.score_table(model, pieces.to(device), args.max_ans_len)
     if args.do_predict:
-        chains, gold = run_batches(model, loader, args, final=False)
-        metrics, best_res = qa_data.predict_metrics(chains, gold, args.sp_pred, logger, fixed_thresh=0.8)
+        if pieces is not None:
+            metrics, best_res = qa_eval.predict_metrics(pieces, table, tokenizer, args.sp_pred, logger, fixed_thresh=0.8)
+        else:
+            chains, gold = run_batches(model, loader, args, final=False)
+            metrics, best_res = qa_data.predict_metrics(chains, gold, args.sp_pred, logger, fixed_thresh=0.8)
         if args.save_prediction != "":
             with open(args.save_prediction, "w") as f:
                 json.dump(best_res, f)
         logger.info(f"test performance {metrics}")
     elif args.do_test:
-        chains, _ = run_batches(model, loader, args, final=True)
-        results = qa_data.final_results(chains, weight=0.8)
+        if pieces is not None:
+            results = qa_eval.final_results(pieces, table, tokenizer, args.sp_pred, weight=0.8)
+        else:
+            chains, _ = run_batches(model, loader, args, final=True)
+            results = qa_data.final_results(chains, weight=0.8)
         if args.save_prediction != "":
             with open(args.save_prediction, "w") as f:
                 json.dump(results, f)
