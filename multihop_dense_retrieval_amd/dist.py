@@ -43,14 +43,16 @@ def slice_bounds(B, N):
     return [(edges[r], edges[r + 1]) for r in range(N)]
 
 
-def flat_layout(sizes, N):
+def flat_layout(sizes, N, align=1):
     """(offsets, S, padded): tensor i of `sizes` elements lies at offsets[i] of one flat buffer (the running sum: no gaps), S is the per-rank
-    segment, ceil(total / N) rounded up to a multiple of SEGMENT_MULTIPLE floats, and padded = N * S >= total is the buffer's length."""
-    sizes, N = [int(s) for s in sizes], int(N)
-    if N < 1 or not sizes or min(sizes) < 1:
-        raise ValueError("flat_layout: N >= 1 and at least one size, every size >= 1")
+    segment, ceil(total / N) rounded up to a multiple of SEGMENT_MULTIPLE floats, and padded = N * S >= total is the buffer's length.
+    align > 1: every offset is rounded up to a multiple of it (the reader's heads hold 1 and 2 elements); a gap is never written."""
+    sizes, N, align = [int(s) for s in sizes], int(N), int(align)
+    if N < 1 or align < 1 or not sizes or min(sizes) < 1:
+        raise ValueError("flat_layout: N >= 1, align >= 1 and at least one size, every size >= 1")
     offsets, total = [], 0
     for s in sizes:
+        total = -(-total // align) * align
         offsets.append(total)
         total += s
     S = -(-(-(-total // N)) // SEGMENT_MULTIPLE) * SEGMENT_MULTIPLE
@@ -263,6 +265,18 @@ def gather_with_grad(world, x_local, bounds):
     return _GatherWithGrad.apply(x_local, world, bounds)
 
 
+def scalar_rank_sum(world, value):
+    """The [1] fp32 tensor ((v_0 + v_1) + v_2) + ... of every rank's [1] fp32 device tensor `value`: the values are moved as bytes (one
+    gather_rows of a row of four floats per rank, the kernel's smallest stride) and added in rank order by mdr_rank_sum, so every rank holds
+    the same bits, dist.rank_sum_host's, whatever the transport. One collective; no library all-reduce."""
+    if not (torch.is_tensor(value) and value.is_cuda and value.dtype == torch.float32 and value.numel() == 1):
+        raise ValueError(f"value must be an fp32 tensor of one element on a HIP device (there is no CPU fallback), got {_lib.describe(value)}")
+    row = torch.zeros((1, 4), dtype=torch.float32, device=value.device)
+    row[0, :1].copy_(value.detach().reshape(1))
+    recv = world.gather_rows(row, slice_bounds(world.size, world.size)).contiguous()
+    return rank_sum(recv, torch.empty(4, dtype=torch.float32, device=value.device), n=1)[:1]
+
+
 # -- the gradient bucket -------------------------------------------------------------------------------------------------------------------
 class GradBucket:
     """One flat fp32 buffer behind every trainable parameter's .grad (flat_layout), allocated once and zeroed. The views are installed before
@@ -279,9 +293,9 @@ class GradBucket:
             raise RuntimeError("GradBucket: every trainable parameter must be an fp32 tensor on one HIP device (there is no CPU fallback)")
         if not 1 <= world.size <= MAX_RANKS:
             raise ValueError(f"GradBucket: {world.size} ranks, the ordered sum is built for 1 .. {MAX_RANKS}")
-        self.offsets, self.segment, padded = flat_layout([p.numel() for p in self.params], world.size)
-        if any(off % 4 for off in self.offsets):  # mdr_optim_step reads 16-byte aligned gradients; every tensor of the encoder is a multiple of 64
-            raise ValueError("GradBucket: every parameter but the last must hold a multiple of 4 elements (the views are read 16 bytes at a time)")
+        # mdr_optim_step reads 16-byte aligned gradients. Every tensor of the encoder is a multiple of 64, so the retriever's layout has no gap;
+        # the reader's qa_outputs.bias, rank.bias and sp.bias are followed by one (zero for ever, summed like everything else)
+        self.offsets, self.segment, padded = flat_layout([p.numel() for p in self.params], world.size, align=4)
         self.total = self.offsets[-1] + self.params[-1].numel()
         self.flat = torch.zeros(padded, dtype=torch.float32, device=dev)
         self.mine = torch.empty(self.segment, dtype=torch.float32, device=dev)

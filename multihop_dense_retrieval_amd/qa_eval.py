@@ -388,14 +388,59 @@ class ScoreTable:
         return self.batch_sents[int(np.searchsorted(np.asarray(self.batch_lo), i, side="right")) - 1]
 
 
-def score_table(model, pieces, max_ans_len):
-    """The arena sweep: every batch assembled on the device, decoded, its outputs kept in a ScoreTable."""
+def batch_deal(n_batches, N):
+    """[(first, behind)] * N: the contiguous run of whole batches each of N ranks decodes (dist.slice_bounds over the batches: balanced,
+    in rank order, empty only when there are fewer batches than ranks). Batches are dealt, never rows: a batch stays the host path's, so the
+    forward's kernel choice, and with it every bit, is the one-rank run's."""
+    from .dist import slice_bounds
+    return slice_bounds(n_batches, N)
+
+
+def merge_tables(local, batches, world):
+    """The complete ScoreTable from the ranks' partial ones. `local`: this rank's table of all n rows, of which it filled the
+    batches batch_deal(len(batches), N)[rank]; `batches`: every (lo, hi) in order. The ranks' row ranges are contiguous and in rank order, so
+    the merge is a concatenation: one gather_objects (each rank's batch_lo, batch_sents and whether it keeps sp_prob) and one gather_rows of
+    [rows, 4 + max_sents] fp32 -- the int16 patterns as integers, positions up to 512 and fp16 probabilities are all exact there. The result
+    is a fresh table filled by put() batch by batch in file order, as one rank fills it: nothing but a batch's own rows and its first S_b
+    sp_prob columns is taken from anybody, and batch_lo and batch_sents come out as put() writes them."""
+    deal = batch_deal(len(batches), world.size)
+    edges = [lo for lo, _ in batches] + [local.n]
+    bounds = [(edges[a], edges[b]) for a, b in deal]
+    a, b = deal[world.rank]
+    if list(local.batch_lo) != [lo for lo, _ in batches[a:b]]:
+        raise ValueError(f"rank {world.rank} of {world.size} decodes batches {a} .. {b} and its table holds the batches at rows {local.batch_lo}")
+    told = world.gather_objects((list(local.batch_lo), list(local.batch_sents), local.sp_prob is not None))
+    batch_lo, batch_sents = [x for t in told for x in t[0]], [x for t in told for x in t[1]]
+    has_sp = any(t[2] for t in told)
+    if batch_lo != edges[:-1]:
+        raise ValueError("the ranks' batches do not add up to the file's: they do not evaluate the same pieces")
+    lo, hi = bounds[world.rank]
+    cols = [local.rank16[lo:hi].float(), local.span16[lo:hi].float(), local.start[lo:hi].float(), local.end[lo:hi].float()]
+    mine = torch.stack(cols, 1) if hi > lo else torch.zeros((0, 4), dtype=torch.float32, device=local.device)
+    if has_sp and local.max_sents:
+        sp = local.sp_prob[lo:hi].float() if local.sp_prob is not None else torch.zeros((hi - lo, local.max_sents), dtype=torch.float32, device=local.device)
+        mine = torch.cat([mine, sp], 1)
+    full = world.gather_rows(mine.contiguous(), bounds)
+    merged = ScoreTable(local.n, local.max_sents, local.device)
+    for (b_lo, b_hi), s_b in zip(batches, batch_sents):
+        head = {"rank_score": full[b_lo:b_hi, 0].to(torch.int16).view(torch.float16), "span_score": full[b_lo:b_hi, 1].to(torch.int16).view(torch.float16),
+                "start": full[b_lo:b_hi, 2].to(torch.int64), "end": full[b_lo:b_hi, 3].to(torch.int64)}
+        if has_sp:
+            head["sp_prob"] = full[b_lo:b_hi, 4:4 + s_b].to(torch.float16)
+        merged.put(b_lo, head)
+    return merged
+
+
+def score_table(model, pieces, max_ans_len, world=None):
+    """The arena sweep: every batch assembled on the device, decoded, its outputs kept in a ScoreTable. world (a dist.TorchWorld or a rank of
+    dist.LoopbackWorld): this rank decodes its run of batches (batch_deal) and merge_tables hands every rank the complete table."""
     table = ScoreTable(pieces.n, pieces.max_sents, pieces.dev["chains"].device)
-    for lo, hi in pieces.batches:
+    first, behind = (0, len(pieces.batches)) if world is None else batch_deal(len(pieces.batches), world.size)[world.rank]
+    for lo, hi in pieces.batches[first:behind]:
         rows = pieces.assemble(lo, hi)
         table.put(lo, model.decode({k: rows[k] for k in ("input_ids", "attention_mask", "token_type_ids", "paragraph_mask", "sent_offsets", "label")},
                                    max_ans_len))
-    return table
+    return table if world is None else merge_tables(table, pieces.batches, world)
 
 
 # ---- evaluation on the winners -----------------------------------------------------------------------------------------------------------

@@ -183,14 +183,56 @@ def optimizer_for(model, args, loss_scale="dynamic"):
                            fp16_copies=[P[n] for n in fp16_copy_names(list(P))], decoupled_weight_decay=not getattr(args, "use_adam", False))
 
 
-def train_step(model, batch, args, opt, seed):
+RANK_ROWS = "_rank_rows"  # a batch that holds one rank's rows alone says so here: (lo, hi, B), widths of the full batch (train.RANK_ROWS)
+
+
+def rank_rows(batch, world):
+    """(this rank's rows of `batch`, lo, hi): rows dist.slice_bounds(B, N)[rank] of the full batch's tensors, the widths untouched, so a
+    row's input does not depend on the rank count. A batch that carries RANK_ROWS holds those rows already (scripts/train_qa.py's feed);
+    its tensors may be missing altogether when the slice is empty."""
+    from . import dist
+    if RANK_ROWS in batch:
+        lo, hi, B = batch[RANK_ROWS]
+        local = {k: v for k, v in batch.items() if k != RANK_ROWS}
+    else:
+        B = int(batch["input_ids"].shape[0])
+        lo, hi = dist.slice_bounds(B, world.size)[world.rank]
+        local = {k: v[lo:hi] if torch.is_tensor(v) and v.dim() and v.shape[0] == B else v for k, v in batch.items()}
+    if (lo, hi) != dist.slice_bounds(B, world.size)[world.rank]:
+        raise ValueError(f"the batch holds rows {lo} .. {hi} of {B}, rank {world.rank} of {world.size} owns {dist.slice_bounds(B, world.size)[world.rank]}")
+    return local, lo, hi
+
+
+def train_step(model, batch, args, opt, seed, world=None, bucket=None):
     """One forward and backward of the reader's loss: model(batch, seed, opt.half), divided by gradient_accumulation_steps, scaled by the
     optimizer's loss scale for the backward. Returns the unscaled loss (a [1] device tensor). The caller owns opt.step() and
-    scheduler.step(); FusedAdam zeroes the gradients in place, so zero_grad() is never called."""
+    scheduler.step(); FusedAdam zeroes the gradients in place, so zero_grad() is never called.
+
+    world (a dist.TorchWorld or a rank of dist.LoopbackWorld) and bucket (the dist.GradBucket behind the parameters' gradients): the step of
+    one rank of several. The reference's loss is a plain sum over the rows, so the full batch's loss is the sum of the
+    ranks' partial losses and nothing is gathered before it: the rank forwards its rows (rank_rows) under dist.rank_seed(seed, rank) and
+    backpropagates its partial loss; the caller runs bucket.reduce() at the accumulation boundary, immediately before opt.step(). A rank
+    without rows makes no forward and no backward and contributes +0.0 and an all-zero bucket. Every rank returns the same bits: the
+    partial losses (each already divided by gradient_accumulation_steps) added in rank order by dist.scalar_rank_sum. No division by the
+    rank count: N ranks train what one rank trains."""
     if not model.training:
         raise RuntimeError("train_step needs the model in train() mode")
-    loss = model(batch, seed=seed, half=opt.half)
-    if args.gradient_accumulation_steps > 1:
-        loss = loss / args.gradient_accumulation_steps
-    opt.scale_loss(loss).backward()
-    return loss.detach()
+    if world is None:
+        loss = model(batch, seed=seed, half=opt.half)
+        if args.gradient_accumulation_steps > 1:
+            loss = loss / args.gradient_accumulation_steps
+        opt.scale_loss(loss).backward()
+        return loss.detach()
+    from . import dist
+    if bucket is None or bucket.world is not world:
+        raise ValueError("a step on several ranks needs the dist.GradBucket of this world behind the gradients")
+    local, lo, hi = rank_rows(batch, world)
+    if hi > lo:
+        loss = model(local, seed=dist.rank_seed(seed, world.rank), half=opt.half)
+        if args.gradient_accumulation_steps > 1:
+            loss = loss / args.gradient_accumulation_steps
+        opt.scale_loss(loss).backward()
+        part = loss.detach()
+    else:
+        part = torch.zeros(1, dtype=torch.float32, device=bucket.flat.device)
+    return dist.scalar_rank_sum(world, part)

@@ -7,7 +7,7 @@
         --max_q_len 64 --gradient_accumulation_steps 8 --neg-num 5 --sp-pred --sp-weight 0.05 --warmup-ratio 0.1 --num_train_epochs 7
 
 Flags are the reference's (mdr/qa/config.py), parsed verbatim. --do_predict runs predict() with the fixed 0.8 combination factor and
-writes its log lines and --save-prediction; --do_test runs eval_final(). One rank; the dev batches are the reference's (sequential,
+writes its log lines and --save-prediction; --do_test runs eval_final(). The dev batches are the reference's (sequential,
 --predict_batch_size chains) and are loaded in this process (num_workers is accepted and not used: the forward is on the device and data
 workers would fork a process that holds it). Numerics are apex O1's whether or not --fp16 is given (the README's QA command passes it). The
 config and the tokenizer come from --model_name, a local directory or a model in the local cache; nothing is downloaded.
@@ -44,9 +44,31 @@ decoded to strings. Log lines, metrics, --save-prediction bytes and checkpoint_b
 that begins "--eval-arena is not supported: " and names the host path for a chain that does not have exactly two passages, an _id on two
 lines of the file, or a tokenizer for which "yes" or "no" is not a single WordPiece.
 
+Several ranks: `torchrun --nproc-per-node N scripts/train_qa.py --do_train ...`. The rank comes from --local_rank (the
+reference's flag) or from LOCAL_RANK, RANK and WORLD_SIZE; with neither, or with a world of one rank, everything above holds unchanged, bit
+for bit. N ranks train what one rank trains: every rank makes the same host draws and computes the full batch's widths, assembles and
+forwards rows dist.slice_bounds(B, N)[rank] of it under dist.rank_seed(seed, rank) and backpropagates its partial loss -- the reference's
+loss is a plain sum over the rows, so nothing is gathered before it --, the gradients are summed over the ranks in rank order by
+mdr_rank_sum (dist.GradBucket) before every optimizer step, and the logged loss is the partial losses added in rank order the same way. A
+DEVIATION from the reference: under DataParallel it takes loss.mean() over the replicas' sums and chunks the batch by ceil(B / N); here
+there is no division by N and the slices are balanced, because the README's reader recipe runs on one device and that objective is the
+published one. MhopSampler's n_gpu = 8 stays what it is: a property of the sampler, not of the launch. With --eval-arena every evaluation
+(and --do_predict, --do_test) is split: rank r decodes a contiguous run of whole dev batches (qa_eval.batch_deal), the score tables' rows are
+exchanged as bytes, and every rank selects, decodes the winners, computes the metrics and takes the same checkpoint_best.pt decision;
+without it every rank evaluates the whole dev set by the host path and rank 0 logs a line that says so. --dist-backend nccl (RCCL, the
+default) or gloo; --share-gpu puts every rank on device 0 (gloo only: a rehearsal on one card); --dist-timeout SECONDS goes to
+init_process_group; --check-ranks compares a checksum of the parameters' bits over the ranks behind every evaluation and at the end
+(`ranks agree: <hex>`): the meanings, defaults and code of scripts/train_mhop.py. Rank 0 alone makes the output directory and writes
+log.txt, TensorBoard, the checkpoints and the log lines. The process group is joined before anything opens the device: rank 0 builds and
+writes the caches (their workers are forked) while the others wait at a gloo barrier and then load them. Before the first step the ranks
+compare a digest of the arena's and the dev pieces' tags, the item count, --seed, --train_batch_size, --gradient_accumulation_steps,
+--neg-num and the world size.
+
 Whatever keeps --do_train from running exits with a message that begins "training is not supported: ": a --model_name that the trainable
 reader refuses (it is built for ELECTRA, from a local directory; the default bert-base-uncased is refused), no HIP device, a missing
---train_file. The command line is checked for these before any file or device is opened.
+--train_file, more than dist.MAX_RANKS ranks, --share-gpu without gloo or without a launcher, more ranks than visible devices without
+--share-gpu, a launcher without MASTER_ADDR / MASTER_PORT. The command line and the launcher's environment are checked for these before any
+file or device is opened.
 """
 import argparse
 import logging
@@ -58,6 +80,8 @@ from functools import partial
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+if os.path.join(ROOT, "scripts") not in sys.path:  # (train_mhop.py's launch plumbing, for a caller that loads this file from elsewhere)
+    sys.path.append(os.path.join(ROOT, "scripts"))
 
 
 def train_args(argv=None):
@@ -103,7 +127,51 @@ def train_args(argv=None):
     p.add_argument("--sp-weight", default=0, type=float)
     p.add_argument("--piece-arena", action="store_true")  # not in the reference: the training feed's piece arena (module docstring)
     p.add_argument("--eval-arena", action="store_true")  # not in the reference: evaluation from a dev piece arena (module docstring)
+    # several ranks (module docstring), not in the reference: the meanings and defaults of scripts/train_mhop.py
+    p.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl")  # "nccl" is RCCL
+    p.add_argument("--share-gpu", action="store_true")  # every rank on device 0, gloo only: the rehearsal on one card
+    p.add_argument("--dist-timeout", type=int, default=1800)  # seconds, init_process_group's
+    p.add_argument("--check-ranks", action="store_true")  # compare the parameters' checksum over the ranks at every evaluation
     return p.parse_args(argv)
+
+
+def launch(args, environ=None):
+    """(rank, world size, local rank) of this process: scripts/train_mhop.py's rank_setup, whose refusals exit here, under --do_train with
+    the prefix every refusal of training carries. (0, 1, -1) without --local_rank and without a launcher: the one-rank run."""
+    import train_mhop
+    try:
+        return train_mhop.rank_setup(args, environ)
+    except SystemExit as e:
+        if args.do_train and isinstance(e.code, str):
+            sys.exit("training is not supported: " + e.code.replace("scripts/train_mhop.py", "scripts/train_qa.py"))
+        raise
+
+
+class Ranks:
+    """What the script needs of a launch of several ranks: the dist.TorchWorld of scripts/train_mhop.py's join_world and a gloo group of its
+    own, whose barrier touches no device (the pieces' workers are forked before this process opens one)."""
+
+    def __init__(self, args, rank, size):
+        from datetime import timedelta
+        import torch.distributed
+        import train_mhop
+        self.rank, self.size = rank, size
+        self.world = train_mhop.join_world(args, size)
+        self.host = torch.distributed.new_group(backend="gloo", timeout=timedelta(seconds=args.dist_timeout))
+
+    def rank_zero_first(self, fn):
+        """fn() on rank 0, then on the others: rank 0 builds and writes a cache, the others wait at the barrier and load it."""
+        import torch.distributed
+        if self.rank == 0:
+            out = fn()
+            torch.distributed.barrier(group=self.host)
+            return out
+        torch.distributed.barrier(group=self.host)
+        return fn()
+
+    def close(self):
+        import torch.distributed
+        torch.distributed.destroy_process_group()
 
 
 def run_batches(model, loader, args, final):
@@ -133,15 +201,15 @@ def eval_pieces_for(args, tokenizer, logger):
                  "takes every predict file)")
 
 
-def check_train_inputs(args):
-    """What --do_train needs, read from the command line alone, before any file or device is opened: every refusal begins alike."""
+def check_train_inputs(args, environ=None):
+    """What --do_train needs, read from the command line and the launcher's environment alone, before any file or device is opened: every
+    refusal begins alike. Returns launch()'s (rank, world size, local rank)."""
     no = "training is not supported: "
     name = args.model_name
     if "electra" not in name.lower() or not os.path.isdir(name):
         sys.exit(f"{no}--model_name {name!r} is not a local ELECTRA directory (the trainable reader is built for ELECTRA, QAModel's own pooler; "
                  "the config, the tokenizer and the weights come from that directory and nothing is downloaded)")
-    if args.local_rank != -1:
-        sys.exit(f"{no}multi-rank training is not built: run one rank (--local_rank -1)")
+    ranks = launch(args, environ)
     import torch
     if args.no_cuda or not torch.cuda.is_available():
         sys.exit(f"{no}no HIP device is visible (the reader trains on a HIP device only; there is no CPU fallback)")
@@ -152,6 +220,7 @@ def check_train_inputs(args):
         sys.exit(f"{no}--init_checkpoint {args.init_checkpoint!r}: no such file")
     if args.gradient_accumulation_steps < 1 or args.train_batch_size < 1:
         sys.exit(f"{no}--gradient_accumulation_steps and --train_batch_size must be at least 1")
+    return ranks
 
 
 class AverageMeter:
@@ -167,18 +236,30 @@ class AverageMeter:
         self.avg = self.sum / self.count
 
 
-def arena_batches(arena, pad_id, device):
+def arena_batches(arena, pad_id, device, world=None):
     """The product's feed: one epoch's indices go to the device once; every batch is mdr_reader_train_assemble on a slice of them, its
-    widths from the arena's host metadata (no synchronisation)."""
+    widths from the arena's host metadata (no synchronisation). world (a dist.TorchWorld or a rank of dist.LoopbackWorld): every rank is
+    handed the same indices and computes the full batch's widths, and assembles rows dist.slice_bounds(B, N)[rank] of it alone, which the
+    batch says under reader_train.RANK_ROWS; a rank without rows makes no call and yields that entry alone."""
     import torch
-    from multihop_dense_retrieval_amd import qa_train_arena
+    from multihop_dense_retrieval_amd import dist as mdr_dist, qa_train_arena, reader_train
 
     def feed(indices, batch_size):
         on_dev = torch.tensor(indices, dtype=torch.int64, device=device)
         for lo in range(0, len(indices), batch_size):
             out_len, n_sent, n_span = arena.batch_shape(indices[lo:lo + batch_size])
-            out = arena.assemble(on_dev[lo:lo + batch_size], out_len, n_sent, n_span, pad_id)
-            yield {k: out[k] for k in qa_train_arena.NET_KEYS}
+            if world is None:
+                out = arena.assemble(on_dev[lo:lo + batch_size], out_len, n_sent, n_span, pad_id)
+                yield {k: out[k] for k in qa_train_arena.NET_KEYS}
+                continue
+            B = len(indices[lo:lo + batch_size])
+            first, behind = mdr_dist.slice_bounds(B, world.size)[world.rank]
+            net = {}
+            if behind > first:
+                out = arena.assemble(on_dev[lo + first:lo + behind], out_len, n_sent, n_span, pad_id)
+                net = {k: out[k] for k in qa_train_arena.NET_KEYS}
+            net[reader_train.RANK_ROWS] = (first, behind, B)
+            yield net
     return feed
 
 
@@ -195,15 +276,21 @@ def host_batches(dataset, pad_id, device):
     return feed
 
 
-def train(args, model, sampler, feed, evaluate, logger, tb_logger=None, loss_scale="dynamic"):
+def train(args, model, sampler, feed, evaluate, logger, tb_logger=None, loss_scale="dynamic", world=None):
     """train_qa.py:138-211. sampler: qa_train_data.MhopSampler; feed(indices, batch_size) yields the net_inputs of one epoch's batches;
     evaluate() returns predict()'s metrics on the current weights; loss_scale: reader_train.optimizer_for's (the script runs the dynamic one).
     Returns {"loss": every batch's, "epoch_means", "global_step", "skipped_steps": the
-    optimizer steps the dynamic loss scale skipped while it came down from 2^16, as apex skips them (the schedule advances all the same)}."""
+    optimizer steps the dynamic loss scale skipped while it came down from 2^16, as apex skips them (the schedule advances all the same)}.
+    world: None, or this rank's dist.TorchWorld (or a rank of dist.LoopbackWorld) -- `feed` then yields this rank's rows
+    (arena_batches(..., world)), the gradients live in a dist.GradBucket that is reduced before every optimizer step, rank 0 alone saves,
+    --check-ranks compares the parameters' checksum behind every evaluation and at the end, and `logger` and `tb_logger` are the caller's
+    to silence on the other ranks."""
     import torch
-    from multihop_dense_retrieval_amd import optim, qa_train_data, reader_train
+    from multihop_dense_retrieval_amd import dist as mdr_dist, optim, qa_train_data, reader_train
     from multihop_dense_retrieval_amd import train as mdr_train
     optimizer = reader_train.optimizer_for(model, args, loss_scale=loss_scale)
+    bucket = mdr_dist.GradBucket(model.parameters(), world) if world is not None else None
+    multi = {"world": world, "bucket": bucket} if world is not None else {}
     global_step, batch_step, best_em = 0, 0, 0  # gradient update step; forward batch count
     train_loss_meter = AverageMeter()
     model.train()
@@ -214,18 +301,29 @@ def train(args, model, sampler, feed, evaluate, logger, tb_logger=None, loss_sca
     state, losses, epoch_means = {"loss": None}, [], []
 
     def save(name):
-        if not args.output_dir:  # (in-process callers that want no files)
+        if not args.output_dir or (world is not None and world.rank != 0):  # (in-process callers that want no files)
             return
         torch.save({k: v.detach().float().cpu() for k, v in model.state_dict().items()}, os.path.join(args.output_dir, name))
 
+    def check_ranks():
+        if world is not None and getattr(args, "check_ranks", False):
+            import train_mhop
+            checksum = train_mhop.parameter_checksum(model)
+            differ = train_mhop.ranks_agree(world, "the parameters' checksum", checksum)
+            if differ:
+                sys.exit(differ)
+            logger.info("ranks agree: %s", checksum)
+
     def step_fn(batch, _batch_step):
         seed = int(torch.randint(0, 2 ** 62, (1,), generator=seeds))
-        state["loss"] = reader_train.train_step(model, batch, args, optimizer, seed)
+        state["loss"] = reader_train.train_step(model, batch, args, optimizer, seed, **multi)
         losses.append(state["loss"].item())
         train_loss_meter.update(losses[-1])
 
     def update_fn(_batch_step):
         nonlocal global_step, best_em
+        if bucket is not None:
+            bucket.reduce()  # every rank's gradients become the ordered sum over the ranks: the one communication of an update
         optimizer.step()
         scheduler.step()
         global_step += 1
@@ -235,6 +333,7 @@ def train(args, model, sampler, feed, evaluate, logger, tb_logger=None, loss_sca
         if args.eval_period != -1 and global_step % args.eval_period == 0:
             em = evaluate()["em"]
             model.train()
+            check_ranks()
             logger.info("Step %d Train loss %.2f em %.2f on epoch=%d" % (global_step, train_loss_meter.avg, em * 100, epoch))
             if best_em < em:
                 logger.info("Saving model with best em %.2f -> em %.2f on step=%d" % (best_em * 100, em * 100, global_step))
@@ -249,6 +348,7 @@ def train(args, model, sampler, feed, evaluate, logger, tb_logger=None, loss_sca
         epoch_means.append(sum(losses[first:]) / max(1, len(losses) - first))
         em = evaluate()["em"]
         model.train()
+        check_ranks()
         logger.info("Step %d Train loss %.2f em %.2f" % (global_step, train_loss_meter.avg, em * 100))
         if tb_logger is not None:
             tb_logger.add_scalar("dev_em", em * 100, global_step)
@@ -257,6 +357,7 @@ def train(args, model, sampler, feed, evaluate, logger, tb_logger=None, loss_sca
             save("checkpoint_best.pt")
             best_em = em
     save("checkpoint_last.pt")  # not in the reference (module docstring)
+    check_ranks()
     logger.info("Training finished!")
     return {"loss": losses, "epoch_means": epoch_means, "global_step": global_step, "skipped_steps": optimizer.read_state()["skipped_total"]}
 
@@ -288,7 +389,10 @@ def initial_state(args, config, model):
     return start
 
 
-def start_training(args, config, tokenizer, device, logger):
+def start_training(args, config, tokenizer, device, logger, ranks=None):
+    """ranks: None, or the Ranks of a launch of several (module docstring). Whatever writes a cache runs on rank 0 first; the process group
+    was joined before this point and the device is selected only behind the forked workers."""
+    import hashlib
     import random
     import numpy as np
     import torch
@@ -306,14 +410,18 @@ def start_training(args, config, tokenizer, device, logger):
     except NotImplementedError as e:
         sys.exit(f"training is not supported: {e}")
     eval_pieces = eval_loader = None
+    world = ranks.world if ranks is not None else None
+    first = ranks.rank_zero_first if ranks is not None else (lambda fn: fn())
     if args.eval_arena:  # built HERE, as the training pieces below: before model.to(device), its workers are forked processes
-        eval_pieces = eval_pieces_for(args, tokenizer, logger)
+        eval_pieces = first(lambda: eval_pieces_for(args, tokenizer, logger))
         logger.info(f"Num of dev batches: {len(eval_pieces.batches)}")
     else:
         collate = partial(qa_data.qa_collate, pad_id=tokenizer.pad_token_id)
         eval_dataset = qa_data.QADataset(tokenizer, args.predict_file, args.max_seq_len, args.max_q_len)
         eval_loader = DataLoader(eval_dataset, batch_size=args.predict_batch_size, collate_fn=collate, num_workers=0)
         logger.info(f"Num of dev batches: {len(eval_loader)}")
+        if world is not None:
+            logger.info(f"every one of the {world.size} ranks evaluates the whole dev set by the host path: --eval-arena splits its batches over the ranks")
     if args.init_checkpoint != "":
         logger.info(f"Loading model from {args.init_checkpoint}")
     model.load_state_dict(initial_state(args, config, model))
@@ -321,38 +429,54 @@ def start_training(args, config, tokenizer, device, logger):
     if args.piece_arena:  # built HERE, before model.to(device) makes this process hold the device: its workers are forked processes
         train_dataset = qa_train_data.QATrainDataset(tokenizer, args.train_file, args.max_seq_len, args.max_q_len)
         try:
-            pieces = qa_train_pieces.QATrainPieces.load_or_build(args.train_file, train_dataset, tokenizer, log=logger.info, workers=min(16, args.num_workers))
+            pieces = first(lambda: qa_train_pieces.QATrainPieces.load_or_build(args.train_file, train_dataset, tokenizer, log=logger.info,
+                                                                               workers=min(16, args.num_workers)))
         except ValueError as e:
             sys.exit(f"training is not supported: {e} (run without --piece-arena: the default item arena takes chains of any length)")
+    if ranks is not None:
+        torch.cuda.set_device(device)  # (the collectives of a device backend run on the current device)
     model.to(device)
     if eval_pieces is not None:
         eval_pieces.to(device)
     print(f"number of trainable parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
-    try:
-        from torch.utils.tensorboard import SummaryWriter
-        tb_logger = SummaryWriter(os.path.join(args.output_dir.replace("logs", "tflogs")))
-    except ImportError:
-        tb_logger = None
-        logger.info("TensorBoard is not installed: its scalars are not written")
+    tb_logger = None
+    if ranks is None or ranks.rank == 0:
+        try:
+            from torch.utils.tensorboard import SummaryWriter
+            tb_logger = SummaryWriter(os.path.join(args.output_dir.replace("logs", "tflogs")))
+        except ImportError:
+            logger.info("TensorBoard is not installed: its scalars are not written")
     if pieces is None:
         train_dataset = qa_train_data.QATrainDataset(tokenizer, args.train_file, args.max_seq_len, args.max_q_len)
     sampler = qa_train_data.MhopSampler(train_dataset, num_neg=args.neg_num)
-    arena = (pieces if pieces is not None else qa_train_arena.QATrainArena.load_or_build(args.train_file, train_dataset, tokenizer, log=logger.info)).to(device)
+    arena = (pieces if pieces is not None else
+             first(lambda: qa_train_arena.QATrainArena.load_or_build(args.train_file, train_dataset, tokenizer, log=logger.info))).to(device)
+    if world is not None:  # before the first step: ranks that would train on different data or settings stop here, with a message
+        import train_mhop
+        tags = ((qa_train_pieces.train_pieces_tag if pieces is not None else qa_train_arena.train_arena_tag)(tokenizer, args.max_seq_len, args.max_q_len, args.train_file),
+                qa_eval.eval_pieces_tag(tokenizer, args.max_q_len, args.predict_file) if eval_pieces is not None else f"host|{os.stat(args.predict_file).st_size}")
+        told = (f"{tags[0]}|{tags[1]}|{len(train_dataset)}|{args.seed}|{args.train_batch_size}|{args.gradient_accumulation_steps}|{args.neg_num}|"
+                f"{world.size}")
+        differ = train_mhop.ranks_agree(world, "arena tag, dev pieces' tag, item count, seed, batch size, accumulation steps, negatives or world size",
+                                        hashlib.sha256(told.encode()).hexdigest())
+        if differ:
+            sys.exit(differ)
 
     def evaluate():
         if eval_pieces is not None:
-            table = qa_eval.score_table(model.inference(), eval_pieces, args.max_ans_len)
+            table = qa_eval.score_table(model.inference(), eval_pieces, args.max_ans_len, **({"world": world} if world is not None else {}))
             return qa_eval.predict_metrics(eval_pieces, table, tokenizer, args.sp_pred, logger, fixed_thresh=None)[0]
         chains, gold = run_batches(model.inference(), eval_loader, args, final=False)
         return qa_data.predict_metrics(chains, gold, args.sp_pred, logger, fixed_thresh=None)[0]
 
-    return train(args, model, sampler, arena_batches(arena, tokenizer.pad_token_id, device), evaluate, logger, tb_logger)
+    if world is None:
+        return train(args, model, sampler, arena_batches(arena, tokenizer.pad_token_id, device), evaluate, logger, tb_logger)
+    return train(args, model, sampler, arena_batches(arena, tokenizer.pad_token_id, device, world), evaluate, logger, tb_logger, world=world)
 
 
 def main(argv=None):
     args = train_args(argv)
-    if args.do_train:
-        check_train_inputs(args)
+    rank, world_size, local_rank = check_train_inputs(args) if args.do_train else launch(args)
     import json
     import torch
     import transformers
@@ -362,46 +486,58 @@ def main(argv=None):
     model_name = (f"{args.prefix}-seed{args.seed}-bsz{args.train_batch_size}-fp16{args.fp16}-lr{args.learning_rate}-decay{args.weight_decay}"
                   f"-neg{args.neg_num}-sn{args.shared_norm}-adam{args.use_adam}-warm{args.warmup_ratio}-sp{args.sp_weight}")
     args.output_dir = os.path.join(args.output_dir, date_curr, model_name)
-    if args.do_train and os.path.exists(args.output_dir) and os.listdir(args.output_dir):
-        print(f"output directory {args.output_dir} already exists and is not empty.")
-    os.makedirs(args.output_dir, exist_ok=True)
-    logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S", level=logging.INFO,
-                        handlers=[logging.FileHandler(os.path.join(args.output_dir, "log.txt")), logging.StreamHandler()])
+    handlers = [logging.NullHandler()]  # rank 0 alone makes the output directory and writes log.txt and the log lines
+    if rank == 0:
+        if args.do_train and os.path.exists(args.output_dir) and os.listdir(args.output_dir):
+            print(f"output directory {args.output_dir} already exists and is not empty.")
+        os.makedirs(args.output_dir, exist_ok=True)
+        handlers = [logging.FileHandler(os.path.join(args.output_dir, "log.txt")), logging.StreamHandler()]
+    logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S", level=logging.INFO, handlers=handlers)
     logger = logging.getLogger(__name__)
     logger.setLevel(logging.INFO)
     logger.info(args)
     if args.no_cuda or not torch.cuda.is_available():
         sys.exit("the reader runs on a HIP device only (there is no CPU fallback)")
-    device = torch.device("cuda", 0)
-    logger.info("device %s n_gpu %d distributed training %r", device, 1, False)
+    device = torch.device("cuda", 0 if args.share_gpu else max(local_rank, 0))
+    # the process group is joined HERE, before anything opens the device: the pieces' workers are forked, and the ranks meet at a gloo barrier
+    ranks = Ranks(args, rank, world_size) if world_size > 1 else None
+    logger.info("device %s n_gpu %d distributed training %r", device, 1, ranks is not None)
     config = transformers.AutoConfig.from_pretrained(args.model_name, local_files_only=True)
     tokenizer = transformers.BertTokenizer.from_pretrained(args.model_name, local_files_only=True)
     if args.do_train:
-        return start_training(args, config, tokenizer, device, logger)
+        out = start_training(args, config, tokenizer, device, logger, ranks)
+        if ranks is not None:
+            ranks.close()
+        return out
     model = reader.QAModel(config, args)
     pieces = loader = None
+    world = ranks.world if ranks is not None else None
     if args.eval_arena:  # before model.to(device): the workers that tokenise the passages are forked
-        pieces = eval_pieces_for(args, tokenizer, logger)
+        pieces = ranks.rank_zero_first(lambda: eval_pieces_for(args, tokenizer, logger)) if ranks is not None else eval_pieces_for(args, tokenizer, logger)
         logger.info(f"Num of dev batches: {len(pieces.batches)}")
     else:
         collate = partial(qa_data.qa_collate, pad_id=tokenizer.pad_token_id)
         dataset = qa_data.QADataset(tokenizer, args.predict_file, args.max_seq_len, args.max_q_len)
         loader = DataLoader(dataset, batch_size=args.predict_batch_size, collate_fn=collate, num_workers=0)
         logger.info(f"Num of dev batches: {len(loader)}")
+        if world is not None:
+            logger.info(f"every one of the {world.size} ranks evaluates the whole dev set by the host path: --eval-arena splits its batches over the ranks")
     if args.init_checkpoint != "":
         logger.info(f"Loading model from {args.init_checkpoint}")
         reader.load_saved(model, args.init_checkpoint, exact=False, map_location="cpu")
+    if ranks is not None:
+        torch.cuda.set_device(device)
     model.to(device).eval()
     table = None
     if pieces is not None and (args.do_predict or args.do_test):
-        table = qa_eval.score_table(model, pieces.to(device), args.max_ans_len)
+        table = qa_eval.score_table(model, pieces.to(device), args.max_ans_len, **({"world": world} if world is not None else {}))
     if args.do_predict:
         if pieces is not None:
             metrics, best_res = qa_eval.predict_metrics(pieces, table, tokenizer, args.sp_pred, logger, fixed_thresh=0.8)
         else:
             chains, gold = run_batches(model, loader, args, final=False)
             metrics, best_res = qa_data.predict_metrics(chains, gold, args.sp_pred, logger, fixed_thresh=0.8)
-        if args.save_prediction != "":
+        if args.save_prediction != "" and rank == 0:
             with open(args.save_prediction, "w") as f:
                 json.dump(best_res, f)
         logger.info(f"test performance {metrics}")
@@ -411,9 +547,11 @@ def main(argv=None):
         else:
             chains, _ = run_batches(model, loader, args, final=True)
             results = qa_data.final_results(chains, weight=0.8)
-        if args.save_prediction != "":
+        if args.save_prediction != "" and rank == 0:
             with open(args.save_prediction, "w") as f:
                 json.dump(results, f)
+    if ranks is not None:
+        ranks.close()
 
 
 if __name__ == "__main__":
