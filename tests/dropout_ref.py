@@ -38,7 +38,13 @@ M0, M1 = 0xD2511F53, 0xCD9E8D57
 W0, W1 = 0x9E3779B9, 0xBB67AE85
 MASK32 = np.uint64(0xffffffff)
 
-MUTATIONS = ("mask_transposed", "mask_next_head", "mask_next_sequence", "no_mask_sweep0", "no_scale_dv", "byte_swapped", "cls_row1")
+MUTATIONS = ("mask_transposed", "mask_next_head", "mask_next_sequence", "no_mask_sweep0", "no_scale_dv", "byte_swapped", "cls_row1", "bh_stride_2",
+             "fwd_no_rescale")
+# the defects that change the mask itself (attn_masks); the others change what emulate() does with the correct one
+MASK_MUTATIONS = ("mask_transposed", "mask_next_head", "mask_next_sequence", "byte_swapped", "cls_row1", "bh_stride_2")
+# the defects written for the training geometry (more than two heads, more than three chunks), with host cases of their own in
+# tests/test_dropout_host.py: bh_stride_2 is the correct mask at two heads
+GEOMETRY_MUTATIONS = ("bh_stride_2", "fwd_no_rescale")
 
 # the lengths the bound tests pack into one call, and those of the mask read-out (4-blocks, 16-row tiles, 64-row chunks and owner blocks, the top of
 # the counter range at L = 512)
@@ -103,26 +109,73 @@ def attn_keep(i, j, bh, T, seed, site, swapped=False):
     return byte_of(seed, i >> 2, j >> 2, bh, site, k) >= T
 
 
+def attn_keep_blocks(i0, ni, j0, nj, bh, T, seed, site, swapped=False):
+    """bool [len(bh), ni, nj]: attn_keep(i0 + a, j0 + c, bh[k]) at [k, a, c], from ONE generator call per 4 x 4 block of (query, key) and all
+    the (sequence, head) numbers bh at once: the 16 bytes of counter (i >> 2, j >> 2, bh, site) are the block's, byte 4 (i & 3) + (j & 3)."""
+    bh = np.asarray(bh, np.int64)
+    ib, jb = np.arange(i0 >> 2, ((i0 + ni - 1) >> 2) + 1), np.arange(j0 >> 2, ((j0 + nj - 1) >> 2) + 1)
+    by = call_bytes(seed, ib[None, :, None], jb[None, None, :], bh[:, None, None], site)   # [bh, i >> 2, j >> 2, 16]
+    by = by.reshape(len(bh), len(ib), len(jb), 4, 4)                                       # [..., i & 3, j & 3] (swapped: [..., j & 3, i & 3])
+    by = by.transpose(0, 1, 4, 2, 3) if swapped else by.transpose(0, 1, 3, 2, 4)
+    by = by.reshape(len(bh), 4 * len(ib), 4 * len(jb))
+    return by[:, i0 - 4 * int(ib[0]):i0 - 4 * int(ib[0]) + ni, j0 - 4 * int(jb[0]):j0 - 4 * int(jb[0]) + nj] >= T
+
+
+def mask_counter(b, heads, mutation=None):
+    """int64 [heads]: the (sequence, head) numbers b * heads + h of sequence b, the counter's third word; mutation: the defects of MUTATIONS that
+    sit in this word."""
+    h = np.arange(heads, dtype=np.int64)
+    if mutation == "bh_stride_2":
+        return b * 2 + h
+    return b * heads + h + {"mask_next_head": 1, "mask_next_sequence": heads}.get(mutation, 0)
+
+
 def attn_masks(cu, heads, mode, T, seed, site, mutation=None):
     """per sequence (None for an empty one) the factors m as float64 [heads, nq, n], nq = 1 in mode 3. mutation: the mask-side defects of
-    MUTATIONS."""
+    MUTATIONS (every other name: the correct mask). One generator call per 4 x 4 block (attn_keep_blocks); attn_keep is the per-element
+    statement of the same mapping, and tests/test_dropout_host.py shows the two equal."""
     out = []
     for b in range(len(cu) - 1):
         n = int(cu[b + 1] - cu[b])
         if n == 0:
             out.append(None)
             continue
-        qi = np.arange(1 if mode == 3 else n)[:, None]
-        if mode == 3 and mutation == "cls_row1":
-            qi = qi + 1
-        kj = np.arange(n)[None, :]
-        ms = []
-        for h in range(heads):
-            bh = b * heads + h + {"mask_next_head": 1, "mask_next_sequence": heads}.get(mutation, 0)
-            keep = attn_keep(kj, qi, bh, T, seed, site) if mutation == "mask_transposed" else attn_keep(qi, kj, bh, T, seed, site, mutation == "byte_swapped")
-            ms.append(keep.astype(np.float64) * float(scale(T)))
-        out.append(np.stack(ms))
+        q0, nq = (1 if mutation == "cls_row1" else 0, 1) if mode == 3 else (0, n)
+        bh = mask_counter(b, heads, mutation)
+        if mutation == "mask_transposed":   # m_ij read at (j, i)
+            keep = attn_keep_blocks(0, n, q0, nq, bh, T, seed, site).transpose(0, 2, 1)
+        else:
+            keep = attn_keep_blocks(q0, nq, 0, n, bh, T, seed, site, mutation == "byte_swapped")
+        out.append(keep.astype(np.float64) * float(scale(T)))
     return out
+
+
+def onehot_pattern(expected, dctx, cu, heads, mode, keep):
+    """The bit-known outputs under oracle.attention_oracle.onehot(lens, heads, seed) = (qkv, cu, expected) and T = 128: the fp16-rounded p is
+    a permutation matrix pi and the factor is exactly 2, so ctx[i] = fp16(2 V[pi(i)]) where (i, pi(i)) is kept and +0 where it is dropped, and
+    dV[pi(i)] = fp16(2 dO[i]) or 0 likewise (mode 3: i = 0 alone; every other dV row is 0). keep: per sequence bool [heads, nq, n] (None for an
+    empty one). (ctx float16, dV float16 [T, hidden], pairs kept, pairs): columns 0 and 1 of a head's V rows spell the key, which gives pi
+    from `expected`."""
+    hidden = 64 * heads
+    ctx = np.zeros(((len(cu) - 1) if mode == 3 else int(cu[-1]), hidden), np.float16)
+    dV = np.zeros((int(cu[-1]), hidden), np.float16)
+    e = expected.astype(np.float64)
+    kept, pairs = 0, 0
+    for b in range(len(cu) - 1):
+        lo, n = int(cu[b]), int(cu[b + 1] - cu[b])
+        if n == 0:
+            continue
+        q = np.arange(1 if mode == 3 else n)
+        for h in range(heads):
+            cols = slice(64 * h, 64 * h + 64)
+            pi = np.rint((-e[lo:lo + n, 64 * h + 1] * 8 - 1) * 32 + e[lo:lo + n, 64 * h] * 8 - 1).astype(np.int64)
+            assert sorted(pi) == list(range(n))
+            k = keep[b][h, q, pi[q]][:, None]
+            dO = (dctx[b:b + 1] if mode == 3 else dctx[lo:lo + n])[:, cols]
+            (ctx[b:b + 1] if mode == 3 else ctx[lo:lo + n])[:, cols] = np.where(k, np.float16(2) * expected[lo + q, cols], np.float16(0))
+            dV[lo + pi[q], cols] = np.where(k, np.float16(2) * dO, np.float16(0))
+            kept, pairs = kept + int(k.sum()), pairs + len(q)
+    return ctx, dV, kept, pairs
 
 
 # ---- the fp64 model and the bound ----------------------------------------------------------------------------------------------------------
@@ -244,7 +297,9 @@ def emulate(qkv, dctx, cu, heads, mode, T, seed, site, mutation=None):
 
     mutation (None: the correct dataflow) switches ONE defect on: mask_transposed: m_ij read at (j, i); mask_next_head / mask_next_sequence: the
     mask of head h + 1 / of sequence b + 1; no_mask_sweep0: delta from the unmasked dP; no_scale_dv: dV from p o keep without the scale;
-    byte_swapped: the byte index 4 (j & 3) + (i & 3); cls_row1: mode 3 reads the mask of query 1."""
+    byte_swapped: the byte index 4 (j & 3) + (i & 3); cls_row1: mode 3 reads the mask of query 1; bh_stride_2: the counter's third word is
+    b * 2 + h (the correct mask at two heads, by construction); fwd_no_rescale: the FORWARD's running sum is l_run + csum without the alpha,
+    so its lse, and with it ctx, is wrong wherever a later chunk raises the maximum (mode 0; the backward keeps its own, correct sweep 0)."""
     assert mode in (0, 3) and (mutation is None or mutation in MUTATIONS)
     f32 = np.float32
     masks = attn_masks(cu, heads, mode, T, seed, site, mutation)
@@ -275,22 +330,27 @@ def emulate(qkv, dctx, cu, heads, mode, T, seed, site, mutation=None):
                 m_run = np.full((heads, nq, 1), -np.inf, f32)
                 l_run = np.zeros((heads, nq, 1), f32)
                 d_run = np.zeros((heads, nq, 1), f32)
+                l_fwd = np.zeros((heads, nq, 1), f32)   # the forward's own running sum: l_run, but for fwd_no_rescale
                 for c0 in range(0, n, CHUNK):
                     sc, dc = s[:, :, c0:c0 + CHUNK], dP0[:, :, c0:c0 + CHUNK]
                     m_new = np.maximum(m_run, sc.max(axis=2, keepdims=True))
                     alpha = exp2_32((m_run - m_new) * LOG2E32)
                     e = exp2_32(fma32(sc, LOG2E32, -m_new * LOG2E32))
-                    l_run = l_run * alpha + e.sum(axis=2, keepdims=True, dtype=f32)
+                    csum = e.sum(axis=2, keepdims=True, dtype=f32)
+                    l_run = l_run * alpha + csum
+                    l_fwd = (l_fwd if mutation == "fwd_no_rescale" else l_fwd * alpha) + csum
                     d_run = d_run * alpha + (e * dc).sum(axis=2, keepdims=True, dtype=f32)
                     m_run = m_new
                 lse = m_run + np.log(l_run).astype(f32)
                 delta = d_run / l_run
                 p = exp2_32((s - lse) * LOG2E32)
+                p_fwd = exp2_32((s - (m_run + np.log(l_fwd).astype(f32))) * LOG2E32)
             dS16 = (p * (dP - delta)).astype(np.float16).astype(f32)
             Pd16 = (p * m).astype(np.float16).astype(f32)
+            Pc16 = Pd16 if mode == 3 else (p_fwd * m).astype(np.float16).astype(f32)   # the forward's operand of ctx
             Pv16 = (p * (m != 0)).astype(np.float16).astype(f32) if mutation == "no_scale_dv" else Pd16
         with np.errstate(over="ignore"):
-            c, dQ, dK, dV = (x.astype(np.float16) for x in (Pd16 @ V, (dS16 @ K) * f32(0.125), (agr._T(dS16) @ Q) * f32(0.125), agr._T(Pv16) @ dO))
+            c, dQ, dK, dV = (x.astype(np.float16) for x in (Pc16 @ V, (dS16 @ K) * f32(0.125), (agr._T(dS16) @ Q) * f32(0.125), agr._T(Pv16) @ dO))
         _store_ctx(ctx, cu, b, heads, mode, c)
         agr._store(dqkv, cu, b, heads, dQ, dK, dV)
     return ctx, dqkv

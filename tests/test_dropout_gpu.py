@@ -2,8 +2,13 @@
 for bit, the row kernel's output bits, the mask of EVERY (sequence, head, query, key) read out of the attention kernels, and the training
 forward and its backward against the fp64 model inside the derived bound. No tolerance here was read off a device. Every output buffer starts as
 a finite sentinel between guard rows, which must keep their bits.
+
+The bound and the one-hot cases run at two heads and five short lengths, and again at the geometry training uses: 12 and 16 heads, L = 512, the
+edge lengths of tests/attention_grad_ref.py in one ragged call (eight chunks, eight owner blocks, row strides of 3 x 768 and 3 x 1024 halves, a
+mask counter in the hundreds); the row kernel at 2051 rows of 768 and 1024. Almost all of a case's time is its fp64 reference on the host.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -50,13 +55,17 @@ def rows_call(x, T, seed, site, y, y16=None, add16=None, rows=None, M=None, N=No
                                           x.shape[1] if N is None else N, T, seed, site, ptr(y), ptr(y16), 0, _lib.current_stream_ptr())
 
 
-@pytest.mark.parametrize("p", [0.1, 0.5])
-@pytest.mark.parametrize("x16", [True, False], ids=["fp16", "fp32-also16"])
-@pytest.mark.parametrize("N", [64, 192])
-@pytest.mark.parametrize("M", [1, 5, 67])
+# The small grid, then the widths training calls it at: 2051 rows of 768 and 1024 are 385 and 513 workgroups, the last one partial, where the
+# small grid has at most four; a thread's (row, group) comes from a division of an index that runs past 131 000.
+ROWS_WIDE = [(2051, 768), (2051, 1024)]
+ROWS_GRID = ([(M, N, x16, p) for p in (0.1, 0.5) for x16 in (True, False) for N in (64, 192) for M in (1, 5, 67)] +
+             [(M, N, x16, 0.1) for x16 in (True, False) for M, N in ROWS_WIDE])
+
+
+@pytest.mark.parametrize("M,N,x16,p", ROWS_GRID, ids=[f"{M}-{N}-{'fp16' if x16 else 'fp32-also16'}-{p}" for M, N, x16, p in ROWS_GRID])
 def test_rows_forward_bits(M, N, x16, p):
     """y bits == x * m in numpy from the replica's mask; fp32: y16 == fp16(y32); with a row count, the rows behind it and the guards keep the
-    sentinel; an inf at a dropped position gives NaN."""
+    sentinel (the wide cases: also a count of 0, for which nothing is written); an inf at a dropped position gives NaN."""
     _lib, _, dropout = libs()
     T = dropout.threshold(p)
     dt, tdt = (np.float16, torch.float16) if x16 else (np.float32, torch.float32)
@@ -69,7 +78,7 @@ def test_rows_forward_bits(M, N, x16, p):
     with np.errstate(invalid="ignore"):
         want = (x.astype(np.float32) * m).astype(dt)
     assert np.isnan(want[at])
-    for valid in sorted({M, max(M - 2, 0)}):
+    for valid in sorted({M, max(M - 2, 0)} | ({0} if (M, N) in ROWS_WIDE else set())):
         y = Guarded(M, (N,), tdt, GUARD, GUARD, name="y")
         y16 = None if x16 else Guarded(M, (N,), torch.float16, GUARD, GUARD, name="y16")
         rows = None if valid == M else torch.tensor([valid], dtype=torch.int32, device="cuda")
@@ -241,16 +250,91 @@ def test_backward_first_query_mask_read_out(lens, heads):
 @pytest.mark.parametrize("family", ["realistic1", "spike16"])
 @pytest.mark.parametrize("mode", [0, 3])
 def test_forward_and_backward_within_the_derived_bound(mode, family, scale, p):
-    heads, lens = 2, ref.LENS_BOUND
+    check_bound(2, max(ref.LENS_BOUND), ref.LENS_BOUND, mode, family, scale, p)
+
+
+@functools.lru_cache(maxsize=1)
+def family_inputs(family, heads, lens):
+    """(qkv, cu) of a family over the lengths `lens` (a tuple), made once for the consecutive cases that differ in scale and p alone (a hundred
+    sequences at twelve heads take longer to draw than to check); nobody writes to them."""
+    return ao.FAMILIES[family](list(lens), heads, 11)
+
+
+def dqkv_locator(cu, heads):
+    """index (row, column) of dqkv -> "sequence b, len n, head h, dQ | dK | dV": the `where` of fp.assert_within"""
+    return lambda at: f"{ao.locator(cu, 1)((at[0], at[1] % (64 * heads)))}, {'dQ dK dV'.split()[at[1] // (64 * heads)]}"
+
+
+def check_bound(heads, L, lens, mode, family, scale, p):
+    """One forward and one backward call over the ragged batch `lens`: EVERY element of ctx and of dqkv inside the derived bound of the fp64 model
+    under the replica's masks. Prints the two worst ratios."""
     T = ref.threshold(p)
-    qkv, cu = ao.FAMILIES[family](lens, heads, 11)
+    qkv, cu = family_inputs(family, heads, tuple(lens))
     dctx = agr.dctx_grid(len(lens) if mode == 3 else int(cu[-1]), 64 * heads, 2, scale)
-    ctx, dqkv = run(qkv, dctx, cu, heads, max(lens), mode, T)
+    ctx, dqkv = run(qkv, dctx, cu, heads, L, mode, T)
     ctx_r, ctx_b, dqkv_r, dqkv_b = ref.reference_and_bound(qkv, dctx, cu, heads, mode, ref.attn_masks(cu, heads, mode, T, SEED, SITE))
-    label = f"mode={mode} family={family} scale={scale} p={p}"
+    label = f"mode={mode} heads={heads} L={L} family={family} scale={scale} p={p}"
     print(f"RATIO {label} ctx {fp.worst_ratio(ctx, ctx_r, ctx_b)[0]:.4f} dqkv {fp.worst_ratio(dqkv, dqkv_r, dqkv_b)[0]:.4f}")
-    fp.assert_within(ctx, ctx_r, ctx_b, "ctx " + label)
-    fp.assert_within(dqkv, dqkv_r, dqkv_b, "dqkv " + label)
+    fp.assert_within(ctx, ctx_r, ctx_b, "ctx " + label, ao.locator(cu, 3 if mode == 3 else 1))
+    fp.assert_within(dqkv, dqkv_r, dqkv_b, "dqkv " + label, dqkv_locator(cu, heads))
+
+
+# The geometry training runs at, which the two heads and five short lengths above do not reach: 12 heads (the retriever) and 16 heads (the
+# answer reader: a row stride of 3 x 1024 halves in qkv and dqkv, 1024 in ctx), L = 512, the lengths -1, 0, +1 around every multiple of the MFMA
+# tile up to 512 in attention_grad_ref's four interleaved groups. A call holds 25 sequences (mode 3: 100), so the forward's and the backward's
+# running (max, sum) go over up to eight chunks of 64 keys -- under stair_up the maximum rises in every one --, the owner blocks 0 .. 7 meet a
+# sequence's end at every tile edge, and the mask counter b * heads + h runs to 24 * 12 + 11 (mode 3: 99 * 12 + 11), where a counter of any
+# other stride in `heads` draws another mask than the replica's. The gradient carries a loss scale of 256, as in training.
+BOUND_TRAINING = [(12, 0, "stair_up", 256.0, 0.1), (12, 1, "realistic4", 256.0, 0.1), (12, 2, "spike16", 256.0, 0.1), (12, 3, "stair_down", 256.0, 0.1),
+                  (12, 1, "realistic4", 1.0, 0.5), (16, 1, "realistic4", 256.0, 0.1), (16, 1, "spike16", 256.0, 0.1)]
+
+
+def scale_id(scale):
+    return {1.0: "unit", 256.0: "x256"}[scale]
+
+
+@pytest.mark.parametrize("heads,group,family,scale,p", BOUND_TRAINING,
+                         ids=[f"h{h}-L512-edges{g}-{f}-{scale_id(s)}-p{p}" for h, g, f, s, p in BOUND_TRAINING])
+def test_every_query_within_the_derived_bound_at_training_geometry(heads, group, family, scale, p):
+    check_bound(heads, 512, agr.LENS_EDGES[group::4], 0, family, scale, p)
+
+
+@pytest.mark.parametrize("p", [0.1, 0.5])
+@pytest.mark.parametrize("scale", [1.0, 256.0], ids=scale_id)
+@pytest.mark.parametrize("family", agr.FAMILY_NAMES)
+@pytest.mark.parametrize("heads,lens", [pytest.param(12, agr.LENS_EDGES, id="h12-L512-edges"), pytest.param(16, agr.LENS_EDGES[1::4], id="h16-L512-edges1")])
+def test_first_query_within_the_derived_bound_at_training_geometry(heads, lens, family, scale, p):
+    """Mode 3: one ragged call of every edge length (100 sequences at 12 heads). The dQ rows behind a sequence's first have bound 0."""
+    check_bound(heads, 512, lens, 3, family, scale, p)
+
+
+# ---- attention: bit-known outputs ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", [0, 3])
+@pytest.mark.parametrize("heads,L,lens", [pytest.param(1, 129, agr.LENS_SWEEP, id="h1-L129-sweep"), pytest.param(12, 512, agr.LENS_EDGES[1::4], id="h12-L512-edges1"),
+                                          pytest.param(16, 512, agr.LENS_EDGES[1::4], id="h16-L512-edges1")])
+def test_onehot_permutation_under_half_dropout_is_bit_known(heads, L, lens, mode):
+    """q_i = code(pi(i)): the fp16-rounded p is exactly a permutation matrix, and at T = 128 the factor is exactly 2. So ctx[i] == fp16(2 V[pi(i)])
+    where the replica keeps (i, pi(i)) and +0 where it drops it, and dV[pi(i)] == fp16(2 dO[i]) or 0 likewise, bit for bit: the query -> key ->
+    mask byte map of every tile, chunk, lane slot, owner block, head and sequence at once, where a bound can only say it loosely. dQ and dK stay
+    within the derived bound. Mode 3 (the first query: ctx[b], and dV in row pi(0)) gives the same pattern -- e = 1, inv = 1 and m = 2 make its
+    two products exact, as tests/test_dropout_host.py shows on the emulation; its dK and dV rows are single products, whose zero takes the
+    operands' signs, so dV compares there with -0 counted as +0."""
+    qkv, cu, expected = ao.onehot(lens, heads, 3)
+    hidden = 64 * heads
+    dctx = agr.dctx_grid(len(lens) if mode == 3 else int(cu[-1]), hidden, 4)
+    ctx, dqkv = run(qkv, dctx, cu, heads, L, mode, 128)
+    masks = ref.attn_masks(cu, heads, mode, 128, SEED, SITE)
+    ctx_w, dV_w, kept, pairs = ref.onehot_pattern(expected, dctx, cu, heads, mode, [m != 0 for m in masks])
+    assert 0.3 * pairs < kept < 0.7 * pairs, (kept, pairs)   # both outcomes are well populated
+    bad = np.argwhere(bits(ctx) != bits(ctx_w))
+    assert not len(bad), ("ctx", len(bad), bad[0], ao.locator(cu, 3 if mode == 3 else 1)(bad[0]), float(ctx[tuple(bad[0])]), float(ctx_w[tuple(bad[0])]))
+    dV = dqkv[:, 2 * hidden:] + np.float16(0) if mode == 3 else dqkv[:, 2 * hidden:]
+    bad = np.argwhere(bits(dV) != bits(dV_w))
+    assert not len(bad), ("dV", len(bad), bad[0], ao.locator(cu, 1)(bad[0]), float(dV[tuple(bad[0])]), float(dV_w[tuple(bad[0])]))
+    _, _, dqkv_r, dqkv_b = ref.reference_and_bound(qkv, dctx, cu, heads, mode, masks)
+    label = f"mode={mode} heads={heads} L={L} family=onehot p=0.5"
+    print(f"RATIO {label} kept {kept} of {pairs} dQ|dK {fp.worst_ratio(dqkv[:, :2 * hidden], dqkv_r[:, :2 * hidden], dqkv_b[:, :2 * hidden])[0]:.4f}")
+    fp.assert_within(dqkv[:, :2 * hidden], dqkv_r[:, :2 * hidden], dqkv_b[:, :2 * hidden], "dQ | dK " + label, dqkv_locator(cu, heads))
 
 
 # ---- attention: edge cases -------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """CPU (-m "not gpu"): the host restatement of dropout (tests/dropout_ref.py) -- the generator's known answers and drop rate, the fp64 model
-against torch.autograd, the emulation of the kernels' dataflow inside the derived bound and every mutation outside it -- and the agreement of
-include/mdr_dropout.h, dropout.SIGNATURES and the built library."""
+against torch.autograd, the emulation of the kernels' dataflow inside the derived bound and every mutation outside it, the block-wise mask
+builder against the per-element mapping, the one-hot family's bit-known pattern under p = 0.5, the two defects that need more than two heads
+or a rising maximum -- and the agreement of include/mdr_dropout.h, dropout.SIGNATURES and the built library."""
 import ctypes
 import os
 import re
@@ -130,7 +131,8 @@ def test_emulation_inside_the_bound_at_the_gpu_tests_lengths(mode, family, scale
     assert worst <= 1.0
 
 
-@pytest.mark.parametrize("mode,mutation", [(mode, mu) for mode in (0, 3) for mu in ref.MUTATIONS if mode == 3 or mu != "cls_row1"])
+@pytest.mark.parametrize("mode,mutation", [(mode, mu) for mode in (0, 3) for mu in ref.MUTATIONS
+                                           if mu not in ref.GEOMETRY_MUTATIONS and (mode == 3 or mu != "cls_row1")])
 def test_every_mutation_leaves_the_bound(mode, mutation):
     for p in (0.1, 0.5):
         qkv, dctx, cu, heads = _case(mode, "realistic1", 1.0)
@@ -138,6 +140,148 @@ def test_every_mutation_leaves_the_bound(mode, mutation):
         want = ref.reference_and_bound(qkv, dctx, cu, heads, mode, ref.attn_masks(cu, heads, mode, T, SEED, SITE))
         worst = _worst(ref.emulate(qkv, dctx, cu, heads, mode, T, SEED, SITE, mutation), want)
         assert worst > 1.0, (mutation, mode, p, worst)
+
+
+# ---- the block-wise mask builder -------------------------------------------------------------------------------------------------------------
+def _masks_per_element(cu, heads, mode, T, mutation=None):
+    """attn_masks as attn_keep states it: one generator call per (query, key) element."""
+    out = []
+    for b in range(len(cu) - 1):
+        n = int(cu[b + 1] - cu[b])
+        if n == 0:
+            out.append(None)
+            continue
+        qi = np.arange(1 if mode == 3 else n)[:, None] + (1 if (mode == 3 and mutation == "cls_row1") else 0)
+        kj = np.arange(n)[None, :]
+        ms = []
+        for h in range(heads):
+            bh = b * 2 + h if mutation == "bh_stride_2" else b * heads + h + {"mask_next_head": 1, "mask_next_sequence": heads}.get(mutation, 0)
+            keep = (ref.attn_keep(kj, qi, bh, T, SEED, SITE) if mutation == "mask_transposed" else
+                    ref.attn_keep(qi, kj, bh, T, SEED, SITE, mutation == "byte_swapped"))
+            ms.append(keep.astype(np.float64) * float(ref.scale(T)))
+        out.append(np.stack(ms))
+    return out
+
+
+@pytest.mark.parametrize("mutation", (None,) + ref.MASK_MUTATIONS)
+@pytest.mark.parametrize("mode", [0, 3])
+def test_block_wise_masks_are_the_per_element_mapping(mode, mutation):
+    """attn_masks makes one generator call per 4 x 4 block; attn_keep one per element. Equal for every length of the mask read-out (a sequence of
+    length 0 between them), three heads (so that bh_stride_2 is not the identity), both thresholds, and under every mask-side mutation."""
+    heads = 3
+    lens = ref.LENS_READOUT[:4] + [0] + ref.LENS_READOUT[4:]
+    cu = np.concatenate([[0], np.cumsum(lens)])
+    for T in (26, 128):
+        got, want = ref.attn_masks(cu, heads, mode, T, SEED, SITE, mutation), _masks_per_element(cu, heads, mode, T, mutation)
+        assert len(got) == len(want) == len(lens)
+        for b, n in enumerate(lens):
+            if n == 0:
+                assert got[b] is None and want[b] is None
+                continue
+            assert got[b].dtype == want[b].dtype and got[b].shape == want[b].shape == (heads, 1 if mode == 3 else n, n)
+            assert np.array_equal(got[b], want[b]), (b, n, np.argwhere(got[b] != want[b])[0])
+    if mutation is not None and not (mode == 0 and mutation == "cls_row1"):
+        plain = ref.attn_masks(cu, heads, mode, 128, SEED, SITE)
+        assert any(not np.array_equal(a, b) for a, b in zip(got, plain) if a is not None), "the mutation left every mask as it was"
+    assert set(ref.MASK_MUTATIONS) <= set(ref.MUTATIONS)
+
+
+# ---- the one-hot family under p = 0.5 --------------------------------------------------------------------------------------------------------
+def _onehot_case(lens, heads, mode):
+    qkv, cu, expected = ao.onehot(lens, heads, 3)
+    dctx = agr.dctx_grid(len(lens) if mode == 3 else int(cu[-1]), 64 * heads, 4)
+    return qkv, cu, expected, dctx
+
+
+def _onehot_mismatches(got, want):
+    """(ctx elements whose bits differ, dV elements that differ): ctx bit for bit; dV bit for bit in mode 0 -- a sum from +0 -- and, as single
+    products in mode 3, with -0 counted as +0 (`want` carries +0)"""
+    (ctx, dqkv), (ctx_w, dV_w, mode) = got, want
+    dV = dqkv[:, 2 * ctx_w.shape[1]:]
+    if mode == 3:
+        dV = dV + np.float16(0)
+    return int((fp.bits(ctx) != fp.bits(ctx_w)).sum()), int((fp.bits(dV) != fp.bits(dV_w)).sum())
+
+
+@pytest.mark.parametrize("mode", [0, 3])
+def test_onehot_emulation_gives_the_bit_known_pattern(mode):
+    """With p a permutation matrix and T = 128 the emulated kernels return ctx[i] = 2 V[pi(i)] and dV[pi(i)] = 2 dO[i] where (i, pi(i)) is kept and
+    zero where it is not, bit for bit, at the lengths of the bound tests and two heads (what tests/test_dropout_gpu.py asks of the device at 1, 12
+    and 16 heads). Mode 3 forms p = e * inv and p * m as two products: e = 1, inv = 1 and m = 2 for the winner, so the pattern holds there too;
+    its dV rows are single products, whose zero takes the operands' signs: zero by value."""
+    heads, lens = 2, ref.LENS_BOUND
+    qkv, cu, expected, dctx = _onehot_case(lens, heads, mode)
+    keep = [m != 0 for m in ref.attn_masks(cu, heads, mode, 128, SEED, SITE)]
+    ctx_w, dV_w, kept, pairs = ref.onehot_pattern(expected, dctx, cu, heads, mode, keep)
+    assert 0 < kept < pairs and pairs == heads * (len(lens) if mode == 3 else int(cu[-1]))
+    assert (ctx_w != 0).any() and (dV_w != 0).any()
+    assert _onehot_mismatches(ref.emulate(qkv, dctx, cu, heads, mode, 128, SEED, SITE), (ctx_w, dV_w, mode)) == (0, 0)
+    # the pattern is the mask's: another site's mask does not fit it
+    other = ref.emulate(qkv, dctx, cu, heads, mode, 128, SEED, SITE + 1)
+    assert min(_onehot_mismatches(other, (ctx_w, dV_w, mode))) > 0
+
+
+# ---- the defects that only the training geometry shows ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", [0, 3])
+def test_a_head_stride_of_two_is_invisible_at_two_heads_and_caught_at_twelve(mode):
+    """bh_stride_2 (the counter's third word b * 2 + h): at two heads it IS the correct mask, so every case of two heads passes with it -- shown
+    on the old bound case's inputs. At twelve heads on a short ragged batch it leaves the derived bound and breaks the one-hot pattern."""
+    for p in (0.1, 0.5):
+        qkv, dctx, cu, heads = _case(mode, "realistic1", 1.0)
+        T = ref.threshold(p)
+        for a, b in zip(ref.attn_masks(cu, heads, mode, T, SEED, SITE), ref.attn_masks(cu, heads, mode, T, SEED, SITE, "bh_stride_2")):
+            assert np.array_equal(a, b)
+        got, plain = ref.emulate(qkv, dctx, cu, heads, mode, T, SEED, SITE, "bh_stride_2"), ref.emulate(qkv, dctx, cu, heads, mode, T, SEED, SITE)
+        assert fp.same_bits(got[0], plain[0]) and fp.same_bits(got[1], plain[1])
+    heads, lens = 12, [65, 130, 300]
+    for p in (0.1, 0.5):
+        T = ref.threshold(p)
+        qkv, cu = ao.FAMILIES["realistic1"](lens, heads, 11)
+        dctx = agr.dctx_grid(len(lens) if mode == 3 else int(cu[-1]), 64 * heads, 2)
+        want = ref.reference_and_bound(qkv, dctx, cu, heads, mode, ref.attn_masks(cu, heads, mode, T, SEED, SITE))
+        assert _worst(ref.emulate(qkv, dctx, cu, heads, mode, T, SEED, SITE), want) <= 1.0
+        worst = _worst(ref.emulate(qkv, dctx, cu, heads, mode, T, SEED, SITE, "bh_stride_2"), want)
+        assert worst > 1.0, (mode, p, worst)
+    qkv, cu, expected, dctx = _onehot_case(lens, heads, mode)
+    keep = [m != 0 for m in ref.attn_masks(cu, heads, mode, 128, SEED, SITE)]
+    ctx_w, dV_w, _, _ = ref.onehot_pattern(expected, dctx, cu, heads, mode, keep)
+    assert _onehot_mismatches(ref.emulate(qkv, dctx, cu, heads, mode, 128, SEED, SITE), (ctx_w, dV_w, mode)) == (0, 0)
+    assert min(_onehot_mismatches(ref.emulate(qkv, dctx, cu, heads, mode, 128, SEED, SITE, "bh_stride_2"), (ctx_w, dV_w, mode))) > 0
+
+
+def test_a_forward_sum_without_the_rescale_leaves_the_bound_under_a_rising_maximum():
+    """fwd_no_rescale (the forward's l_run + csum without alpha): under stair_up the maximum rises by 16 in every chunk of 64 keys, so over five
+    and eight chunks lse is too large by about log(chunks) and ctx too small by that factor; the backward keeps its own sweep 0, so dqkv keeps
+    its bits. Mode 3 has no running sum: the mutation changes nothing there.
+
+    Do the old LENS_BOUND inputs (two heads, at most three chunks, realistic1 and spike16) catch it too? Computed below, not assumed: YES, both
+    do (ctx lands 473 and 782 bounds away: the lengths 65 and 130 have rows whose maximum sits in a later chunk). So a value comparison of two or
+    three chunks already sees this defect; what the longer cases add is the rescale chained over five to eight chunks, which the mutant misses
+    by 353 bounds here."""
+    heads, lens, mode, T = 2, [300, 512], 0, 26
+    qkv, cu = ao.FAMILIES["stair_up"](lens, heads, 11)
+    dctx = agr.dctx_grid(int(cu[-1]), 64 * heads, 2)
+    want = ref.reference_and_bound(qkv, dctx, cu, heads, mode, ref.attn_masks(cu, heads, mode, T, SEED, SITE))
+    plain = ref.emulate(qkv, dctx, cu, heads, mode, T, SEED, SITE)
+    got = ref.emulate(qkv, dctx, cu, heads, mode, T, SEED, SITE, "fwd_no_rescale")
+    assert _worst(plain, want) <= 1.0
+    ctx_ratio = fp.worst_ratio(got[0], want[0], want[1])[0]
+    print(f"RATIO fwd_no_rescale stair_up lens={lens}: ctx {ctx_ratio:.1f}")
+    assert ctx_ratio > 1.0 and fp.same_bits(got[1], plain[1])
+    for b, n in enumerate(lens):   # every sequence of five or more chunks by itself
+        rows = slice(int(cu[b]), int(cu[b + 1]))
+        assert n > 4 * ref.CHUNK and fp.worst_ratio(got[0][rows], want[0][rows], want[1][rows])[0] > 1.0
+    caught = {}
+    for family in ("realistic1", "spike16"):
+        qkv, dctx, cu, heads = _case(0, family, 1.0)
+        want = ref.reference_and_bound(qkv, dctx, cu, heads, 0, ref.attn_masks(cu, heads, 0, T, SEED, SITE))
+        got = ref.emulate(qkv, dctx, cu, heads, 0, T, SEED, SITE, "fwd_no_rescale")
+        caught[family] = fp.worst_ratio(got[0], want[0], want[1])[0]
+        print(f"RATIO fwd_no_rescale LENS_BOUND {family}: ctx {caught[family]:.1f}")
+    assert caught["realistic1"] > 1.0 and caught["spike16"] > 1.0, caught
+    qkv, dctx, cu, heads = _case(3, "realistic1", 1.0)
+    a, b = ref.emulate(qkv, dctx, cu, heads, 3, T, SEED, SITE), ref.emulate(qkv, dctx, cu, heads, 3, T, SEED, SITE, "fwd_no_rescale")
+    assert fp.same_bits(a[0], b[0]) and fp.same_bits(a[1], b[1])
 
 
 def test_header_binding_and_library_agree():
